@@ -5,7 +5,7 @@ root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/compact_keep.txt; : > "$out"
 wl=${1:-dvbs2}
 run() {
-    env "$@" python "$root/bench.py" --no-cpu-baseline --frame-loop-steps 0 --as-shipped-steps 0 --reps 0 --steps 5 --workload $wl --mode shipped 2>/dev/null | python -c "
+    env "$@" python "$root/bench.py" --full --no-cpu-baseline --frame-loop-steps 0 --as-shipped-steps 0 --reps 0 --steps 5 --workload $wl --mode shipped 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$wl $*: %.1f k cw/s' % (d['value']/1e3), 'ms/step %.2f' % d['ms_per_step'], 'layout %.2f fused %.2f' % (d['kernel_ms_per_step']['layout'], d['kernel_ms_per_step']['fused_pass']))" >> "$out"

@@ -7,7 +7,7 @@ for B in 512 1024 1536 2048 4096 32768; do
   for V in lib lib_variants/cache_default; do
     [ -f "$R/lut_ldpc_amd/$V/liblut_ldpc_amd.so" ] || continue
     steps=$(( 32768 / B * 3 )); [ $steps -lt 6 ] && steps=6
-    LUTLDPC_LIB=$R/lut_ldpc_amd/$V/liblut_ldpc_amd.so python3 "$R/bench.py" --batch $B --steps $steps --warmup 3 --no-cpu-baseline --no-configs --frame-loop-steps 0 --as-shipped-steps 0 --reps 0 \
+    LUTLDPC_LIB=$R/lut_ldpc_amd/$V/liblut_ldpc_amd.so python3 "$R/bench.py" --full --batch $B --steps $steps --warmup 3 --no-cpu-baseline --no-configs --frame-loop-steps 0 --as-shipped-steps 0 --reps 0 \
       > "$OUT/b${B}_$(basename $V).json" 2> "$OUT/b${B}_$(basename $V).err" || { echo "failed B=$B $V"; tail -3 "$OUT/b${B}_$(basename $V).err"; }
     python3 - "$OUT/b${B}_$(basename $V).json" $B $V <<'PY'
 import json,sys

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 run() {  # name, counters...
     local name=$1; shift
-    rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$R/$OUT/$name" -- python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events $BENCH_ARGS > "$R/$OUT/$name.log" 2>&1
+    rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$R/$OUT/$name" -- python3 "$R/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events $BENCH_ARGS > "$R/$OUT/$name.log" 2>&1
 }
 run sq_a SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS
 run sq_b SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR

@@ -5,7 +5,7 @@ root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/shipped_snr.txt; : > "$out"
 wl=${1:-dvbs2}; shift
 for snr in ${@:-1.11 1.5 2.0 3.0 4.0}; do
-    python "$root/bench.py" --no-cpu-baseline --frame-loop-steps 2 --reps 0 --steps 5 --workload $wl --mode shipped --snr $snr 2>/dev/null | python -c "
+    python "$root/bench.py" --full --no-cpu-baseline --frame-loop-steps 2 --reps 0 --steps 5 --workload $wl --mode shipped --snr $snr 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$wl snr $snr: %.1f k cw/s' % (d['value']/1e3), 'iters %.2f' % d['config']['mean_iterations_executed'], 'ms/step %.2f' % d['ms_per_step'],
