@@ -151,6 +151,23 @@ int lutldpc_decoder_sim_batch(lutldpc_decoder *d, const lutldpc_channel_cells *c
                               uint64_t frame0, int B, const uint8_t *codewords, int K_info, int32_t *frame_stats,
                               uint8_t *cha_out, uint8_t *bits_out);
 
+/* Random codewords made on the device (LDPC.zero_codeword = false).  The codeword of frame f is a pure function of
+ * (seed, stream, f): information bits from Philox4x32-10 with key = seed, counter = (f lo, f hi, k/128, stream | 0x80000000)
+ * (bit k = bit k%32 of output word (k%128)/32, as random_info_bits of the host driver), parity bit i = popcount(A_i & u) mod 2
+ * over the generator's dense parity rows; codeword = [u | parity] in the decoder's column order.
+ *
+ * set_generator: rows = R rows of ceil(K/64) words (bit j of word w = information bit 64w + j), K + R = nvar; copied to the
+ *   device, replaces an earlier generator.  ERR_ARG: rows NULL or K + R != nvar; ERR_STATE: host-only handle;
+ *   ERR_UNSUPPORTED: K > 8192.  describe() gains "generator": {"K":.., "R":..}.
+ * encode_random: the codewords of frames frame0 .. frame0+B-1; codewords = host [B*nvar] bytes (0/1), or NULL to keep
+ *   them on the device only.  ERR_STATE without a generator.
+ * sim_batch_random: lutldpc_decoder_sim_batch with those codewords as the sent ones (same seed / stream for the info bits
+ *   and the channel): no host encoding, no upload.  ERR_STATE without a generator. */
+int lutldpc_decoder_set_generator(lutldpc_decoder *d, int K, int R, const uint64_t *rows);
+int lutldpc_decoder_encode_random(lutldpc_decoder *d, uint64_t seed, uint32_t stream, uint64_t frame0, int B, uint8_t *codewords);
+int lutldpc_decoder_sim_batch_random(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream,
+                                     uint64_t frame0, int B, int K_info, int32_t *frame_stats, uint8_t *cha_out, uint8_t *bits_out);
+
 /* The labels the sampler would produce for those frames (host, frame-major [B*nvar]); for tests. */
 int lutldpc_decoder_sample_labels(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream,
                                   uint64_t frame0, int B, const uint8_t *codewords, uint8_t *cha, uint8_t *msg0);

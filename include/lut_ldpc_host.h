@@ -67,10 +67,14 @@ int lutldpc_codec_encode(lutldpc_codec *c, const uint8_t *info, uint8_t *codewor
 /* One batch of the Monte-Carlo loop (front end + decode + error counting on the device) at Eb/N0
  * snr_db: frames frame0 .. frame0+B-1 of stream `stream` (= index of the SNR point).  The channel
  * cells are derived from the codec's boundaries; with zero_codeword = 0 the data bits come from the
- * Philox stream and are encoded on the host (needs with_generator).  stats: host [B*4] int32 as in
- * lutldpc_decoder_sim_batch. */
+ * Philox stream and are encoded on the device (lutldpc_decoder_sim_batch_random; needs with_generator;
+ * generators of more than 8192 information bits stay on the host encoder).  stats: host [B*4] int32 as
+ * in lutldpc_decoder_sim_batch. */
 int lutldpc_codec_sim_batch(lutldpc_codec *c, double snr_db, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
                             int zero_codeword, int32_t *stats);
+/* the random codewords of frames frame0 .. frame0+B-1 as sim_batch(zero_codeword = 0) sends them, made on the device:
+ * host [B*nvar] bytes (lutldpc_decoder_encode_random); ERR_STATE without a generator on the device */
+int lutldpc_codec_encode_random(lutldpc_codec *c, uint64_t seed, uint32_t stream, uint64_t frame0, int B, uint8_t *codewords);
 /* the labels (and sent codewords, may be NULL) of those frames, for tests */
 int lutldpc_codec_sample_labels(lutldpc_codec *c, double snr_db, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
                                 int zero_codeword, uint8_t *cha, uint8_t *msg0, uint8_t *codewords);

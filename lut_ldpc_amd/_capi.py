@@ -59,6 +59,9 @@ _SIGNATURES = {
     "lutldpc_decoder_decode_batch_trace": (C.c_int, [_vp, _u8p, _u8p, C.c_int, C.c_int, _u8p, _ip, _u8p, C.c_int64, _ip]),
     "lutldpc_selftest_jit_source": (C.c_int64, [_vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int64, C.c_int]),
     "lutldpc_selftest_resident_source": (C.c_int64, [_vp, C.c_int, C.c_char_p, C.c_int64, C.c_int, C.POINTER(C.c_int32)]),
+    "lutldpc_decoder_set_generator": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
+    "lutldpc_decoder_encode_random": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p]),
+    "lutldpc_decoder_sim_batch_random": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, _ip, _u8p, _u8p]),
 }
 for _name, (_res, _args) in _SIGNATURES.items():
     if hasattr(lib, _name):
@@ -113,6 +116,7 @@ _u64p, _i64p = C.POINTER(C.c_uint64), C.POINTER(C.c_int64)
 _SIM_SIGNATURES = {
     "lutldpc_codec_sim_batch": (C.c_int, [_vp, C.c_double, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, _ip]),
     "lutldpc_codec_sample_labels": (C.c_int, [_vp, C.c_double, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, _u8p, _u8p, _u8p]),
+    "lutldpc_codec_encode_random": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p]),
     "lutldpc_codec_channel_cells": (C.c_int, [_vp, C.c_double, _u64p, _u8p, _u8p, _u8p, _u8p, _u8p]),
     "lutldpc_ber_sim_run": (C.c_int, [_cp, _cp, C.c_int, _cp, C.c_int, C.c_int, C.c_int, _dp, _i64p, C.c_int]),
     "lutldpc_ber_sim_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),

@@ -160,6 +160,13 @@ class Codec:
                                               _p(cha, C.c_uint8), _p(msg, C.c_uint8), _p(cw, C.c_uint8)))
         return cha, msg, cw
 
+    def encode_random(self, seed, stream, frame0, B) -> np.ndarray:
+        """The random codewords of frames frame0..frame0+B-1 that sim_batch(zero_codeword=False) sends, made on the device
+        (Philox information bits + generator parity): (B, nvar) uint8."""
+        cw = np.empty((B, self.nvar), np.uint8)
+        check(lib.lutldpc_codec_encode_random(self._h, int(seed), int(stream), int(frame0), int(B), _p(cw, C.c_uint8)))
+        return cw
+
     def channel_cells(self, snr_db):
         thr = np.zeros(72, np.uint64)
         arrs = [np.zeros(72, np.uint8) for _ in range(5)]

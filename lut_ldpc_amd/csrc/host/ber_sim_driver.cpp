@@ -304,9 +304,13 @@ void LDPC_BER_Sim_LUT::sim_batch(double snr, int snr_index, int64_t frame0, int 
     const lutldpc_channel_cells view = cells.view();
     const uint64_t seed = (uint64_t)(int64_t)(rand_seed + rand_seed_offset);      // RNG_reset(rand_seed + rand_seed_offset), :129
     if (!zero_codeword && !encoder_set) throw std::runtime_error("Non zero codewords require the encoder to be set!");
+    // random codewords are made on the device, next to the sampler (the same codewords as random_info_bits + encode: a pure
+    // function of (seed, SNR index, frame)); the message-dump debug path (output_verbosity >= 2) and generators beyond the
+    // device encoder's size keep the host encoder
+    const bool device_codewords = !zero_codeword && decoder_output_verbosity <= 1 && C->has_device_generator();
     std::vector<unsigned char> codewords;
     const uint8_t *cwp = nullptr;
-    if (!zero_codeword) {
+    if (!zero_codeword && !device_codewords) {
         bvec info((size_t)K), cw;
         codewords.resize((size_t)B * N);
         for (int i = 0; i < B; i++) {
@@ -341,9 +345,12 @@ void LDPC_BER_Sim_LUT::sim_batch(double snr, int snr_index, int64_t frame0, int 
     // output_verbosity > 0: the reference prints every frame's labels and decided bits (src/LDPC_Code_LUT.cpp:228-238)
     std::vector<uint8_t> cha_dump, bits_dump;
     if (decoder_output_verbosity > 0) { cha_dump.resize((size_t)B * N); bits_dump.resize((size_t)B * N); }
-    if (lutldpc_decoder_sim_batch(C->device_handle(), &view, seed, (uint32_t)snr_index, (uint64_t)frame0, B, cwp, K, reinterpret_cast<int32_t *>(stats),
-                                  cha_dump.empty() ? nullptr : cha_dump.data(), bits_dump.empty() ? nullptr : bits_dump.data()) != LUTLDPC_OK)
-        throw std::runtime_error(std::string("LDPC_BER_Sim_LUT::sim_snr_point(): ") + lutldpc_last_error());
+    const int rc = device_codewords
+        ? lutldpc_decoder_sim_batch_random(C->device_handle(), &view, seed, (uint32_t)snr_index, (uint64_t)frame0, B, K, reinterpret_cast<int32_t *>(stats),
+                                           cha_dump.empty() ? nullptr : cha_dump.data(), bits_dump.empty() ? nullptr : bits_dump.data())
+        : lutldpc_decoder_sim_batch(C->device_handle(), &view, seed, (uint32_t)snr_index, (uint64_t)frame0, B, cwp, K, reinterpret_cast<int32_t *>(stats),
+                                    cha_dump.empty() ? nullptr : cha_dump.data(), bits_dump.empty() ? nullptr : bits_dump.data());
+    if (rc != LUTLDPC_OK) throw std::runtime_error(std::string("LDPC_BER_Sim_LUT::sim_snr_point(): ") + lutldpc_last_error());
     for (int i = 0; i < B && !cha_dump.empty(); i++) C->print_stimuli(&cha_dump[(size_t)i * N], &bits_dump[(size_t)i * N]);
 }
 

@@ -203,9 +203,20 @@ int lutldpc_codec_sim_batch(lutldpc_codec *c, double snr_db, uint64_t seed, uint
         if (!c || !stats || B <= 0) throw std::invalid_argument("NULL / bad argument");
         const ChannelCellTable cells = cells_for(c, snr_db);
         const lutldpc_channel_cells view = cells.view();
+        // random codewords: made on the device (generators beyond the device encoder's size: on the host, as before)
+        if (!zero_codeword && c->C->has_device_generator())
+            return lutldpc_decoder_sim_batch_random(c->C->device_handle(), &view, seed, stream, frame0, B, c->C->get_ninfo(), stats, nullptr, nullptr);
         std::vector<unsigned char> cw;
         if (!zero_codeword) make_codewords(c, seed, stream, frame0, B, cw);
         return lutldpc_decoder_sim_batch(c->C->device_handle(), &view, seed, stream, frame0, B, zero_codeword ? nullptr : cw.data(), c->C->get_ninfo(), stats, nullptr, nullptr);
+    });
+}
+
+int lutldpc_codec_encode_random(lutldpc_codec *c, uint64_t seed, uint32_t stream, uint64_t frame0, int B, uint8_t *codewords) {
+    return guarded([&] {
+        if (!c || !codewords || B <= 0) throw std::invalid_argument("NULL / bad argument");
+        if (!c->C->has_device_generator()) throw std::logic_error("encode_random: the codec has no generator on the device (with_generator, at most 8192 information bits)");
+        return lutldpc_decoder_encode_random(c->C->device_handle(), seed, stream, frame0, B, codewords);
     });
 }
 

@@ -131,6 +131,7 @@ LDPC_Code_LUT::~LDPC_Code_LUT() { drop_device(); }
 
 void LDPC_Code_LUT::drop_device() {
     if (dev) { lutldpc_decoder_destroy(dev); dev = nullptr; }
+    dev_generator = false;
 }
 
 void LDPC_Code_LUT::set_device(int d) {
@@ -374,6 +375,13 @@ lutldpc_decoder *LDPC_Code_LUT::device_handle() {
                                minLUT ? 1 : 0, vtxt.c_str(), ctxt.c_str(), device, &dev) != LUTLDPC_OK)
         hip_fail("LDPC_Code_LUT: creating the HIP decoder failed");
     if (lutldpc_decoder_set_exit_conditions(dev, max_iters, psc, pisc) != LUTLDPC_OK) hip_fail("LDPC_Code_LUT::set_exit_conditions()");
+    // the generator (built, or loaded with G_A from a codec file) goes with the decoder: random codewords are made on the device
+    dev_generator = false;
+    if (device >= 0 && G_defined && G && G->is_initialized()) {
+        const int rc = lutldpc_decoder_set_generator(dev, G->get_K(), G->get_R(), G->get_A().data());
+        if (rc == LUTLDPC_OK) dev_generator = true;
+        else if (rc != LUTLDPC_ERR_UNSUPPORTED) hip_fail("LDPC_Code_LUT: uploading the generator failed");
+    }
     return dev;
 }
 

@@ -36,6 +36,10 @@ public:
     bool is_initialized() const { return init_; }
     void encode(const bvec &input, bvec &output) const;
     int get_ninfo() const { return K_; }
+    // read access for the device encoder (lutldpc_decoder_set_generator)
+    int get_K() const { return K_; }
+    int get_R() const { return R_; }
+    const std::vector<uint64_t> &get_A() const { return A_; }
     void save(const std::string &filename) const;      // appended to an existing .it file
     void load(const std::string &filename);
 private:
@@ -88,8 +92,11 @@ public:
     // to `os`, frame after frame, as the reference streams them to std::cout; lut_decode_batch calls it with std::cout when
     // set_output_verbosity(>= 2) is in force
     void lut_decode_batch_dump(const uint8_t *cha, const uint8_t *msg0, int B, uint8_t *bits, int32_t *iters, int level, std::ostream &os);
-    lutldpc_decoder *device_handle();        // creates the HIP decoder on first use
+    lutldpc_decoder *device_handle();        // creates the HIP decoder on first use (and uploads the generator, if any)
     void set_device(int device);             // default 0; -1 = host-only (set-up without a GPU)
+    // the device handle holds the generator: random codewords can be made on the device (false for generators of more
+    // than 8192 information bits, which stay on the host encoder)
+    bool has_device_generator() { device_handle(); return dev_generator; }
 
     double get_rate() const { return 1.0 - static_cast<double>(nchk_lin_indep) / nvar; }
     int get_nvar() const { return nvar; }
@@ -153,6 +160,7 @@ private:
     int output_verbosity = 0;
     initial_message_mode_t initial_message_mode = CONT;
     lutldpc_decoder *dev = nullptr;
+    bool dev_generator = false;
     int device = 0;
 };
 
