@@ -929,8 +929,12 @@ int launch_tree_pass(lutldpc_decoder *d, PassPlan &plan, std::vector<FastClassPl
     P.G = G; P.nz = nz; P.check = check; P.write_hard = write_hard; P.vfail_stride_w = d->Bcap / 4;
     std::vector<char> keep((size_t)P.n_seg, 1);
     bool any = false;
+    // The compile-time and generated variable kernels read the sign of an outgoing label as bit sbit = log2(nz) (exit test and
+    // decided bits); that holds only where nz is a power of two.  A variable pass that writes any other alphabet (Nq_Msg = 12:
+    // nz = 6) runs in the interpreter below, which compares the label with nz.
+    const bool sign_bit = KIND != TT_VAR || is_pow2(nz);
     // specialised kernels take the classes they know, one launch per degree class
-    if (d->use_fast && fast && KIND != TT_CHK)
+    if (d->use_fast && fast && KIND != TT_CHK && sign_bit)
         for (int i = 0; i < P.n_seg; i++) {
             if (!(*fast)[(size_t)i].ok) continue;
             bool ok = false;
@@ -942,7 +946,7 @@ int launch_tree_pass(lutldpc_decoder *d, PassPlan &plan, std::vector<FastClassPl
             if (ok) keep[(size_t)i] = 0;
         }
     // run-time generated kernels (jit.hpp) for the classes without a compile-time one
-    if (jit)
+    if (jit && sign_bit)
         for (int i = 0; i < P.n_seg && (size_t)i < jit->size(); i++) {
             const JitKernel *k = (*jit)[(size_t)i];
             if (!keep[(size_t)i] || !k) continue;
@@ -1836,9 +1840,14 @@ void make_describe(lutldpc_decoder *d) {
     }
     o << "],\"cn_classes\":[";
     for (size_t i = 0; i < d->cclass.size(); i++) {
-        const bool f = d->use_fast && d->min_lut && d->cclass[i].deg >= 2 && d->cclass[i].deg <= kFastMaxCnDeg && is_pow2(d->Nq_Msg[0] / 2);
+        // fill_cn_fast decides per iteration: a schedule that mixes power-of-two and other message alphabets runs both kernels
+        int n_fast = 0;
+        for (int nq : d->Nq_Msg)
+            n_fast += d->use_fast && d->min_lut && d->cclass[i].deg >= 2 && d->cclass[i].deg <= kFastMaxCnDeg && is_pow2(nq / 2) && nq / 2 <= 64;
+        const char *minsum = n_fast == (int)d->Nq_Msg.size() ? "cn_minsum_fast_kernel"
+                           : n_fast == 0 ? "cn_minsum_generic_kernel" : "cn_minsum_fast_kernel+cn_minsum_generic_kernel";
         o << (i ? "," : "") << "{\"deg\":" << d->cclass[i].deg << ",\"nodes\":" << d->cclass[i].nodes.size() << ",\"kernel\":\""
-          << (d->min_lut ? (f ? "cn_minsum_fast_kernel" : "cn_minsum_generic_kernel")
+          << (d->min_lut ? minsum
                          : (!d->chk_jit.empty() && i < d->chk_jit[0].size() && d->chk_jit[0][i]) ? "lutldpc_jit_pass" : "tree_pass_kernel<CHK>") << "\"}";
     }
     o << "],\"resident\":" << (resident_active(d) ? 1 : 0) << ",\"skewed_pipeline\":" << ((d->skew && d->skew_ok) ? 1 : 0) << ",\"fused_bucket\":" << d->fused_bucket_id << ",\"compaction\":" << (d->use_compact < 0 ? 2 : d->use_compact) << ",\"compaction_min_groups\":" << [&] { for (int G = 1; G <= 2 * kPermuteMaxGroups; G++) if (compaction_on(d, G)) return G; return -1; }() << ",\"chain_nodes\":" << (d->use_chain ? d->n_chain_nodes : 0) << ",\"placement\":" << d->place_info;

@@ -219,6 +219,10 @@ LDPC_BER_Sim_LUT::LDPC_BER_Sim_LUT(const std::string &params, const std::string 
     else reuse_lut.assign((size_t)max_iter, 0);
     allow_degree_one = ini.get("LUT.allow_degree_one", false);
     known_rank = ini.get("LDPC.known_rank", 0);
+    // the sampler's cell table holds at most 72 cells (kernels_frontend.hpp: kMaxCells); a channel alphabet of more labels, or an
+    // initial message alphabet of more labels in continuous-input mode, never fits: refuse here, before the design and any result
+    if (codec_filename.empty() && (Nq_Cha > 72 || (initial_message_mode == "from_continuous_input" && !Nq_Msg.empty() && Nq_Msg[0] > 72)))
+        throw std::runtime_error("LDPC_BER_Sim_LUT::LDPC_BER_Sim_LUT(): more than 72 cells: the sampler takes alphabets of at most 72 labels");
     trees_path = join(base, trees_dir);
     fs::create_directories(trees_path);
 }

@@ -34,17 +34,23 @@ static px_out philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, 
     return o;
 }
 
+/* At most n_cha + n_msg + 1 boundaries before duplicates are removed: with alphabets of up to 128 labels (127 boundaries
+ * each) that is 255 boundaries and 256 cells.  make_cells refuses anything larger instead of writing past the arrays. */
+#define OR_MAX_CELLS 256
+
 typedef struct {
     int n_cells;
-    uint64_t thr[80];
-    uint8_t cha[80], msg[80], neg[80], cha_m[80], msg_m[80];
+    uint64_t thr[OR_MAX_CELLS];
+    uint8_t cha[OR_MAX_CELLS], msg[OR_MAX_CELLS], neg[OR_MAX_CELLS], cha_m[OR_MAX_CELLS], msg_m[OR_MAX_CELLS];
 } or_cells;
 
 static int cmp_dbl(const void *a, const void *b) { double x = *(const double *)a, y = *(const double *)b; return (x > y) - (x < y); }
 
-static void make_cells(or_cells *C, double N0, const double *qb_cha, int n_cha, const double *qb_msg, int n_msg, int mode, const int *map)
+/* returns 0, or -1 (nothing written) when the boundaries do not fit the table */
+static int make_cells(or_cells *C, double N0, const double *qb_cha, int n_cha, const double *qb_msg, int n_msg, int mode, const int *map)
 {
-    double t[80]; int nt = 0;
+    if (n_cha < 0 || n_msg < 0 || n_cha + (mode == 0 ? n_msg : 0) + 1 > OR_MAX_CELLS - 1) return -1;
+    double t[OR_MAX_CELLS]; int nt = 0;
     for (int i = 0; i < n_cha; i++) t[nt++] = qb_cha[i] * N0 / 4;
     if (mode == 0) for (int i = 0; i < n_msg; i++) t[nt++] = qb_msg[i] * N0 / 4;
     t[nt++] = 0.0;
@@ -72,6 +78,7 @@ static void make_cells(or_cells *C, double N0, const double *qb_cha, int n_cha, 
         if (j > 0 && thr < C->thr[j - 1]) thr = C->thr[j - 1];
         C->thr[j] = thr;
     }
+    return 0;
 }
 
 static void sample_frame(const or_cells *C, uint64_t seed, uint32_t stream, uint64_t frame, int N, const uint8_t *cw,
@@ -104,13 +111,13 @@ void or_sim_info_bits(uint64_t seed, uint32_t stream, uint64_t frame, int K, uin
     }
 }
 
-/* labels of frames frame0..frame0+B-1 (frame-major), for comparing the device sampler */
-void or_sim_sample_labels(const or_codec *c, double snr_db, double rate, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
-                          const uint8_t *codewords, uint8_t *cha_out, uint8_t *msg_out, int *uncoded)
+/* labels of frames frame0..frame0+B-1 (frame-major), for comparing the device sampler; -1: the cell table does not fit */
+int or_sim_sample_labels(const or_codec *c, double snr_db, double rate, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
+                         const uint8_t *codewords, uint8_t *cha_out, uint8_t *msg_out, int *uncoded)
 {
     double N0 = pow(10.0, -snr_db / 10.0) / rate;
     or_cells C;
-    make_cells(&C, N0, c->qb_Cha.v, c->qb_Cha.n, c->qb_Msg.v, c->qb_Msg.n, c->initial_message_mode, c->Nq_Cha_2_Nq_Msg_map.v);
+    if (make_cells(&C, N0, c->qb_Cha.v, c->qb_Cha.n, c->qb_Msg.v, c->qb_Msg.n, c->initial_message_mode, c->Nq_Cha_2_Nq_Msg_map.v) != 0) return -1;
     int *cha = (int *)malloc(sizeof(int) * (size_t)c->nvar), *msg = (int *)malloc(sizeof(int) * (size_t)c->nvar);
     for (int f = 0; f < B; f++) {
         int unc;
@@ -119,18 +126,19 @@ void or_sim_sample_labels(const or_codec *c, double snr_db, double rate, uint64_
         if (uncoded) uncoded[f] = unc;
     }
     free(cha); free(msg);
+    return 0;
 }
 
 /* sim_snr_point, src/LDPC_BER_Sim.cpp:246-311.  codewords: [Nframes][nvar] sent bits or NULL (zero
  * codeword).  counters = {frames, data bits, frame errors, data bit errors, uncoded bit errors}.
  * per_frame (optional, [Nframes][4]) receives {iters, frame error, bit errors, uncoded errors}.
- * Returns the sweep's exit flag (BER < ber_min || FER < fer_min). */
+ * Returns the sweep's exit flag (BER < ber_min || FER < fer_min), or -1 when the cell table does not fit. */
 int or_sim_snr_point(or_codec *c, double snr_db, double rate, int K, uint64_t seed, uint32_t stream, int64_t Nframes, int Nfers,
                      double ber_min, double fer_min, const uint8_t *codewords, int64_t *counters, int32_t *per_frame)
 {
     double N0 = pow(10.0, -snr_db / 10.0) / rate;
     or_cells C;
-    make_cells(&C, N0, c->qb_Cha.v, c->qb_Cha.n, c->qb_Msg.v, c->qb_Msg.n, c->initial_message_mode, c->Nq_Cha_2_Nq_Msg_map.v);
+    if (make_cells(&C, N0, c->qb_Cha.v, c->qb_Cha.n, c->qb_Msg.v, c->qb_Msg.n, c->initial_message_mode, c->Nq_Cha_2_Nq_Msg_map.v) != 0) return -1;
     int N = c->nvar;
     int *cha = (int *)malloc(sizeof(int) * (size_t)N), *msg = (int *)malloc(sizeof(int) * (size_t)N);
     uint8_t *out = (uint8_t *)malloc((size_t)N);
@@ -179,11 +187,12 @@ or_code *or_code_from_graph(int nvar, int nchk, const int *dv, const int *dc, co
     return c;
 }
 
-/* the cell table for tests: returns n_cells */
+/* the cell table for tests (arrays of OR_MAX_CELLS entries): returns n_cells, or -1 when the table does not fit */
 int or_sim_channel_cells(const or_codec *c, double snr_db, double rate, uint64_t *thr, uint8_t *cha, uint8_t *msg, uint8_t *neg, uint8_t *cha_m, uint8_t *msg_m)
 {
     or_cells C;
-    make_cells(&C, pow(10.0, -snr_db / 10.0) / rate, c->qb_Cha.v, c->qb_Cha.n, c->qb_Msg.v, c->qb_Msg.n, c->initial_message_mode, c->Nq_Cha_2_Nq_Msg_map.v);
+    if (make_cells(&C, pow(10.0, -snr_db / 10.0) / rate, c->qb_Cha.v, c->qb_Cha.n, c->qb_Msg.v, c->qb_Msg.n, c->initial_message_mode,
+                   c->Nq_Cha_2_Nq_Msg_map.v) != 0) return -1;
     for (int j = 0; j < C.n_cells; j++) {
         if (j < C.n_cells - 1) thr[j] = C.thr[j];
         cha[j] = C.cha[j]; msg[j] = C.msg[j]; neg[j] = C.neg[j]; cha_m[j] = C.cha_m[j]; msg_m[j] = C.msg_m[j];

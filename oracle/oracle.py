@@ -77,7 +77,7 @@ def lib() -> C.CDLL:
             "or_api_codec_tree_info": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, ip, ip]),
             "or_api_codec_n_sets": (C.c_int, [vp, C.c_int]),
             "or_sim_channel_cells": (C.c_int, [vp, C.c_double, C.c_double, C.POINTER(C.c_uint64), u8p, u8p, u8p, u8p, u8p]),
-            "or_sim_sample_labels": (None, [vp, C.c_double, C.c_double, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, u8p, u8p, u8p, ip]),
+            "or_sim_sample_labels": (C.c_int, [vp, C.c_double, C.c_double, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, u8p, u8p, u8p, ip]),
             "or_sim_snr_point": (C.c_int, [vp, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_uint32, C.c_int64, C.c_int, C.c_double,
                                            C.c_double, u8p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
             "or_sim_info_bits": (None, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, u8p]),
@@ -295,9 +295,11 @@ class Codec:
 
     # ---- Monte-Carlo front end (oracle/or_sim.c) ---------------------------------------------------
     def channel_cells(self, snr_db: float, rate: float):
-        thr = np.zeros(80, np.uint64)
-        arrs = [np.zeros(80, np.uint8) for _ in range(5)]
+        thr = np.zeros(256, np.uint64)                          # OR_MAX_CELLS (or_sim.c)
+        arrs = [np.zeros(256, np.uint8) for _ in range(5)]
         n = lib().or_sim_channel_cells(self._h, snr_db, rate, thr.ctypes.data_as(C.POINTER(C.c_uint64)), *[_u8p(a) for a in arrs])
+        if n < 0:
+            raise ValueError("the cell table of these alphabets does not fit the oracle's")
         return {"thr": thr[:n - 1], "cha": arrs[0][:n], "msg": arrs[1][:n], "neg": arrs[2][:n], "cha_m": arrs[3][:n], "msg_m": arrs[4][:n]}
 
     def sample_labels(self, snr_db, rate, seed, stream, frame0, B, codewords=None):
@@ -305,7 +307,8 @@ class Codec:
         cha, msg = np.zeros((B, N), np.uint8), np.zeros((B, N), np.uint8)
         unc = np.zeros(B, np.int32)
         cw = None if codewords is None else np.ascontiguousarray(codewords, np.uint8)
-        lib().or_sim_sample_labels(self._h, snr_db, rate, seed, stream, frame0, B, _u8p(cw) if cw is not None else None, _u8p(cha), _u8p(msg), _ip(unc))
+        if lib().or_sim_sample_labels(self._h, snr_db, rate, seed, stream, frame0, B, _u8p(cw) if cw is not None else None, _u8p(cha), _u8p(msg), _ip(unc)) != 0:
+            raise ValueError("the cell table of these alphabets does not fit the oracle's")
         return cha, msg, unc
 
     def sim_snr_point(self, snr_db, rate, K, seed, stream, nframes, nfers=20, ber_min=1e-7, fer_min=1e-5, codewords=None):
@@ -315,6 +318,8 @@ class Codec:
         stop = lib().or_sim_snr_point(self._h, snr_db, rate, K, seed, stream, nframes, nfers, ber_min, fer_min,
                                       _u8p(cw) if cw is not None else None, counters.ctypes.data_as(C.POINTER(C.c_int64)),
                                       per.ctypes.data_as(C.POINTER(C.c_int32)))
+        if stop < 0:
+            raise ValueError("the cell table of these alphabets does not fit the oracle's")
         return counters, per[:counters[0]], bool(stop)
 
     def syndrome_ok(self, bits: np.ndarray) -> bool:

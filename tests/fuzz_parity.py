@@ -26,7 +26,7 @@ for c in range(cases):
     if dvc == [2]:
         dvc = [2, 3]
     p = rng.dirichlet(np.ones(len(dvc)) * 2)
-    nqc, nqm = int(rng.choice([8, 16])), int(rng.choice([8, 16]))
+    nqc, nqm = int(rng.choice([2, 4, 8, 16, 32])), int(rng.choice([2, 4, 8, 16, 32]))
     I = int(rng.integers(3, 12))
     B = int(rng.choice([1, 63, 257, 513, 700, 1100, 1537]))
     if COMPACT:
@@ -71,14 +71,15 @@ for c in range(cases):
         print(f"case {c}: BP N={N} M={M} dv={sorted(set(dv.tolist()))} dc={sorted(set(dc.tolist()))} d={dpar} B={Bb} iters<={I + 8} {'ok' if okc else 'MISMATCH'}, return codes with the syndrome test {codes[:8]}", flush=True)
         continue
     cd = orc.Codec(code, skip_rank=True); cd.set_rank(M); cd.rate = 1.0 - M / N
-    # one case in four each: check-node LUT trees instead of min-sum, a message alphabet that shrinks along the iterations,
-    # LUT stages reused over several iterations (src/LDPC_Code_LUT.cpp:120-169)
+    # one case in four each: check-node LUT trees instead of min-sum, a message alphabet that shrinks along the iterations (halved
+    # from a random iteration on, two labels in the last one), LUT stages reused over several iterations (src/LDPC_Code_LUT.cpp:120-169)
     extra = {}
     nq_vec = np.full(I, nqm, np.int32)
     if draws[0][0] == 0 and dc.max() <= 12:
         extra["min_lut"] = False
-    if draws[0][1] == 0 and nqm == 16 and I >= 4:
-        nq_vec[min(draws[1], I - 2):] = 8
+    if draws[0][1] == 0 and nqm >= 4 and I >= 4:
+        nq_vec[min(draws[1], I - 2):] = nqm // 2
+        nq_vec[-1] = 2
     if draws[0][2] == 0:
         reuse = draws[2].astype(np.int32); reuse[0] = 0; reuse[-1] = 0     # (first and last iteration are exempt: src/LDPC_Code_LUT.cpp:122)
         for i in range(1, I):                                  # a reused stage keeps the alphabets of the stage it repeats

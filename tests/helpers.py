@@ -39,6 +39,21 @@ CONFIGS = {
     "dvbs2_q4": ("rate0.50_irreg_dvbs2_N64800", dict(sigma2=0.88 ** 2, max_iters=50, nq_cha=16, nq_msg=16, allow_deg1=True)),
     "dvbs2_q4_i6": ("rate0.50_irreg_dvbs2_N64800", dict(sigma2=0.88 ** 2, max_iters=6, nq_cha=16, nq_msg=16, allow_deg1=True)),
     "twin64800_q4_i6": ("rate0.50_dv02-08_dc07-08_lut_q4_N64800", dict(sigma2=0.88 ** 2, max_iters=6, nq_cha=16, nq_msg=16)),
+    # label alphabets from 2 to 64 labels (tests/test_15_label_alphabets_gpu.py); the schedule 8 8 8 8 4 4 4 2 is the one
+    # data/params/ber.ini.regular.example documents (qbits_messages = 3 3 3 3 2 2 2 1)
+    "reg36_n1000_ex8421": ("rate0.50_dv03_dc06_N1000", dict(sigma2=0.6 ** 2, max_iters=8, nq_cha=16, nq_msg=[8, 8, 8, 8, 4, 4, 4, 2])),
+    "n500_ex8421": ("rate0.50_dv02-17_dc08-09_lut_q4_N500", dict(sigma2=0.6 ** 2, max_iters=8, nq_cha=16, nq_msg=[8, 8, 8, 8, 4, 4, 4, 2])),
+    "reg36_n1000_ex8421_chklut": ("rate0.50_dv03_dc06_N1000", dict(sigma2=0.6 ** 2, max_iters=8, nq_cha=16, nq_msg=[8, 8, 8, 8, 4, 4, 4, 2],
+                                                                    min_lut=False)),
+    "reg36_n1000_m2": ("rate0.50_dv03_dc06_N1000", dict(sigma2=0.5 ** 2, max_iters=8, nq_cha=16, nq_msg=2)),          # 1-bit messages
+    "reg36_n1000_c2m4": ("rate0.50_dv03_dc06_N1000", dict(sigma2=0.6 ** 2, max_iters=8, nq_cha=2, nq_msg=4)),         # hard-decision channel
+    "reg36_n1000_c4m4": ("rate0.50_dv03_dc06_N1000", dict(sigma2=0.7 ** 2, max_iters=8, nq_cha=4, nq_msg=4)),
+    "reg36_n1000_grow": ("rate0.50_dv03_dc06_N1000", dict(sigma2=0.75 ** 2, max_iters=6, nq_cha=8, nq_msg=[4, 8, 8, 16, 16, 16])),
+    "reg36_n1000_m12": ("rate0.50_dv03_dc06_N1000", dict(sigma2=0.8 ** 2, max_iters=8, nq_cha=16, nq_msg=12)),        # half not a power of two
+    "reg36_n1000_m6": ("rate0.50_dv03_dc06_N1000", dict(sigma2=0.8 ** 2, max_iters=8, nq_cha=16, nq_msg=6)),
+    "reg36_n1000_m16_12_8": ("rate0.50_dv03_dc06_N1000", dict(sigma2=0.8 ** 2, max_iters=6, nq_cha=16, nq_msg=[16, 16, 12, 12, 8, 8])),
+    "reg36_n1000_c32m8": ("rate0.50_dv03_dc06_N1000", dict(sigma2=0.8 ** 2, max_iters=8, nq_cha=32, nq_msg=8)),
+    "reg36_n1000_q6": ("rate0.50_dv03_dc06_N1000", dict(sigma2=0.8 ** 2, max_iters=4, nq_cha=64, nq_msg=64)),          # 6-bit labels
 }
 
 

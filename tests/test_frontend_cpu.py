@@ -9,7 +9,9 @@ from helpers import CODES, oracle_codec
 from test_host_design_parity import product_codec
 
 
-@pytest.mark.parametrize("name,mode", [("n500_q4_i8", 0), ("reg36_n1000_mixed", 0), ("c5_minlut", 1)])
+@pytest.mark.parametrize("name,mode", [("n500_q4_i8", 0), ("reg36_n1000_mixed", 0), ("c5_minlut", 1)] +
+                         [(n, m) for n in ("reg36_n1000_c2m4", "reg36_n1000_c4m4", "reg36_n1000_m2", "reg36_n1000_ex8421", "reg36_n1000_m12",
+                                           "reg36_n1000_c32m8", "reg36_n1000_q5", "reg36_n1000_q6") for m in (0, 1)])
 @pytest.mark.parametrize("snr", [0.0, 2.5, 6.0])
 def test_channel_cells_match_oracle(name, mode, snr):
     want_cd = oracle_codec(name)
@@ -23,6 +25,44 @@ def test_channel_cells_match_oracle(name, mode, snr):
     assert (np.diff(got["thr"].astype(np.float64)) >= 0).all()
     want_cd.set_initial_message_mode(0)
     got_cd.close()
+
+
+def test_oracle_cell_table_at_64_labels_in_continuous_input_mode():
+    """64 channel and 64 message labels, continuous input: 127 boundaries before duplicates are removed (the oracle's table used
+    to hold 80 and was overrun), 64 cells after -- within the product's limit of 72 -- and equal on both sides."""
+    want_cd = oracle_codec("reg36_n1000_q6")
+    want_cd.set_initial_message_mode(0)
+    got_cd = product_codec("reg36_n1000_q6")
+    got_cd.set_initial_message_mode(0)
+    assert len(want_cd.qb_cha) + len(want_cd.qb_msg) + 1 == 127
+    for snr in (1.0, 4.0):
+        want = want_cd.channel_cells(snr, want_cd.rate)
+        got = got_cd.channel_cells(snr)
+        assert len(want["cha"]) == len(got["cha"]) == 64
+        for k in want:
+            assert (want[k] == got[k]).all(), k
+    got_cd.close()
+
+
+def test_ber_sim_refuses_a_channel_alphabet_beyond_the_cell_table(tmp_path):
+    """qbits_channel = 7 (128 labels) needs 128 cells, more than the sampler's 72: the run stops with that message before the
+    design and before any result is written, in the C++ driver and in the Python one."""
+    import ctypes as C
+    from lut_ldpc_amd import ber_sim
+    from lut_ldpc_amd._capi import ERR_ARG, lib
+    from helpers import ROOT
+    for d in ("codes", "trees"):
+        (tmp_path / d).mkdir()
+    ini = (ROOT / "data" / "params" / "ber.ini.regular.example").read_text()
+    assert "qbits_channel = 4" in ini
+    params = tmp_path / "ber.ini"
+    params.write_text(ini.replace("qbits_channel = 4", "qbits_channel = 7"))
+    snr = (C.c_double * 32)(); cnt = (C.c_int64 * 160)()
+    n = lib.lutldpc_ber_sim_run(str(params).encode(), str(tmp_path).encode(), 0, b"", -1, 1, 1, snr, cnt, 32)
+    assert n == ERR_ARG and "more than 72 cells" in lib.lutldpc_last_error().decode()
+    with pytest.raises(L.LutLdpcError, match="more than 72 cells"):
+        ber_sim.run(params, tmp_path, seed=0, device=-1, quiet=True)
+    assert not list((tmp_path / "results").rglob("*.it"))
 
 
 def test_sampler_statistics():

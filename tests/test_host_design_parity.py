@@ -23,7 +23,11 @@ def product_codec(name, device=-1):
 
 
 @pytest.mark.parametrize("name", ["n500_q4_i8", "reg36_n1000_mixed", "reg36_n1000_q3_chklut", "reg36_n1000_rootonly",
-                                  "reg36_n1000_high", "c5_minlut", "c5_chklut", "dvbs2_q4_i6"])
+                                  "reg36_n1000_high", "c5_minlut", "c5_chklut", "dvbs2_q4_i6",
+                                  # label alphabets from 2 to 64 labels (tests/test_15_label_alphabets_gpu.py)
+                                  "reg36_n1000_ex8421", "n500_ex8421", "reg36_n1000_ex8421_chklut", "reg36_n1000_m2", "reg36_n1000_c2m4",
+                                  "reg36_n1000_c4m4", "reg36_n1000_grow", "reg36_n1000_m12", "reg36_n1000_m6", "reg36_n1000_m16_12_8",
+                                  "reg36_n1000_c32m8", "reg36_n1000_q6"])
 def test_design_matches_oracle(name):
     want = oracle_codec(name)
     got = product_codec(name)
