@@ -15,7 +15,7 @@ if os.environ.get("LUTLDPC_LIB"):          # A/B runs of two builds of the same 
     LIB_PATH = Path(os.environ["LUTLDPC_LIB"])
 
 OK, ERR_ARG, ERR_PARSE, ERR_UNSUPPORTED, ERR_HIP, ERR_STATE = 0, -1, -2, -3, -4, -5
-K_CN_PASS, K_VN_PASS, K_DECISION, K_SYNDROME, K_LAYOUT, K_FRONTEND, K_FUSED_PASS, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7
+K_CN_PASS, K_VN_PASS, K_DECISION, K_SYNDROME, K_LAYOUT, K_FRONTEND, K_FUSED_PASS, K_RESIDENT, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8
 KIND_NAMES = ["cn_pass", "vn_pass", "decision", "syndrome", "layout", "frontend", "fused_pass", "resident"]
 
 

@@ -1,0 +1,211 @@
+// decoder_frontend.hip -- the simulation front end on the device: channel sampler, random-codeword encoder, error counters, and
+// the C-ABI entries built on them.  Home of every kernel of kernels_frontend.hpp and kernels_encode.hpp.
+#include "decoder_state.hpp"
+#include "kernels_frontend.hpp"
+#include "kernels_encode.hpp"
+
+#pragma GCC visibility push(hidden)
+
+// (see preload_code_objects) this unit's code object
+hipError_t preload_frontend_kernels() {
+    hipFuncAttributes a;
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&encode_random_kernel));
+}
+
+static int fill_cells(const lutldpc_channel_cells *c, const lutldpc_decoder *d, ChannelCells &C) {
+    if (!c || !c->thr || !c->cha_label || !c->msg_label || !c->slicer_neg || !c->cha_label_mirror || !c->msg_label_mirror)
+        return fail(LUTLDPC_ERR_ARG, "channel cells: NULL member");
+    if (c->n_cells < 1 || c->n_cells > kMaxCells) return fail(LUTLDPC_ERR_ARG, "channel cells: n_cells outside [1,72]");
+    std::memset(&C, 0, sizeof(C));
+    C.n_cells = c->n_cells;
+    for (int j = 0; j < c->n_cells; j++) {
+        if (j < c->n_cells - 1) { C.thr[j] = c->thr[j]; if (j && c->thr[j] < c->thr[j - 1]) return fail(LUTLDPC_ERR_ARG, "channel cells: thresholds must ascend"); }
+        if (c->cha_label[j] >= d->Nq_Cha || c->cha_label_mirror[j] >= d->Nq_Cha || c->msg_label[j] >= d->Nq_Msg[0] || c->msg_label_mirror[j] >= d->Nq_Msg[0])
+            return fail(LUTLDPC_ERR_ARG, "channel cells: label outside its alphabet");
+        C.cha[j] = c->cha_label[j]; C.msg[j] = c->msg_label[j]; C.neg[j] = c->slicer_neg[j] ? 1 : 0;
+        C.cha_m[j] = c->cha_label_mirror[j]; C.msg_m[j] = c->msg_label_mirror[j];
+    }
+    return LUTLDPC_OK;
+}
+
+// sampler -> d_cha_t / d_msg0_t (tile layout); stats zeroed and slicer errors accumulated.  sent_rows (device, d_sent): the
+// codewords as sent-bit rows, made by encode_tiles; otherwise codewords_host (frame-major, uploaded) or none (all-zero)
+static int sample_tiles(lutldpc_decoder *d, const ChannelCells &C, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *codewords_host,
+                 const uint8_t *sent_rows = nullptr) {
+    int rc = ensure_batch(d, B);
+    if (rc) return rc;
+    const int Bpad = d->bpad(B), G = Bpad / d->tile(), N = d->nvar;
+    HIP_TRY(d->d_stats.alloc((size_t)Bpad * 4));
+    HIP_TRY(hipMemsetAsync(d->d_stats.p, 0, sizeof(int32_t) * (size_t)Bpad * 4, d->stream));
+    const uint8_t *cw = nullptr;
+    if (codewords_host) {
+        HIP_TRY(d->d_codewords.alloc((size_t)B * N));
+        HIP_TRY(hipMemcpyAsync(d->d_codewords.p, codewords_host, (size_t)B * N, hipMemcpyHostToDevice, d->stream));
+        cw = d->d_codewords.p;
+    }
+    Timed t(d, LUTLDPC_K_FRONTEND);
+    const int ppt = 8, npairs = (N + 1) / 2;
+    dim3 grid((unsigned)((npairs + 4 * ppt - 1) / (4 * ppt)), (unsigned)G);
+    DEV_PARAM(dC, d, C);
+    if (sent_rows)
+        PACK_DISPATCH(d, launch_k(sample_labels_kernel<PK, true>, grid, dim3(256), 0, d->stream, dC, (uint32_t)seed, (uint32_t)(seed >> 32), stream, frame0, B, N,
+                           sent_rows, d->d_cha_t.p, d->d_msg0_t.p, d->d_stats.p, ppt));
+    else
+        PACK_DISPATCH(d, launch_k(sample_labels_kernel<PK>, grid, dim3(256), 0, d->stream, dC, (uint32_t)seed, (uint32_t)(seed >> 32), stream, frame0, B, N, cw,
+                           d->d_cha_t.p, d->d_msg0_t.p, d->d_stats.p, ppt));
+    LAUNCH_CHECK();
+    return LUTLDPC_OK;
+}
+
+// random codewords of frames frame0 .. frame0+B-1 -> d_sent (sent-bit rows of bpad(B) frames; pad frames zero)
+static int encode_tiles(lutldpc_decoder *d, uint64_t seed, uint32_t stream, uint64_t frame0, int B) {
+    if (!d->gen_set) return fail(LUTLDPC_ERR_STATE, "no generator set: random codewords on the device need lutldpc_decoder_set_generator first");
+    const int Bpad = d->bpad(B), G = Bpad / d->tile(), N = d->nvar;
+    const int RB = d->pack == 2 ? sent_row_bytes<2>() : sent_row_bytes<1>();
+    HIP_TRY(d->d_sent.alloc((size_t)G * N * RB));
+    Timed t(d, LUTLDPC_K_FRONTEND);
+    const int K = d->gen_K, R = d->gen_R;
+    const int W128 = (K + 127) / 128, T = (R + kEncTileRows - 1) / kEncTileRows, W32 = (K + 31) / 32;
+    // one wave per parity tile (at least one information word per wave where the tiles are fewer); a workgroup is 64 frames
+    const unsigned gx = (unsigned)(Bpad / kEncFrames), gy = (unsigned)std::max(1, (std::max(T, (W32 + 7) / 8) + 3) / 4);
+    launch_k(encode_random_kernel, dim3(gx, gy), dim3(256), (size_t)W128 * kEncFrames * 16, d->stream, d->d_gen.p, K, R, d->gen_W32p,
+             (uint32_t)seed, (uint32_t)(seed >> 32), stream, frame0, B, N, d->tile(), d->d_sent.p);
+    LAUNCH_CHECK();
+    return LUTLDPC_OK;
+}
+
+// d_sent -> frame-major bytes at dst (device, B*N)
+static int launch_sent_to_bytes(lutldpc_decoder *d, uint8_t *dst, int B) {
+    const size_t n = (size_t)B * d->nvar;
+    PACK_DISPATCH(d, launch_k(sent_rows_to_bytes_kernel<PK>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d->stream, d->d_sent.p, B, d->nvar, dst));
+    LAUNCH_CHECK();
+    return LUTLDPC_OK;
+}
+
+// lutldpc_decoder_sim_batch (codewords: host, frame-major, or null) and lutldpc_decoder_sim_batch_random (device_codewords:
+// made by the encoder on the device from (seed, stream, frame))
+static int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
+                   const uint8_t *codewords, bool device_codewords, int K_info, int32_t *frame_stats, uint8_t *cha_out, uint8_t *bits_out) {
+    if (!d || !frame_stats) return fail(LUTLDPC_ERR_ARG, "NULL argument");
+    if (d->device < 0) return fail(LUTLDPC_ERR_STATE, "decoder was created without a device (host-only handle)");
+    if (B <= 0 || K_info < 0 || K_info > d->nvar) return fail(LUTLDPC_ERR_ARG, "bad B / K_info");
+    if (device_codewords && !d->gen_set) return fail(LUTLDPC_ERR_STATE, "sim_batch_random: no generator set (lutldpc_decoder_set_generator)");
+    ChannelCells C;
+    int rc = fill_cells(cells, d, C);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(d->device));
+    if (device_codewords) {
+        if ((rc = ensure_batch(d, B))) return rc;
+        if ((rc = encode_tiles(d, seed, stream, frame0, B))) return rc;
+    }
+    if ((rc = sample_tiles(d, C, seed, stream, frame0, B, codewords, device_codewords ? d->d_sent.p : nullptr))) return rc;
+    if ((rc = decode_tiles(d, B))) return rc;
+    {
+        Timed t(d, LUTLDPC_K_FRONTEND);
+        const int Bpad = d->bpad(B), G = Bpad / d->tile(), rpw = 64;
+        const int rows = K_info > 0 ? K_info : 1;
+        const dim3 grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)), (unsigned)G);
+        if (device_codewords)
+            PACK_DISPATCH(d, launch_k(count_errors_kernel<PK, true>, grid, dim3(256), 0, d->stream, d->d_hard.p, d->d_sent.p, B, d->nvar, K_info, d->d_iters.p,
+                               d->d_stats.p, rpw));
+        else
+            PACK_DISPATCH(d, launch_k(count_errors_kernel<PK>, grid, dim3(256), 0, d->stream, d->d_hard.p,
+                               codewords ? d->d_codewords.p : nullptr, B, d->nvar, K_info, d->d_iters.p, d->d_stats.p, rpw));
+        LAUNCH_CHECK();
+    }
+    HIP_TRY(hipMemcpyAsync(frame_stats, d->d_stats.p, sizeof(int32_t) * (size_t)B * 4, hipMemcpyDeviceToHost, d->stream));
+    if (cha_out || bits_out) {
+        const int Bpad = d->bpad(B), G = Bpad / d->tile(), N = d->nvar;
+        const size_t n = (size_t)B * N;
+        HIP_TRY(d->d_out_bits.alloc(n));
+        if (cha_out) {
+            if ((rc = launch_transpose_out(d, d->d_cha_t.p, d->d_out_bits.p, B, G))) return rc;
+            LAUNCH_CHECK();
+            HIP_TRY(hipMemcpyAsync(cha_out, d->d_out_bits.p, n, hipMemcpyDeviceToHost, d->stream));
+        }
+        if (bits_out) {
+            if ((rc = launch_transpose_out(d, d->d_hard.p, d->d_out_bits.p, B, G))) return rc;
+            LAUNCH_CHECK();
+            HIP_TRY(hipMemcpyAsync(bits_out, d->d_out_bits.p, n, hipMemcpyDeviceToHost, d->stream));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    return LUTLDPC_OK;
+}
+
+#pragma GCC visibility pop
+
+extern "C" {
+
+int lutldpc_decoder_sim_batch(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
+                              const uint8_t *codewords, int K_info, int32_t *frame_stats, uint8_t *cha_out, uint8_t *bits_out) {
+    return sim_batch_impl(d, cells, seed, stream, frame0, B, codewords, false, K_info, frame_stats, cha_out, bits_out);
+}
+
+int lutldpc_decoder_sim_batch_random(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
+                                     int K_info, int32_t *frame_stats, uint8_t *cha_out, uint8_t *bits_out) {
+    return sim_batch_impl(d, cells, seed, stream, frame0, B, nullptr, true, K_info, frame_stats, cha_out, bits_out);
+}
+
+int lutldpc_decoder_set_generator(lutldpc_decoder *d, int K, int R, const uint64_t *rows) {
+    if (!d) return fail(LUTLDPC_ERR_ARG, "NULL decoder");
+    if (!rows) return fail(LUTLDPC_ERR_ARG, "generator rows are NULL");
+    if (K < 1 || R < 0 || K + R != d->nvar) return fail(LUTLDPC_ERR_ARG, "generator: K + R must equal nvar (K >= 1)");
+    if (d->device < 0) return fail(LUTLDPC_ERR_STATE, "decoder was created without a device (host-only handle)");
+    if (K > kEncMaxInfoBits) return fail(LUTLDPC_ERR_UNSUPPORTED, "generator: more than 8192 information bits (device encoder limit)");
+    HIP_TRY(hipSetDevice(d->device));
+    const int WK = (K + 63) / 64, W32p = 4 * ((K + 127) / 128), Rp = (R + kEncTileRows - 1) / kEncTileRows * kEncTileRows;
+    std::vector<uint32_t> a((size_t)std::max(Rp, 1) * W32p, 0u);
+    for (int i = 0; i < R; i++)
+        for (int j = 0; j < 2 * WK; j++) {
+            const int k0 = 32 * j;
+            uint32_t w = (uint32_t)(rows[(size_t)i * WK + (size_t)(j >> 1)] >> (32 * (j & 1)));
+            if (k0 + 32 > K) w &= k0 >= K ? 0u : (1u << (K - k0)) - 1u;        // bits beyond K stay zero (the info words carry random bits there)
+            a[(size_t)i * W32p + (size_t)j] = w;
+        }
+    HIP_TRY(hipStreamSynchronize(d->stream));           // (a batch in flight may still read the previous generator)
+    HIP_TRY(d->d_gen.upload(a));
+    d->gen_K = K; d->gen_R = R; d->gen_W32p = W32p; d->gen_set = true;
+    make_describe(d);
+    return LUTLDPC_OK;
+}
+
+int lutldpc_decoder_encode_random(lutldpc_decoder *d, uint64_t seed, uint32_t stream, uint64_t frame0, int B, uint8_t *codewords) {
+    if (!d) return fail(LUTLDPC_ERR_ARG, "NULL decoder");
+    if (B <= 0) return fail(LUTLDPC_ERR_ARG, "B must be positive");
+    if (d->device < 0) return fail(LUTLDPC_ERR_STATE, "decoder was created without a device (host-only handle)");
+    HIP_TRY(hipSetDevice(d->device));
+    int rc = encode_tiles(d, seed, stream, frame0, B);
+    if (rc) return rc;
+    if (codewords) {
+        const size_t n = (size_t)B * d->nvar;
+        HIP_TRY(d->d_out_bits.alloc(n));
+        if ((rc = launch_sent_to_bytes(d, d->d_out_bits.p, B))) return rc;
+        HIP_TRY(hipMemcpyAsync(codewords, d->d_out_bits.p, n, hipMemcpyDeviceToHost, d->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    return LUTLDPC_OK;
+}
+
+int lutldpc_decoder_sample_labels(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
+                                  const uint8_t *codewords, uint8_t *cha, uint8_t *msg0) {
+    if (!d || !cha || !msg0) return fail(LUTLDPC_ERR_ARG, "NULL argument");
+    if (d->device < 0) return fail(LUTLDPC_ERR_STATE, "decoder was created without a device (host-only handle)");
+    if (B <= 0) return fail(LUTLDPC_ERR_ARG, "B must be positive");
+    ChannelCells C;
+    int rc = fill_cells(cells, d, C);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(d->device));
+    if ((rc = sample_tiles(d, C, seed, stream, frame0, B, codewords))) return rc;
+    const int Bpad = d->bpad(B), G = Bpad / d->tile(), N = d->nvar;
+    const size_t n = (size_t)B * N;
+    HIP_TRY(d->d_in_cha.alloc(n)); HIP_TRY(d->d_in_msg.alloc(n));
+    if ((rc = launch_transpose_out(d, d->d_cha_t.p, d->d_in_cha.p, B, G))) return rc;
+    if ((rc = launch_transpose_out(d, d->d_msg0_t.p, d->d_in_msg.p, B, G))) return rc;
+    HIP_TRY(hipMemcpyAsync(cha, d->d_in_cha.p, n, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipMemcpyAsync(msg0, d->d_in_msg.p, n, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    return LUTLDPC_OK;
+}
+
+}  // extern "C"

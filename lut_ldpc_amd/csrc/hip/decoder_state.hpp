@@ -1,0 +1,359 @@
+// decoder_state.hpp -- private state of the decode path: the handle behind include/lut_ldpc_hip.h, its device buffers, the
+// error / launch macros and the functions that cross the borders of the decoder_*.hip units.  Not installed; no kernel is
+// defined here (every kernel has ONE home unit, the others call that unit's host launcher).
+//
+//   decoder.hip            C-ABI: create (knob table) / destroy / exit conditions / decode entries / profiling / describe / selftest
+//   decoder_setup.hip      tree compiler, dense index tables, chain fusion, JIT registry, static uploads
+//   decoder_batch.hip      batch buffers, parameter arena, placement search
+//   decoder_stream.hip     streaming decode: per-class launches, decision pass, graph replay, message trace   (kernels_generic.hpp)
+//   decoder_skew.hip       skewed two-half pipeline through pass_fused_kernel, compaction                     (kernels_compact.hpp)
+//   decoder_resident.hip   LDS-resident decoder (jit_resident.hpp)
+//   decoder_frontend.hip   channel sampler, encoder, error counters and their C-ABI entries    (kernels_frontend.hpp, kernels_encode.hpp)
+#pragma once
+#include "../../../include/lut_ldpc_hip.h"
+#include "kernels_common.hpp"
+#include "kernels_fast.hpp"
+#include "lut_program.hpp"
+#include "jit.hpp"
+#include "jit_resident.hpp"
+
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <sstream>
+#include <string>
+#include <vector>
+
+namespace lutldpc { LUTLDPC_FAST_LAUNCHERS(extern) }     // instantiated in fast_*.hip / fused_b*.hip
+
+using namespace lutldpc;
+
+#pragma GCC visibility push(hidden)
+
+int fail(int code, const std::string &msg);     // sets the thread's last error (decoder.hip: g_err), returns code
+
+#define HIP_TRY(expr)                                                                               \
+    do {                                                                                            \
+        hipError_t e_ = (expr);                                                                     \
+        if (e_ != hipSuccess)                                                                       \
+            return fail(LUTLDPC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));        \
+    } while (0)
+
+// device allocation owned by its holder: freed by the destructor, move-only
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    size_t n = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    hipError_t alloc(size_t count) {
+        if (count <= n) return hipSuccess;
+        release();
+        hipError_t e = hipMalloc((void **)&p, count * sizeof(T));
+        if (e == hipSuccess) n = count; else p = nullptr;
+        return e;
+    }
+    hipError_t upload(const std::vector<T> &h) {
+        hipError_t e = alloc(h.size() ? h.size() : 1);
+        if (e != hipSuccess || h.empty()) return e;
+        return hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+    size_t bytes() const { return n * sizeof(T); }
+};
+
+// the decoder's stream; a member declared BEFORE every device buffer, so that it is destroyed after them
+struct StreamHolder {
+    hipStream_t s = nullptr;
+    StreamHolder() = default;
+    StreamHolder(const StreamHolder &) = delete;
+    StreamHolder &operator=(const StreamHolder &) = delete;
+    ~StreamHolder() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+
+struct NodeClass {
+    int deg = 0;
+    std::vector<int> nodes;     // node ids, ascending
+    int tree_class = -1;        // index of the matching tree inside a tree set
+};
+
+struct PassPlan {               // one launch: all degree classes of one pass of one tree set
+    PassParams P{};
+    int lds_bytes = 0;
+    int out_slots = 0;
+    bool lds_tab = true;
+    bool valid = false;
+};
+
+#pragma GCC visibility pop
+
+struct lutldpc_decoder {
+    // ---- what the user may turn: read once at creation from the environment (decoder.hip: kKnobs holds name, range and
+    // meaning of every one; DESIGN.md section 3 lists them)
+    struct Options {
+        int nodes_per_block = 16;
+        int use_fast = 1;
+        int pack = 0;                                          // 0 = automatic (lutldpc_decoder::pack), 1 = byte rows
+        int nodes_per_wave = 0, nodes_per_wave_cn = 0;         // 0 = derive from the degree (npw_vn / npw_cn)
+        int vn_edges_per_wave = 16, cn_edges_per_wave = 0;     // check side: 0 = automatic (cn_epw)
+        int first_from_nodes = 1;
+        int use_jit = 1;
+        int use_compose = 0, compose_space = 4096;
+        int chk_full_labels = 1;
+        int use_chain = 1;
+        int use_resident = 1, resident_force_S = 0, resident_force_NT = 0, resident_U = 0, resident_xcd = 1, resident_fm = 1;
+        int resident_flag_reduce = -1, resident_cn_persistent = -1, resident_waves_eu = 0;      // -1 = automatic (resident_spec)
+        int place_candidates = 16;
+        int use_compact = -1, compact_keep = 1, compact_first = 8, compact_every = 0;           // use: -1 = automatic, every: 0 = automatic
+        double compact_margin = 1.0, compact_min_share = 0.35;
+        int use_graph = 1;                                     // also cleared by decode_tiles when a capture fails
+        int fused_prio = 0;
+        double tail_front = 0.25;
+        int skew = 1;
+        int late_hard = 1;
+        int validate = 0;
+        int fused_bucket_min = -1;                             // applied after compile_all (lutldpc_decoder_create)
+        int debug_addr = 0;
+    } opt;
+    // ---- code
+    int nvar = 0, nchk = 0, E = 0;
+    std::vector<int> dv, dc, cn_msg_idx, vn_ptr, cn_ptr, cn_vn;
+    std::vector<NodeClass> vclass, cclass;
+    std::vector<int> vn_list, cn_list;         // nodes sorted by class
+    // ---- decoder parameters
+    int Nq_Cha = 0, max_iters_created = 0, max_iters = 0, psc = 1, pisc = 0, min_lut = 1;
+    std::vector<int> Nq_Msg, iter_set;         // iter_set = cumsum(reuse == 0) - 1
+    TreeArray var_trees, chk_trees;
+    // ---- programs: [set][class]
+    std::vector<std::vector<Program>> var_prog, chk_prog, dec_prog;
+    // check programs over full labels (lut_program.hpp: chk_full_label_program) for the generated check kernels, and where their
+    // tables sit in the blob: [set][class], {offset, bytes}, bytes = 0: none (the generated kernel then works on sign / magnitude)
+    std::vector<std::vector<Program>> chk_prog_full;
+    std::vector<std::vector<std::pair<int, int>>> chk_full_tab;
+    std::vector<std::vector<Program>> chk_prog_cf;                    // the same for the programs the LDS-resident decoder runs (chk_prog_c)
+    std::vector<std::vector<std::pair<int, int>>> chk_tab_cf;
+    // the same trees after exact table composition (lut_program.hpp: compose_tree): fewer, larger look-ups; used by the generated
+    // LDS-resident kernel.  *_tab_c: {offset, bytes} of the class blob inside all_tables.  opt.use_compose = 0: the originals.
+    std::vector<std::vector<Program>> var_prog_c, chk_prog_c, dec_prog_c;
+    std::vector<std::vector<std::pair<int, int>>> var_tab_c, chk_tab_c, dec_tab_c;
+    std::vector<Op> all_ops;
+    std::vector<uint8_t> all_tables;
+    std::vector<PassPlan> var_plan, chk_plan, dec_plan;   // per tree set
+    PassPlan cn_minsum_plan;
+    std::vector<std::vector<FastClassPlan>> var_fast, dec_fast;   // [set][class]
+    // dense per-class index tables of the specialised kernels: variable classes {node id, first edge}
+    // per node, check classes the DEG edge ids per node (no pointer chasing, scalar loads)
+    std::vector<int32_t> fast_idx;
+    std::vector<int> vn_idx_off, cn_idx_off;                      // per class
+    std::vector<int> cn_nidx_off;                                 // per check class: the NODE of every entry of the edge table (iteration 0 reads the initial-message rows)
+    std::vector<int> cn_tidx_off, cn_tnidx_off, vn_tidx_off;      // transposed tables of the LDS-resident decoder: [k][node] edges / nodes per check class, [2][node] {node id, first edge} per variable class
+    // chain fusion (build_fast_index): per check class the offset of its {back, forward} node table (-1 = no links),
+    // per variable class the dense table / count of the nodes NOT updated inside the check pass
+    std::vector<int> chain_idx_off, vn_red_off, vn_red_n;
+    int chain_vclass = -1, n_chain_nodes = 0;
+    std::vector<int> cn_npw_class;          // checks per wave of each check class (chain-rich classes of wide checks get at least 4)
+    std::vector<uint8_t> chain_internal;    // 1 = variable node updated inside the check pass (build_fast_index)
+    std::vector<int32_t> edge_vn;           // variable node of every edge (chain_hard_kernel)
+    int pack = 1;               // 2: nibble rows (all alphabets <= 16 labels and opt.pack = 0), 1: byte rows
+    bool skew_ok = false;       // every class of every set has a case in the fused kernel
+    int fused_bucket_id = 0;    // degree bucket of the fused kernel (kernels_fast.hpp: kFusedVnDeg / kFusedCnDeg)
+    bool resident_ok = false;   // the code can be decoded out of LDS (resident_eligible)
+    // ---- device.  The stream comes first: members are destroyed in reverse order, every buffer below goes before it.
+    int device = -1;
+    StreamHolder stream;
+    DevBuf<int32_t> d_vn_ptr, d_cn_ptr, d_cn_idx, d_cn_vn, d_vn_list, d_cn_list, d_fast_idx;
+    DevBuf<Op> d_ops;
+    DevBuf<uint8_t> d_tables;
+    DevBuf<uint8_t> d_chain_internal;
+    DevBuf<int32_t> d_edge_vn;
+    // batch buffers
+    int Bcap = 0;
+    DevBuf<uint8_t> d_msgs, d_cha_t, d_msg0_t, d_hard, d_state, d_vfail;
+    DevBuf<int32_t> d_iters;
+    DevBuf<uint8_t> d_in_cha, d_in_msg, d_out_bits;   // frame-major staging for the host entry points
+    DevBuf<int32_t> d_out_iters;
+    DevBuf<double> d_llr, d_qb_cha, d_qb_msg;
+    DevBuf<int32_t> d_map;
+    DevBuf<uint8_t> d_codewords;
+    DevBuf<int32_t> d_stats;
+    // systematic generator of the random codewords made on the device (kernels_encode.hpp): gen_R parity rows over gen_K
+    // information bits, stored as whole 32-row tiles of gen_W32p = 4*ceil(K/128) dwords; d_sent: the sent-bit rows of a batch
+    bool gen_set = false;
+    int gen_K = 0, gen_R = 0, gen_W32p = 0;
+    DevBuf<uint32_t> d_gen;
+    DevBuf<uint8_t> d_sent;
+    // compaction of the surviving frames (kernels_compact.hpp)
+    DevBuf<int32_t> d_frame_of, d_perm, d_tmp3, d_ctl, d_slot_of, d_iters_tmp;
+    DevBuf<int32_t> d_grp;                           // per frame group: every frame failed the probe of the test on the channel decisions
+    // Parameter structures of the per-class / generic / sampler kernels live in DEVICE memory (kernel arguments stay <= 128 bytes,
+    // kernels_common.hpp: launch_k): a small arena keyed by content.  The first decode of a shape runs as plain launches and
+    // uploads what it needs; the captured second run finds every structure there already.
+    struct ParamArena {
+        std::map<std::string, size_t> off_of;        // content -> byte offset (the key's bytes are the host copy the upload reads)
+        std::vector<DevBuf<uint8_t>> chunks;
+        std::vector<size_t> chunk_base;
+        size_t used = 0, cap = 0;
+        void clear() { chunks.clear(); chunk_base.clear(); off_of.clear(); used = cap = 0; }
+    } params;
+    // message dumps of output_verbosity >= 2 (src/LDPC_Code_LUT.cpp:292-298,311-317,331-337): a small-batch debug path -- per-class
+    // streaming launches, the edge rows copied out after the edge initialisation, (level > 2) every check pass and every
+    // variable pass.  host: [dump][B][E] bytes, dumps in the reference's print order.
+    struct Trace { int level = 0; uint8_t *host = nullptr; size_t cap = 0; int n = 0; int B = 0; };
+    Trace trace;
+    DevBuf<uint8_t> d_trace;
+    // LDS-resident decoder (jit_resident.hpp): codes whose edge messages fit the LDS of a compute unit are decoded by ONE generated
+    // kernel per decode -- all iterations inside, no HBM traffic between the labels and the decided bits.
+    // frame-major label / bit buffers of the current decode_device call, handed to the resident kernel (it reads and writes them
+    // itself: no transposes); null = rows
+    const uint8_t *fm_cha = nullptr, *fm_msg0 = nullptr;
+    uint8_t *fm_bits = nullptr;
+    struct ResidentPlan { int S = 0, NT = 0, lds = 0; const JitKernel *k = nullptr; };
+    std::map<int, ResidentPlan> resident_plans;       // by frame groups
+    std::string resident_log;
+    // tree-specialised kernels for shapes the compile-time path does not cover (jit.hpp); the loaded kernels live in a
+    // process-wide registry keyed by device + source text, see jit_registry(): decoders share them and they are never unloaded
+    std::vector<std::vector<const JitKernel *>> var_jit, dec_jit, chk_jit;     // [set][class], null = none
+    std::string jit_log;                                               // last hiprtc diagnostic (describe())
+    // repeated decodes replayed as one hipGraph launch (decode_tiles)
+    struct GraphSlot { int seen = 0; hipGraphExec_t exec = nullptr; };
+    std::map<std::array<int, 4>, GraphSlot> graphs;       // key {B, psc, pisc, max_iters}
+    void drop_graphs() { for (auto &kv : graphs) if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec); graphs.clear(); }
+    // specialised kernels: nodes handled by one wave = edges_per_wave / degree (equal work per wave for every degree class); a
+    // fixed count when opt.nodes_per_wave[_cn] is set
+    int cn_epw() const { return opt.cn_edges_per_wave > 0 ? opt.cn_edges_per_wave : 42; }
+    int npw_vn(int deg) const { return opt.nodes_per_wave > 0 ? opt.nodes_per_wave : std::max(1, opt.vn_edges_per_wave / std::max(deg, 1)); }
+    int npw_cn(int deg) const { return opt.nodes_per_wave_cn > 0 ? opt.nodes_per_wave_cn : std::max(1, cn_epw() / std::max(deg, 1)); }
+    int npw_cn_class(size_t ci) const { return ci < cn_npw_class.size() && cn_npw_class[ci] > 0 ? cn_npw_class[ci] : npw_cn(cclass[ci].deg); }
+    std::string place_info = "null";                  // what the placement search did (decoder_batch.hip: place_rows), JSON
+    // launch plan of the skewed pipeline for one (frame groups, psc, max_iters): the roles of every launch in DEVICE memory
+    // (the kernel reads them through a pointer), the interleaved item tables, what follows each launch.  Built once, at
+    // the first decode of that shape; dropped with the batch buffers (the roles hold strides of the flag buffers).
+    struct SkewSlot { int n_roles = 0; size_t role_off = 0; const int32_t *items = nullptr; int nb = 0; int state_half = -1, state_ii = 0; };
+    struct SkewPlan { std::vector<SkewSlot> slots; std::vector<RoleParams> h_roles; DevBuf<RoleParams> d_roles; };
+    std::map<std::array<int, 3>, std::unique_ptr<SkewPlan>> skew_plans;
+    // interleaved item tables, keyed by the role block counts AND the (quantised) share of the timeline each role keeps clear
+    std::map<std::pair<std::vector<int>, std::vector<int>>, DevBuf<int32_t>> item_tabs;
+    void drop_plans() { skew_plans.clear(); item_tabs.clear(); }
+    int tile() const { return kRowBytes * pack; }       // frames per group
+    int bpad(int B) const { return (B + tile() - 1) / tile() * tile(); }
+    // ---- profiling
+    bool profiling = false;
+    struct Ev { hipEvent_t a, b; int kind; };
+    std::vector<Ev> ev_live;
+    std::vector<hipEvent_t> ev_pool;
+    double prof_ms[LUTLDPC_K_COUNT] = {0};
+    int64_t prof_n[LUTLDPC_K_COUNT] = {0};
+    std::string describe;
+
+    lutldpc_decoder() = default;
+    lutldpc_decoder(const lutldpc_decoder &) = delete;
+    lutldpc_decoder &operator=(const lutldpc_decoder &) = delete;
+    // device = -1 (host-only handle): no HIP call.  Otherwise: the device made current, the stream drained, graphs and events
+    // destroyed; the members then release every buffer, the stream last.
+    ~lutldpc_decoder();
+};
+
+#pragma GCC visibility push(hidden)
+
+// LUTLDPC_VALIDATE=1: additionally wait for the launch(es) just issued, so that a device fault is reported by the launch site
+// that caused it (function and line), whatever the kernel -- not only the fused ones (no graph capture in that mode)
+#define LAUNCH_CHECK()                                                                              \
+    do {                                                                                            \
+        hipError_t e_ = hipGetLastError();                                                          \
+        if (e_ != hipSuccess) return fail(LUTLDPC_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e_)); \
+        if (d->opt.validate) {                                                                      \
+            e_ = hipStreamSynchronize(d->stream);                                                   \
+            if (e_ == hipSuccess) e_ = hipGetLastError();                                           \
+            if (e_ != hipSuccess) return fail(LUTLDPC_ERR_HIP, std::string("launch failed on the device (") + __func__ + ":" + std::to_string(__LINE__) + "): " + hipGetErrorString(e_)); \
+        }                                                                                           \
+    } while (0)
+
+// device copy of a parameter structure (see lutldpc_decoder::ParamArena); nullptr + last error on failure
+const void *dev_param_bytes(lutldpc_decoder *d, const void *src, size_t n);
+template <class T> const T *dev_param(lutldpc_decoder *d, const T &v) { return static_cast<const T *>(dev_param_bytes(d, &v, sizeof(T))); }
+#define DEV_PARAM(var, d, v)                      \
+    const auto *var = dev_param((d), (v));        \
+    if (!var) return LUTLDPC_ERR_HIP
+
+// instantiate a launch for the decoder's packing
+#define PACK_DISPATCH(d, ...)                        \
+    do {                                             \
+        if ((d)->pack == 2) { constexpr int PK = 2; __VA_ARGS__; } \
+        else { constexpr int PK = 1; __VA_ARGS__; }  \
+    } while (0)
+
+// ---- profiling (decoder.hip): kernel time by kind, from event pairs around the launches of a scope
+hipEvent_t ev_get(lutldpc_decoder *d);
+void prof_fold(lutldpc_decoder *d);
+struct Timed {
+    lutldpc_decoder *d; int kind; hipEvent_t a{}, b{};
+    Timed(lutldpc_decoder *d_, int k) : d(d_), kind(k) {
+        if (d->profiling) { a = ev_get(d); b = ev_get(d); (void)hipEventRecord(a, d->stream); }
+    }
+    ~Timed() {
+        if (d->profiling) { (void)hipEventRecord(b, d->stream); d->ev_live.push_back({a, b, kind}); }
+    }
+};
+void make_describe(lutldpc_decoder *d);
+
+// ---- decoder_setup.hip
+void build_classes(const std::vector<int> &deg, std::vector<NodeClass> &cls, std::vector<int> &list);
+int compile_all(lutldpc_decoder *d);
+int upload_static(lutldpc_decoder *d);
+// Process-wide registry of the run-time generated kernels, keyed by device + source text (decoder_setup.hip: jit_registry)
+struct JitRegistry { std::mutex mu; std::map<std::string, JitKernel> by_src; };
+constexpr size_t kJitRegistryMax = 4096;
+JitRegistry &jit_registry();
+
+// ---- decoder_batch.hip
+int ensure_batch(lutldpc_decoder *d, int B);
+int check_batch_buffers(const lutldpc_decoder *d, int Bpad);
+
+// ---- decoder_stream.hip (home of the kernels of kernels_generic.hpp)
+hipError_t preload_stream_kernels();
+// frames f0 .. f1-1 (both multiples of 256); default: the whole padded batch
+// `sel`: which of the two flag buffers the exit test reads and clears (always 0 outside the skewed pipeline)
+int launch_state(lutldpc_decoder *d, int B, int Bpad, int mode, int value, int f0 = 0, int f1 = -1, int sel = 0);
+int launch_transpose_out(lutldpc_decoder *d, const uint8_t *src_rows, uint8_t *dst, int B, int G, int rows = 0);
+int launch_quantize_llr(lutldpc_decoder *d, size_t n, int n_qb_Cha, int n_qb_Msg, int mode);
+bool chain_active(const lutldpc_decoder *d, int set);
+bool late_hard_active(const lutldpc_decoder *d, bool skewed, bool *chain_skip);
+int launch_late_hard(lutldpc_decoder *d, bool skewed, int g0, int G, const int32_t *ctl);
+int decode_tiles(lutldpc_decoder *d, int B);
+int decode_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d_msg0, int B, uint8_t *d_out_bits, int32_t *d_out_iters);
+
+// ---- decoder_skew.hip (home of the kernels of kernels_compact.hpp; pass_fused_kernel through launch_fused)
+// Half A = groups [0, GA), half B = [GA, G)
+struct HalfRange { int g0, G; };
+hipError_t preload_compact_kernels();
+bool skew_eligible(const lutldpc_decoder *d);
+bool compaction_on(const lutldpc_decoder *d, int G);
+int compaction_min_groups(const lutldpc_decoder *d);       // smallest batch, in frame groups, that compaction_on accepts (-1: none)
+int launch_uncompaction(lutldpc_decoder *d, const HalfRange (&half)[2], int Bpad);
+int iterate_skewed(lutldpc_decoder *d, int B, int Bpad, int G);
+
+// ---- decoder_resident.hip
+ResidentSpec resident_spec(const lutldpc_decoder *d, int S, int NT);
+bool resident_eligible(const lutldpc_decoder *d);
+bool resident_pick(const lutldpc_decoder *d, int G, int &S_out, int &NT_out, int &lds_out);
+inline bool resident_active(const lutldpc_decoder *d) { return d->resident_ok && d->opt.use_resident; }
+int resident_plan_for(lutldpc_decoder *d, int G, lutldpc_decoder::ResidentPlan **out);
+int launch_resident(lutldpc_decoder *d, int G, int B);
+
+// ---- decoder_frontend.hip (home of the kernels of kernels_frontend.hpp and kernels_encode.hpp)
+hipError_t preload_frontend_kernels();
+
+#pragma GCC visibility pop

@@ -1,0 +1,410 @@
+// decoder_stream.hip -- the streaming decode: one launch per pass and degree class, exit tests, decision pass, message trace,
+// graph replay.  Replaces LDPC_Code_LUT::lut_decode and everything below it (src/LDPC_Code_LUT.cpp:259-469,
+// src/LUT_Tree.cpp:402-445,774-820) for a BATCH of frames: the frame loop of LDPC_BER_Sim::sim_snr_point
+// (src/LDPC_BER_Sim.cpp:260-291) becomes the innermost, coalesced memory dimension.  See kernels_common.hpp for the HBM layout.
+// Home of every kernel of kernels_generic.hpp.
+#include "decoder_state.hpp"
+#include "kernels_generic.hpp"
+
+#pragma GCC visibility push(hidden)
+
+// (see preload_code_objects) this unit's code object
+hipError_t preload_stream_kernels() {
+    hipFuncAttributes a;
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&frame_state_kernel));
+}
+
+int launch_state(lutldpc_decoder *d, int B, int Bpad, int mode, int value, int f0, int f1, int sel) {
+    Timed t(d, LUTLDPC_K_LAYOUT);
+    if (f1 < 0) f1 = Bpad;
+    if (f1 <= f0) return LUTLDPC_OK;
+    if (mode == 0) HIP_TRY(hipMemsetAsync(d->d_vfail.p + (size_t)kVfailSlots * d->Bcap, 0, (size_t)kVfailSlots * d->Bcap, d->stream));
+    launch_k(frame_state_kernel, dim3((unsigned)((f1 - f0) / 256)), dim3(256), 0, d->stream,
+                       d->d_state.p, d->d_vfail.p + (size_t)sel * kVfailSlots * d->Bcap, d->d_iters.p, B, f0, f1, mode, value, d->Bcap);
+    LAUNCH_CHECK();
+    return LUTLDPC_OK;
+}
+
+static int launch_syndrome(lutldpc_decoder *d, int G, int sel = 0) {
+    Timed t(d, LUTLDPC_K_SYNDROME);
+    const int cpw = 8;
+    unsigned bx = (unsigned)((d->nchk + 4 * cpw - 1) / (4 * cpw));
+    PACK_DISPATCH(d, launch_k(syndrome_bits_kernel<PK>, dim3(bx, (unsigned)G), dim3(256), 0, d->stream, d->d_hard.p,
+                       reinterpret_cast<const uint32_t *>(d->d_state.p), reinterpret_cast<uint32_t *>(d->d_vfail.p + (size_t)sel * kVfailSlots * d->Bcap),
+                       d->d_cn_ptr.p, reinterpret_cast<const uint32_t *>(d->d_cn_vn.p), d->nchk, d->nvar, cpw, d->Bcap / 4, -1, (const int32_t *)nullptr, (int32_t *)nullptr));
+    LAUNCH_CHECK();
+    return LUTLDPC_OK;
+}
+// The test on the channel decisions (src/LDPC_Code_LUT.cpp:275-279) straight off the channel-label rows: a one-wave probe over
+// the first 64 checks of every group, then the full pass, which skips the groups whose frames have all failed in the probe.
+// The decided bits of the frames that pass are written at the end of the decode (hard_from_labels_masked_kernel).
+static int launch_syndrome_of_labels(lutldpc_decoder *d, int G) {
+    Timed t(d, LUTLDPC_K_SYNDROME);
+    const int cpw = 8, sbit = __builtin_ctz((unsigned)(d->Nq_Cha / 2));
+    HIP_TRY(hipMemsetAsync(d->d_grp.p, 0, sizeof(int32_t) * (size_t)G, d->stream));
+#define SYN_ARGS(CPW, SKIP, OUT) d->d_cha_t.p, reinterpret_cast<const uint32_t *>(d->d_state.p), reinterpret_cast<uint32_t *>(d->d_vfail.p), d->d_cn_ptr.p, \
+                     reinterpret_cast<const uint32_t *>(d->d_cn_vn.p), d->nchk, d->nvar, CPW, d->Bcap / 4, sbit, SKIP, OUT
+    PACK_DISPATCH(d, launch_k(syndrome_bits_kernel<PK>, dim3(1u, (unsigned)G), dim3(64), 0, d->stream, SYN_ARGS(64, (const int32_t *)nullptr, d->d_grp.p)));
+    unsigned bx = (unsigned)((d->nchk + 4 * cpw - 1) / (4 * cpw));
+    PACK_DISPATCH(d, launch_k(syndrome_bits_kernel<PK>, dim3(bx, (unsigned)G), dim3(256), 0, d->stream, SYN_ARGS(cpw, (const int32_t *)d->d_grp.p, (int32_t *)nullptr)));
+#undef SYN_ARGS
+    LAUNCH_CHECK();
+    return LUTLDPC_OK;
+}
+
+// frame-major [B][N] <-> rows; the dword-vectorised kernels need N % 4 == 0 and a 4-byte aligned buffer
+static int launch_transpose_in(lutldpc_decoder *d, const uint8_t *src, uint8_t *dst_rows, int B, int G, int limit) {
+    const int N = d->nvar;
+    if (N % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 3u) == 0)
+        PACK_DISPATCH(d, launch_k(transpose_in_vec_kernel<PK>, dim3((unsigned)((N + 127) / 128), (unsigned)G), dim3(256), 0, d->stream, src, dst_rows, B, N, limit));
+    else
+        PACK_DISPATCH(d, launch_k(transpose_in_kernel<PK>, dim3((unsigned)((N + 31) / 32), (unsigned)G), dim3(256), 0, d->stream, src, dst_rows, B, N, limit));
+    LAUNCH_CHECK();
+    return LUTLDPC_OK;
+}
+int launch_transpose_out(lutldpc_decoder *d, const uint8_t *src_rows, uint8_t *dst, int B, int G, int rows) {
+    const int N = rows > 0 ? rows : d->nvar;
+    if (N % 4 == 0 && (reinterpret_cast<uintptr_t>(dst) & 3u) == 0)
+        PACK_DISPATCH(d, launch_k(transpose_out_vec_kernel<PK>, dim3((unsigned)((N + 127) / 128), (unsigned)G), dim3(256), 0, d->stream, src_rows, dst, B, N));
+    else
+        PACK_DISPATCH(d, launch_k(transpose_out_kernel<PK>, dim3((unsigned)((N + 31) / 32), (unsigned)G), dim3(256), 0, d->stream, src_rows, dst, B, N));
+    LAUNCH_CHECK();
+    return LUTLDPC_OK;
+}
+
+// keep only the classes flagged in `keep` (the others were handled by specialised kernels)
+static PassParams filter_params(const PassParams &P, const std::vector<char> &keep) {
+    PassParams Q = P;
+    Q.n_seg = 0;
+    int blk = 0;
+    for (int i = 0; i < P.n_seg; i++) {
+        if (!keep[(size_t)i]) continue;
+        PassSeg S = P.seg[i];
+        S.block_begin = blk;
+        blk += (S.n_nodes + P.nodes_per_block - 1) / P.nodes_per_block;
+        Q.seg[Q.n_seg++] = S;
+    }
+    Q.blocks_per_group = blk;
+    return Q;
+}
+
+template <int KIND>
+static int launch_tree_pass(lutldpc_decoder *d, PassPlan &plan, std::vector<FastClassPlan> *fast, const std::vector<const JitKernel *> *jit, int G, int nz, int check, int write_hard, int kind_id,
+                     const std::vector<std::pair<int, int>> *jit_tabs = nullptr) {
+    if (!plan.valid) return fail(LUTLDPC_ERR_STATE, "pass plan missing for this tree set");
+    Timed t(d, kind_id);
+    PassParams P = plan.P;
+    P.G = G; P.nz = nz; P.check = check; P.write_hard = write_hard; P.vfail_stride_w = d->Bcap / 4;
+    std::vector<char> keep((size_t)P.n_seg, 1);
+    bool any = false;
+    // The compile-time and generated variable kernels read the sign of an outgoing label as bit sbit = log2(nz) (exit test and
+    // decided bits); that holds only where nz is a power of two.  A variable pass that writes any other alphabet (Nq_Msg = 12:
+    // nz = 6) runs in the interpreter below, which compares the label with nz.
+    const bool sign_bit = KIND != TT_VAR || is_pow2(nz);
+    // specialised kernels take the classes they know, one launch per degree class
+    if (d->opt.use_fast && fast && KIND != TT_CHK && sign_bit)
+        for (int i = 0; i < P.n_seg; i++) {
+            if (!(*fast)[(size_t)i].ok) continue;
+            bool ok = false;
+            FastParams FP = (*fast)[(size_t)i].P;
+            fill_vn_fast(FP, G, nz, check, write_hard, d->npw_vn(FP.deg), d->E, d->nvar, d->Bcap / 4);
+            DEV_PARAM(dFP, d, FP);
+            PACK_DISPATCH(d, ok = launch_vn_fast<KIND, PK>(d->stream, FP, dFP, d->d_msgs.p, d->d_cha_t.p, d->d_hard.p,
+                                     reinterpret_cast<const uint32_t *>(d->d_state.p), reinterpret_cast<uint32_t *>(d->d_vfail.p), d->d_tables.p, d->d_fast_idx.p));
+            if (ok) keep[(size_t)i] = 0;
+        }
+    // run-time generated kernels (jit.hpp) for the classes without a compile-time one
+    if (jit && sign_bit)
+        for (int i = 0; i < P.n_seg && (size_t)i < jit->size(); i++) {
+            const JitKernel *k = (*jit)[(size_t)i];
+            if (!keep[(size_t)i] || !k) continue;
+            FastParams F{};
+            F.n_nodes = P.seg[i].n_nodes; F.deg = P.seg[i].deg;
+            F.idx_off = KIND == TT_CHK ? d->cn_idx_off[(size_t)i] : d->vn_idx_off[(size_t)i];
+            F.nodes_per_wave = KIND == TT_CHK ? d->npw_cn(F.deg) : d->npw_vn(F.deg); F.waves_per_group = (F.n_nodes + F.nodes_per_wave - 1) / F.nodes_per_wave;
+            F.G = G; F.E = d->E; F.N = d->nvar; F.g0 = 0; F.nz = nz; F.check = check; F.write_hard = write_hard; F.vfail_stride_w = d->Bcap / 4;
+            F.tab_off[0] = P.seg[i].tab_off; F.tab_len[0] = P.seg[i].tab_bytes;
+            if (jit_tabs && (size_t)i < jit_tabs->size() && (*jit_tabs)[(size_t)i].second > 0) { F.tab_off[0] = (*jit_tabs)[(size_t)i].first; F.tab_len[0] = (*jit_tabs)[(size_t)i].second; }   // the kernel was generated for these tables
+            uint8_t *msgs = d->d_msgs.p, *hard = d->d_hard.p;
+            const uint8_t *cha = d->d_cha_t.p, *tables = d->d_tables.p;
+            const uint32_t *state_w = reinterpret_cast<const uint32_t *>(d->d_state.p);
+            uint32_t *vfail_w = reinterpret_cast<uint32_t *>(d->d_vfail.p);
+            const int32_t *fidx = d->d_fast_idx.p;
+            DEV_PARAM(dF, d, F);
+            void *args[] = {&dF, &msgs, &cha, &hard, &state_w, &vfail_w, &tables, &fidx};
+            const unsigned blocks = (unsigned)((F.waves_per_group * G + 3) / 4);
+            HIP_TRY(hipModuleLaunchKernel(k->fn, blocks, 1, 1, 256, 1, 1, 0, d->stream, args, nullptr));
+            keep[(size_t)i] = 0;
+        }
+    for (char k : keep) any = any || k;
+    if (any) {
+        P = filter_params(P, keep);
+        DEV_PARAM(dP, d, P);
+        dim3 grid((unsigned)(P.blocks_per_group * G)), block(64);
+        const int32_t *list = KIND == TT_CHK ? d->d_cn_list.p : d->d_vn_list.p;
+        const int32_t *ptr = KIND == TT_CHK ? d->d_cn_ptr.p : d->d_vn_ptr.p;
+        if (plan.lds_tab)
+            PACK_DISPATCH(d, launch_k(tree_pass_kernel<KIND, true, PK>, grid, block, (size_t)plan.lds_bytes, d->stream, dP, d->d_msgs.p, d->d_cha_t.p,
+                               d->d_hard.p, reinterpret_cast<const uint32_t *>(d->d_state.p), reinterpret_cast<uint32_t *>(d->d_vfail.p),
+                               d->d_ops.p, d->d_tables.p, list, ptr, d->d_cn_idx.p, plan.out_slots));
+        else
+            PACK_DISPATCH(d, launch_k(tree_pass_kernel<KIND, false, PK>, grid, block, (size_t)plan.lds_bytes, d->stream, dP, d->d_msgs.p, d->d_cha_t.p,
+                               d->d_hard.p, reinterpret_cast<const uint32_t *>(d->d_state.p), reinterpret_cast<uint32_t *>(d->d_vfail.p),
+                               d->d_ops.p, d->d_tables.p, list, ptr, d->d_cn_idx.p, plan.out_slots));
+    }
+    LAUNCH_CHECK();
+    return LUTLDPC_OK;
+}
+
+static int launch_cn_minsum(lutldpc_decoder *d, int G, int nz, int check) {
+    Timed t(d, LUTLDPC_K_CN_PASS);
+    PassParams P = d->cn_minsum_plan.P;
+    P.G = G; P.nz = nz; P.check = check; P.vfail_stride_w = d->Bcap / 4;
+    std::vector<char> keep((size_t)P.n_seg, 1);
+    bool any = false;
+    if (d->opt.use_fast)
+        for (int i = 0; i < P.n_seg; i++) {
+            bool ok = false;
+            FastParams FP;
+            if (!fill_cn_fast(FP, P.seg[i].deg, P.seg[i].n_nodes, d->cn_idx_off[(size_t)i], G, d->E, nz, check, d->npw_cn(P.seg[i].deg), d->Bcap / 4)) continue;
+            DEV_PARAM(dFP, d, FP);
+            PACK_DISPATCH(d, ok = launch_cn_fast<PK>(d->stream, FP, dFP, d->d_msgs.p,
+                               reinterpret_cast<const uint32_t *>(d->d_state.p), reinterpret_cast<uint32_t *>(d->d_vfail.p), d->d_fast_idx.p));
+            if (ok) keep[(size_t)i] = 0;
+        }
+    for (char k : keep) any = any || k;
+    if (any) {
+        P = filter_params(P, keep);
+        DEV_PARAM(dP, d, P);
+        PACK_DISPATCH(d, launch_k(cn_minsum_generic_kernel<PK>, dim3((unsigned)(P.blocks_per_group * G)), dim3(64), 0, d->stream, dP, d->d_msgs.p,
+                           reinterpret_cast<const uint32_t *>(d->d_state.p), reinterpret_cast<uint32_t *>(d->d_vfail.p),
+                           d->d_cn_list.p, d->d_cn_ptr.p, d->d_cn_idx.p));
+    }
+    LAUNCH_CHECK();
+    return LUTLDPC_OK;
+}
+
+// Are the decided bits of early-terminated frames recovered at the end (hard_from_frozen_kernel) instead of being stored by
+// every variable pass?  Min-sum checks, one message alphabet, and -- in the skewed pipeline -- chain fusion on in every
+// iteration or in none (the nodes it updates get their bits from the check pass).  `chain_skip`: those nodes are skipped by
+// the recovery.  (Compaction drops the messages of finished frames: its check points run the recovery first.)
+bool late_hard_active(const lutldpc_decoder *d, bool skewed, bool *chain_skip) {
+    if (chain_skip) *chain_skip = false;
+    if (!d->opt.late_hard || !d->psc || !d->min_lut) return false;
+    for (int i = 1; i < d->max_iters; i++) if (d->Nq_Msg[(size_t)i] != d->Nq_Msg[0]) return false;
+    if (!skewed) return true;
+    int on = 0, off = 0;
+    for (int ii = 0; ii + 1 < d->max_iters; ii++) (chain_active(d, d->iter_set[(size_t)ii]) ? on : off)++;
+    if (on && off) return false;
+    if (chain_skip) *chain_skip = on > 0;
+    return true;
+}
+
+// chain fusion applies to a check pass that is followed by a variable pass (not the last iteration) when the degree-2
+// class has the compile-time kernel (its root table is staged)
+bool chain_active(const lutldpc_decoder *d, int set) {
+    if (!d->opt.use_chain || d->chain_vclass < 0 || d->n_chain_nodes == 0) return false;
+    const FastClassPlan &f = d->var_fast[(size_t)set][(size_t)d->chain_vclass];
+    return f.ok && f.P.n_tables == 1 && f.P.tab_len[0] <= 1024;
+}
+
+// Decided bits of the frames that left through the exit test, read off their frozen messages (hard_from_frozen_kernel) and, for
+// the nodes updated inside the check pass, off the parity equations (chain_hard_kernel): groups g0 .. g0+G-1; ctl: a compaction
+// check point's control words (the kernels return when it does not permute) or NULL at the end of the decode.
+int launch_late_hard(lutldpc_decoder *d, bool skewed, int g0, int G, const int32_t *ctl) {
+    bool chain_skip = false;
+    if (!late_hard_active(d, skewed, &chain_skip) || G <= 0) return LUTLDPC_OK;
+    const unsigned gx = ctl ? 1024u : 2048u;
+    PACK_DISPATCH(d, launch_k(hard_from_frozen_kernel<PK>, dim3(std::min<unsigned>(gx, (unsigned)((d->nvar + 3) / 4)), (unsigned)G), dim3(256), 0, d->stream, d->d_msgs.p, d->d_hard.p,
+                                        reinterpret_cast<const uint32_t *>(d->d_state.p), d->d_vn_ptr.p, chain_skip ? d->d_chain_internal.p : nullptr, d->nvar, d->E,
+                                        d->Nq_Msg[0] / 2, g0, ctl));
+    if (chain_skip)
+        for (size_t i = 0; i < d->cclass.size(); i++) {
+            if (d->chain_idx_off[i] < 0) continue;
+            const int n = (int)d->cclass[i].nodes.size(), npw = d->npw_cn_class(i), runs = (n + npw - 1) / npw;
+            PACK_DISPATCH(d, launch_k(chain_hard_kernel<PK>, dim3(std::min<unsigned>(512u, (unsigned)((runs + 3) / 4)), (unsigned)G), dim3(256), 0, d->stream, d->d_hard.p,
+                                                reinterpret_cast<const uint32_t *>(d->d_state.p), d->d_fast_idx.p + d->cn_idx_off[i], d->d_fast_idx.p + d->chain_idx_off[i],
+                                                d->d_edge_vn.p, n, d->cclass[i].deg, npw, d->nvar, g0, ctl));
+        }
+    LAUNCH_CHECK();
+    return LUTLDPC_OK;
+}
+
+// one message dump of the trace: the E edge rows of all frames, frame-major, to the next slot of the host buffer (synchronous)
+static int trace_dump(lutldpc_decoder *d) {
+    lutldpc_decoder::Trace &T = d->trace;
+    const size_t one = (size_t)T.B * (size_t)d->E;
+    if ((size_t)(T.n + 1) * one > T.cap) return fail(LUTLDPC_ERR_ARG, "trace buffer too small");
+    const int G = d->bpad(T.B) / d->tile();
+    HIP_TRY(d->d_trace.alloc(one));
+    if (int rc = launch_transpose_out(d, d->d_msgs.p, d->d_trace.p, T.B, G, d->E)) return rc;
+    LAUNCH_CHECK();
+    HIP_TRY(hipMemcpyAsync(T.host + (size_t)T.n * one, d->d_trace.p, one, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    T.n++;
+    return LUTLDPC_OK;
+}
+
+// d_llr -> frame-major labels in d_in_cha / d_in_msg (lutldpc_decoder_decode_llr_batch)
+int launch_quantize_llr(lutldpc_decoder *d, size_t n, int n_qb_Cha, int n_qb_Msg, int mode) {
+    launch_k(quantize_llr_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d->stream, d->d_llr.p, n, d->d_qb_cha.p, n_qb_Cha,
+                       d->d_qb_msg.p, n_qb_Msg, mode, d->d_map.p, d->d_in_cha.p, d->d_in_msg.p);
+    LAUNCH_CHECK();
+    return LUTLDPC_OK;
+}
+
+// Core: decode the B frames whose labels are already in tile layout (d_cha_t / d_msg0_t).
+// Leaves the decided bits in d_hard (tile layout) and the iteration codes in d_iters.
+static int decode_tiles_launch(lutldpc_decoder *d, int B) {
+    int rc;
+    const int Bpad = d->bpad(B), G = Bpad / d->tile();
+    const int N = d->nvar, E = d->E, I = d->max_iters;
+    const int last_set = d->iter_set[(size_t)(I - 1)];
+    if (!d->dec_plan[(size_t)last_set].valid)
+        return fail(LUTLDPC_ERR_STATE, "the tree set of iteration max_iters-1 is not a decision tree set");
+    if ((rc = launch_state(d, B, Bpad, 0, 0))) return rc;
+    const bool tracing = d->trace.level > 1;
+    if (resident_active(d) && !tracing) {         // the whole of lut_decode in one launch, messages in LDS (jit_resident.hpp)
+        if ((rc = launch_resident(d, G, B))) return rc;
+        if (d->profiling && d->ev_live.size() > 8192) prof_fold(d);
+        return LUTLDPC_OK;
+    }
+    if (d->pisc) {   // :275-279
+        if (is_pow2(d->Nq_Cha / 2)) {
+            if ((rc = launch_syndrome_of_labels(d, G))) return rc;
+        } else {
+            // the decided bit `label < Nq_Cha/2` is the inverted sign BIT of the label only when Nq_Cha/2 is a power of two: any other
+            // channel alphabet goes through decided-bit rows (SWAR compare) and the parity pass over them
+            {
+                Timed t(d, LUTLDPC_K_LAYOUT);
+                const size_t n_words = (size_t)G * (size_t)N * kRowBytes / 4;
+                PACK_DISPATCH(d, launch_k(hard_from_labels_kernel<PK>, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, d->stream, d->d_cha_t.p, d->d_hard.p, n_words, d->Nq_Cha / 2));
+                LAUNCH_CHECK();
+            }
+            if ((rc = launch_syndrome(d, G))) return rc;
+        }
+        if ((rc = launch_state(d, B, Bpad, 1, 0))) return rc;
+        {   // decided bits of the frames that passed = signs of their channel labels (:275); groups without such a frame return at once
+            Timed t(d, LUTLDPC_K_LAYOUT);
+            PACK_DISPATCH(d, launch_k(hard_from_labels_masked_kernel<PK>, dim3(std::min<unsigned>(1024u, (unsigned)((N + 3) / 4)), (unsigned)G), dim3(256), 0, d->stream,
+                                                d->d_cha_t.p, d->d_hard.p, reinterpret_cast<const uint32_t *>(d->d_state.p), N, d->Nq_Cha / 2, 0));
+            LAUNCH_CHECK();
+        }
+    }
+    const bool skewed = d->opt.skew && d->skew_ok && !tracing;      // (a single frame group runs the same launches with an empty second half)
+    if (!(skewed && d->opt.first_from_nodes)) {   // :284-289 (the fused pipeline's first check pass reads the initial-message rows itself)
+        Timed t(d, LUTLDPC_K_LAYOUT);
+        launch_k(init_edges_kernel, dim3((unsigned)((N + 3) / 4), (unsigned)G), dim3(256), 0, d->stream, d->d_msg0_t.p, d->d_msgs.p, d->d_vn_ptr.p, N, E);
+        LAUNCH_CHECK();
+    }
+    if (tracing && (rc = trace_dump(d))) return rc;                              // :292-298
+    if (skewed && (rc = iterate_skewed(d, B, Bpad, G))) return rc;
+    for (int ii = 0; ii < I && !skewed; ii++) {   // :301-338
+        const int set = d->iter_set[(size_t)ii];
+        const int nz_in = d->Nq_Msg[(size_t)ii] / 2;
+        const int chk_check = (d->psc && ii > 0) ? 1 : 0;    // finishes the test started by VN pass ii-1
+        if (d->min_lut) rc = launch_cn_minsum(d, G, nz_in, chk_check);
+        else rc = launch_tree_pass<TT_CHK>(d, d->chk_plan[(size_t)set], nullptr, d->chk_jit.empty() ? nullptr : &d->chk_jit[(size_t)set], G, nz_in, chk_check, 0, LUTLDPC_K_CN_PASS,
+                                           (size_t)set < d->chk_full_tab.size() ? &d->chk_full_tab[(size_t)set] : nullptr);
+        if (rc) return rc;
+        if (chk_check && (rc = launch_state(d, B, Bpad, 2, ii))) return rc;   // :327-329 returns (ii-1)+1
+        if (d->trace.level > 2 && (rc = trace_dump(d))) return rc;             // :311-317
+        if (ii != I - 1) {
+            const int nz_out = d->Nq_Msg[(size_t)(ii + 1)] / 2;
+            rc = launch_tree_pass<TT_VAR>(d, d->var_plan[(size_t)set], &d->var_fast[(size_t)set], d->var_jit.empty() ? nullptr : &d->var_jit[(size_t)set], G, nz_out, d->psc ? 1 : 0,
+                                          (d->psc && !late_hard_active(d, false, nullptr)) ? 1 : 0, LUTLDPC_K_VN_PASS);
+            if (rc) return rc;
+        }
+        if (tracing && (rc = trace_dump(d))) return rc;                         // :331-337 (printed after the last iteration too)
+    }
+    {   // decided bits of the frames that left through the exit test, from their frozen messages (see late_hard_active)
+        Timed t(d, LUTLDPC_K_LAYOUT);
+        if ((rc = launch_late_hard(d, skewed, 0, G, nullptr))) return rc;
+        if (skewed && d->psc && d->pisc && compaction_on(d, G) && late_hard_active(d, true, nullptr) && d->opt.compact_keep) {
+            // frames that passed the test on the channel decisions may have been moved by a permutation: their decided-bit rows
+            // did not travel (no other decided bit exists during the iterations), their channel rows did -- write the bits again
+            PACK_DISPATCH(d, launch_k(hard_from_labels_masked_kernel<PK>, dim3(std::min<unsigned>(1024u, (unsigned)((N + 3) / 4)), (unsigned)G), dim3(256), 0, d->stream,
+                                                d->d_cha_t.p, d->d_hard.p, reinterpret_cast<const uint32_t *>(d->d_state.p), N, d->Nq_Cha / 2, 0));
+            LAUNCH_CHECK();
+        }
+    }
+    // :340-349
+    if ((rc = launch_tree_pass<TT_DEC>(d, d->dec_plan[(size_t)last_set], &d->dec_fast[(size_t)last_set], d->dec_jit.empty() ? nullptr : &d->dec_jit[(size_t)last_set], G, 0, 0, 0, LUTLDPC_K_DECISION))) return rc;
+    const int fsel = skewed ? (I & 1) : 0;            // the flag buffer no pass of the skewed pipeline has written since its last test
+    if ((rc = launch_syndrome(d, G, fsel))) return rc;
+    if ((rc = launch_state(d, B, Bpad, 3, I, 0, -1, fsel))) return rc;
+    if (skewed && d->psc && compaction_on(d, G)) {
+        const HalfRange half[2] = {{0, (G + 1) / 2}, {(G + 1) / 2, G - (G + 1) / 2}};
+        if ((rc = launch_uncompaction(d, half, Bpad))) return rc;
+    }
+    if (d->profiling && d->ev_live.size() > 8192) prof_fold(d);
+    return LUTLDPC_OK;
+}
+
+// A decode is 100-300 short launches whose arguments depend only on (B, exit conditions): from the
+// second call with the same key on, the sequence is replayed as ONE hipGraph launch (the first call runs
+// plainly and fills the item-table cache, whose uploads may not happen inside a capture).  Short codes
+// are launch-bound, for them this is worth ~20 %.  Off while kernel events are being recorded.
+int decode_tiles(lutldpc_decoder *d, int B) {
+    if (int rc = check_batch_buffers(d, d->bpad(B))) return rc;
+    if (resident_active(d)) {                     // generate / compile / load outside any stream capture
+        lutldpc_decoder::ResidentPlan *pl = nullptr;
+        if (int rc = resident_plan_for(d, d->bpad(B) / d->tile(), &pl)) return rc;
+    }
+    // (the resident decoder is ONE launch plus the state kernel: nothing to gain from a graph, and the frame-major pointers of the
+    // caller would be frozen into it)
+    if (!d->opt.use_graph || d->profiling || d->trace.level > 1 || resident_active(d)) return decode_tiles_launch(d, B);
+    const std::array<int, 4> key = {B, d->psc, d->pisc, d->max_iters};
+    if (d->graphs.size() > 32 && !d->graphs.count(key)) d->drop_graphs();      // callers with ever-changing batch sizes: bound the cache
+    auto &slot = d->graphs[key];
+    if (slot.exec) {
+        HIP_TRY(hipGraphLaunch(slot.exec, d->stream));
+        return LUTLDPC_OK;
+    }
+    if (slot.seen++ == 0) return decode_tiles_launch(d, B);
+    HIP_TRY(hipStreamBeginCapture(d->stream, hipStreamCaptureModeThreadLocal));
+    const int rc = decode_tiles_launch(d, B);
+    hipGraph_t g = nullptr;
+    const hipError_t e = hipStreamEndCapture(d->stream, &g);
+    if (rc || e != hipSuccess || !g) {
+        if (g) (void)hipGraphDestroy(g);
+        (void)hipGetLastError();
+        d->opt.use_graph = 0;                             // capture not possible here: plain launches from now on
+        return rc ? rc : decode_tiles_launch(d, B);
+    }
+    const hipError_t ei = hipGraphInstantiate(&slot.exec, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    if (ei != hipSuccess) { slot.exec = nullptr; d->opt.use_graph = 0; (void)hipGetLastError(); return decode_tiles_launch(d, B); }
+    HIP_TRY(hipGraphLaunch(slot.exec, d->stream));
+    return LUTLDPC_OK;
+}
+
+// The batched lut_decode (src/LDPC_Code_LUT.cpp:259-353) on device-resident frame-major labels.
+int decode_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d_msg0, int B, uint8_t *d_out_bits, int32_t *d_out_iters) {
+    if (d->device < 0) return fail(LUTLDPC_ERR_STATE, "decoder was created without a device (host-only handle)");
+    if (B <= 0) return fail(LUTLDPC_ERR_ARG, "B must be positive");
+    HIP_TRY(hipSetDevice(d->device));
+    int rc = ensure_batch(d, B);
+    if (rc) return rc;
+    const int Bpad = d->bpad(B), G = Bpad / d->tile();
+    // the LDS-resident decoder reads the frame-major labels and writes the frame-major bits itself
+    const bool direct = resident_active(d) && d->opt.resident_fm && d->trace.level <= 1;
+    if (!direct) {
+        Timed t(d, LUTLDPC_K_LAYOUT);
+        if ((rc = launch_transpose_in(d, d_cha, d->d_cha_t.p, B, G, d->Nq_Cha))) return rc;
+        if ((rc = launch_transpose_in(d, d_msg0, d->d_msg0_t.p, B, G, d->Nq_Msg[0]))) return rc;
+        LAUNCH_CHECK();
+    }
+    if (direct) { d->fm_cha = d_cha; d->fm_msg0 = d_msg0; d->fm_bits = d_out_bits; }
+    rc = decode_tiles(d, B);
+    d->fm_cha = d->fm_msg0 = nullptr; d->fm_bits = nullptr;
+    if (rc) return rc;
+    {
+        Timed t(d, LUTLDPC_K_LAYOUT);
+        if (!direct && (rc = launch_transpose_out(d, d->d_hard.p, d_out_bits, B, G))) return rc;
+        HIP_TRY(hipMemcpyAsync(d_out_iters, d->d_iters.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToDevice, d->stream));
+    }
+    return LUTLDPC_OK;
+}
+
+#pragma GCC visibility pop

@@ -6,7 +6,7 @@
 //     ber_sim designs in its auto modes (src/LDPC_BER_Sim.cpp:487-489) -- expanded at compile time with
 //     every shared sub-expression computed once and evaluated frame by frame on unpacked labels;
 //   * pass_fused_kernel: the check pass of one half of the frame groups and the variable pass of the
-//     other half in one launch (the skewed two-half pipeline of decoder.hip).
+//     other half in one launch (the skewed two-half pipeline of decoder_skew.hip).
 // Other tree shapes get kernels generated at run time (jit.hpp); kernels_generic.hpp is the fallback.
 //
 // Roofline: HBM-bound streaming of 256-byte rows.  Algorithmic bytes per launch with b bytes per label:
@@ -39,7 +39,7 @@ namespace lutldpc {
 // CHAIN (UNR = 1): a degree-2 variable node shared by two consecutive checks of this wave is updated here -- its two
 // incoming messages are this check's output r[0] and the previous check's output r[1], held back in `pend` -- and
 // the NEW variable-to-check messages are stored instead of the check-to-variable ones: one write and one read less per
-// such edge and iteration (decoder.hip: build_fast_index puts the chain edges at slots 0 / 1 of the edge table).
+// such edge and iteration (decoder_setup.hip: build_fast_index puts the chain edges at slots 0 / 1 of the edge table).
 // FIRST (the check pass of iteration 0 in the fused pipeline): every edge still carries its variable node's initial message
 // (src/LDPC_Code_LUT.cpp:284-289), so the inputs are read from the N initial-message rows through a second table holding the
 // NODE of every check edge -- the E edge rows are written for the first time by this pass, no separate copy kernel.
@@ -588,7 +588,7 @@ __global__ __launch_bounds__(256) void vn_balanced_fast_kernel(
 // variable pass on the other half.  The variable pass is bound by LDS look-ups (34 per frame for a
 // degree-8 node), the check pass by HBM streaming and a little VALU work; taken alone each leaves the
 // other resource idle.  The two halves of a batch are independent decodes, so the host runs them half
-// an iteration out of phase (decoder.hip: decode_tiles_skewed) and every launch mixes both kinds of
+// an iteration out of phase (decoder_skew.hip: iterate_skewed) and every launch mixes both kinds of
 // work on every CU: blocks are handed to roles (degree class x pass kind x half) through an
 // interleaved item table, each block stays homogeneous (one role) so its tables sit at LDS offset 0.
 // occupancy window of the first bucket's fused kernel (build-time knobs for tools/ab_variants.sh; 7..8 measured best)
@@ -634,7 +634,7 @@ struct RoleParams {
     ChainParams chain;     // check roles only
     int32_t tab_off[kFusedMaxTables], tab_len[kFusedMaxTables], tab_shift[kFusedMaxTables];
 };
-// host-side staging of the roles of one launch (decoder.hip builds these once per (batch shape, exit conditions) and keeps
+// host-side staging of the roles of one launch (decoder_skew.hip builds these once per (batch shape, exit conditions) and keeps
 // them in DEVICE memory: the kernel gets a pointer, not the 3.4 KB by value)
 struct FusedParams {
     int32_t n_roles;
@@ -771,7 +771,7 @@ inline FastClassPlan plan_fast_vn(const Tree &t, int kind, int d, const std::map
 // ------------------------------------------------------------------------------------------
 // Host-side launchers.  They are ordinary (non-inline) function templates, explicitly instantiated in
 // their own translation units (fast_vn_var.hip, fast_vn_dec.hip, fast_cn.hip, fused.hip) so that the
-// ~250 kernel instantiations compile in parallel; decoder.hip sees `extern template` declarations.
+// ~250 kernel instantiations compile in parallel; the decoder units see `extern template` declarations (decoder_state.hpp).
 constexpr int kFastMaxDeg = 20;      // variable / decision nodes
 constexpr int kFastMaxCnDeg = 32;    // check nodes
 
@@ -859,7 +859,7 @@ void launch_fused(hipStream_t s, const RoleParams *d_roles, const int32_t *items
                  state_w, vfail_w, tables, fast_idx, msg0);
 }
 // force the code object of this translation unit onto the current device now (HIP loads code objects lazily, at the first
-// launch of one of their kernels): decoder.hip calls these at decoder creation, see preload_code_objects
+// launch of one of their kernels): decoder_setup.hip calls these at decoder creation, see preload_code_objects
 template <int PACK, int BUCKET>
 hipError_t preload_fused() {
     hipFuncAttributes a;

@@ -115,11 +115,12 @@ def scenarios(which):
                 run(name, B, snr, env, [(True, True), (False, False)])
         done.append("kernel_variants")
     if which in ("all", "skew"):
-        # skewed pipeline, graph replay (three calls with one key: plain, capture, replay), compaction, no chain
+        # skewed pipeline, graph replay (three calls with one key: plain, capture, replay), compaction, no chain -- on the streaming
+        # path (LUTLDPC_RESIDENT=0, as the GPU tests of these paths set it: codes this small are otherwise decoded out of LDS in one launch)
         for env in [{}, {"LUTLDPC_PACK": "1"}, {"LUTLDPC_SKEW": "0"}, {"LUTLDPC_COMPACT": "1", "LUTLDPC_COMPACT_FIRST": "2", "LUTLDPC_COMPACT_EVERY": "1", "LUTLDPC_COMPACT_MARGIN": "0"}, {"LUTLDPC_CHAIN": "0"},
                     {"LUTLDPC_GRAPH": "0"}]:
             for name, B, snr in [("n500_q4", 1100, 1.6), ("reg36_n1000_q4", 1537, 2.0), ("reg36_n1000_mixed", 1025, 2.2)]:
-                run(name, B, snr, env, [(True, True), (True, False), (False, False)], repeats=3, with_oracle=False)
+                run(name, B, snr, dict(env, LUTLDPC_RESIDENT="0"), [(True, True), (True, False), (False, False)], repeats=3, with_oracle=False)
         assert fake.fakehip_captures() > 0 and fake.fakehip_graph_launches() > 0, "the graph path was not exercised"
         assert fake.fakehip_launches_of(b"pass_fused_kernel") > 0, "the fused kernel was never launched"
         done.append("skew")

@@ -151,7 +151,7 @@ def test_compaction_that_drops_the_rows_of_finished_frames(monkeypatch):
 
 def test_placement_search_of_the_row_buffers_changes_nothing_but_where_they_are(monkeypatch):
     """A batch whose rows exceed 1 GiB makes the streaming decoder try several allocations of its row buffers and keep the fastest
-    (decoder.hip: place_rows; DESIGN.md "The levels are buffer placement"): describe() reports the search, the outputs equal those of a
+    (decoder_batch.hip: place_rows; DESIGN.md "The levels are buffer placement"): describe() reports the search, the outputs equal those of a
     decoder that takes the first allocation (LUTLDPC_PLACE=0) in both exit modes, and a sample of frames equals the oracle."""
     cd = oracle_codec("dvbs2_q4_i6")
     B = 5300                                   # 11 frame groups: 1.19 GB of rows
