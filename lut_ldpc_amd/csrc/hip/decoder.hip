@@ -378,22 +378,23 @@ int lutldpc_selftest_program_stats(lutldpc_decoder *d, int kind, int set, int cl
     return LUTLDPC_OK;
 }
 
+// a generated source handed to the caller: optionally run through hiprtc first (no device needed), copied when cap suffices
+static int64_t give_source(const std::string &src, char *buf, int64_t cap, int compile) {
+    if (compile) {
+        std::vector<char> code; std::string log;
+        if (!jit_compile(src, code, log)) return fail(LUTLDPC_ERR_HIP, "hiprtc: " + log.substr(0, 4000));
+    }
+    if (buf && cap > (int64_t)src.size()) std::memcpy(buf, src.c_str(), src.size() + 1);
+    return (int64_t)src.size() + 1;
+}
+
 int64_t lutldpc_selftest_jit_source(lutldpc_decoder *d, int kind, int set, int cls, char *buf, int64_t cap, int compile) {
     if (!d) return fail(LUTLDPC_ERR_ARG, "NULL decoder");
     const Program *p = find_prog(d, kind, set, cls);
     if (!p) return fail(LUTLDPC_ERR_ARG, "no such program");
-    const PassPlan &plan = kind == TT_VAR ? d->var_plan[(size_t)set] : kind == TT_DEC ? d->dec_plan[(size_t)set] : d->chk_plan[(size_t)set];
     std::string src, err;
-    const bool gen = kind == TT_CHK ? jit_cn_source(*p, d->cclass[(size_t)cls].deg, d->pack, plan.P.seg[cls].tab_bytes, src, err)
-                                    : jit_vn_source(*p, kind, d->vclass[(size_t)cls].deg, d->pack, plan.P.seg[cls].tab_bytes, src, err);
-    if (!gen) return fail(LUTLDPC_ERR_UNSUPPORTED, err);
-    if (compile) {
-        std::vector<char> code;
-        std::string log;
-        if (!jit_compile(src, code, log)) return fail(LUTLDPC_ERR_HIP, "hiprtc: " + log);
-    }
-    if (buf && cap > (int64_t)src.size()) std::memcpy(buf, src.c_str(), src.size() + 1);
-    return (int64_t)src.size() + 1;
+    if (!jit_class_source(d, kind, (size_t)set, (size_t)cls, src, err)) return fail(LUTLDPC_ERR_UNSUPPORTED, err);
+    return give_source(src, buf, cap, compile);
 }
 
 // Source of the LDS-resident decode kernel for a batch of G frame groups (jit_resident.hpp); compile != 0 also runs hiprtc (no
@@ -405,13 +406,7 @@ int64_t lutldpc_selftest_resident_source(lutldpc_decoder *d, int G, char *buf, i
     std::string src, err;
     if (!jit_resident_source(resident_spec(d, S, NT), src, err)) return fail(LUTLDPC_ERR_UNSUPPORTED, "resident decoder: " + err);
     if (info) { info[0] = S; info[1] = NT; info[2] = lds; }
-    if (compile) {
-        std::vector<char> code;
-        std::string log;
-        if (!jit_compile(src, code, log)) return fail(LUTLDPC_ERR_HIP, "hiprtc: " + log.substr(0, 4000));
-    }
-    if (buf && cap > (int64_t)src.size()) std::memcpy(buf, src.c_str(), src.size() + 1);
-    return (int64_t)src.size() + 1;
+    return give_source(src, buf, cap, compile);
 }
 
 }  // extern "C"

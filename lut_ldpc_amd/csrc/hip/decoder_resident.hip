@@ -102,22 +102,13 @@ int resident_plan_for(lutldpc_decoder *d, int G, lutldpc_decoder::ResidentPlan *
         // equal (S, NT) of another batch size: the same kernel
         for (auto &kv : d->resident_plans) if (kv.second.S == pl.S && kv.second.NT == pl.NT) pl.k = kv.second.k;
         if (!pl.k) {
-            std::string src, err;
+            std::string src, err, log;
             if (!jit_resident_source(resident_spec(d, pl.S, pl.NT), src, err)) return fail(LUTLDPC_ERR_UNSUPPORTED, "resident decoder: " + err);
-            JitRegistry &reg = jit_registry();
-            std::lock_guard<std::mutex> lock(reg.mu);
-            const std::string key = std::to_string(d->device) + "\n" + src;
-            auto kt = reg.by_src.find(key);
-            if (kt == reg.by_src.end()) {
-                if (reg.by_src.size() >= kJitRegistryMax) return fail(LUTLDPC_ERR_STATE, "generated-kernel registry full");
-                std::vector<char> code;
-                JitKernel k;
-                std::string log;
-                if (!jit_compile(src, code, log) || !jit_load(code, k, log)) { d->resident_log = log; reg.by_src[key] = JitKernel(); return fail(LUTLDPC_ERR_HIP, "resident decoder: hiprtc / module load failed: " + log.substr(0, 2000)); }
-                kt = reg.by_src.emplace(key, k).first;
-            }
-            if (!kt->second.ok()) return fail(LUTLDPC_ERR_HIP, "resident decoder: kernel unavailable (earlier compile failure)");
-            pl.k = &kt->second;
+            JitKernel *k = jit_get(d->device, src, log);
+            if (!k) return fail(LUTLDPC_ERR_STATE, "generated-kernel registry full");
+            if (!log.empty()) { d->resident_log = log; return fail(LUTLDPC_ERR_HIP, "resident decoder: hiprtc / module load failed: " + log.substr(0, 2000)); }
+            if (!k->ok()) return fail(LUTLDPC_ERR_HIP, "resident decoder: kernel unavailable (earlier compile failure)");
+            pl.k = k;
         }
         it = d->resident_plans.emplace(G, pl).first;
     }

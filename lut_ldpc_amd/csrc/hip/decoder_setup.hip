@@ -364,6 +364,34 @@ static bool fast_covers(const lutldpc_decoder *d, const std::vector<FastClassPla
 // generated kernels are simply not used (the interpreter runs instead).
 JitRegistry &jit_registry() { static JitRegistry *r = new JitRegistry; return *r; }     // never destroyed (see above)
 
+// The kernel of `src` on `device`: from the registry, else compiled, loaded and remembered -- a failure too (an entry that is not
+// ok(); `log` receives the diagnostic of a failure that happened in this call only).  nullptr: the registry is full.
+JitKernel *jit_get(int device, const std::string &src, std::string &log) {
+    JitRegistry &reg = jit_registry();
+    std::lock_guard<std::mutex> lock(reg.mu);
+    const std::string key = std::to_string(device) + "\n" + src;
+    auto it = reg.by_src.find(key);
+    if (it == reg.by_src.end()) {
+        if (reg.by_src.size() >= kJitRegistryMax) return nullptr;
+        std::vector<char> code; JitKernel k; std::string out;      // (out: hiprtc may leave warnings on success, not handed on)
+        if (!jit_compile(src, code, out) || !jit_load(code, k, out)) { k = JitKernel(); log = out.empty() ? "hiprtc returned no code object" : out; }
+        it = reg.by_src.emplace(key, k).first;
+    }
+    return &it->second;                                   // (std::map nodes are stable: the pointer outlives the lock)
+}
+
+// Source of the streaming pass kernel of class i of tree set s as build_jit compiles it.  kind: TT_VAR, TT_DEC, TT_CHK (the
+// sign/magnitude program) or TT_CHK + 32 (the full-label program, with its own table blob)
+bool jit_class_source(const lutldpc_decoder *d, int kind, size_t s, size_t i, std::string &src, std::string &err) {
+    if (kind == TT_CHK + 32 && s < d->chk_full_tab.size() && i < d->chk_full_tab[s].size() && d->chk_full_tab[s][i].second > 0)
+        return jit_cn_source(d->chk_prog_full[s][i], d->cclass[i].deg, d->pack, d->chk_full_tab[s][i].second, src, err);
+    if (kind != TT_VAR && kind != TT_DEC && kind != TT_CHK) { err = "only variable / decision / check-tree programs are generated"; return false; }
+    const PassPlan &plan = kind == TT_VAR ? d->var_plan[s] : kind == TT_DEC ? d->dec_plan[s] : d->chk_plan[s];
+    const auto &progs = kind == TT_VAR ? d->var_prog[s] : kind == TT_DEC ? d->dec_prog[s] : d->chk_prog[s];
+    return kind == TT_CHK ? jit_cn_source(progs[i], d->cclass[i].deg, d->pack, plan.P.seg[i].tab_bytes, src, err)
+                          : jit_vn_source(progs[i], kind, d->vclass[i].deg, d->pack, plan.P.seg[i].tab_bytes, src, err);
+}
+
 // HIP loads the code object of a translation unit lazily, at the first launch of one of its kernels -- possibly in the
 // middle of a decode and long after other modules came and went.  Load all of them at the first decoder creation on a
 // device instead, while nothing of ours is in flight.
@@ -382,8 +410,7 @@ static int preload_code_objects(int device) {
     return LUTLDPC_OK;
 }
 
-// jit.hpp: generate + compile + load a kernel for every variable / decision / CHKTREE class without a
-// compile-time specialised one
+// jit.hpp: generate + compile + load a kernel for every variable / decision / CHKTREE class without a compile-time specialised one
 static void build_jit(lutldpc_decoder *d) {
     const size_t ns = d->var_plan.size();
     d->var_jit.assign(ns, {}); d->dec_jit.assign(ns, {}); d->chk_jit.assign(ns, {});
@@ -393,31 +420,18 @@ static void build_jit(lutldpc_decoder *d) {
             if (kind == TT_CHK && d->min_lut) continue;
             const PassPlan &plan = kind == TT_VAR ? d->var_plan[s] : kind == TT_DEC ? d->dec_plan[s] : d->chk_plan[s];
             if (!plan.valid) continue;
-            const auto &progs = kind == TT_VAR ? d->var_prog[s] : kind == TT_DEC ? d->dec_prog[s] : d->chk_prog[s];
             const auto &cls = kind == TT_CHK ? d->cclass : d->vclass;
             auto &out = kind == TT_VAR ? d->var_jit[s] : kind == TT_DEC ? d->dec_jit[s] : d->chk_jit[s];
             out.assign(cls.size(), nullptr);
             for (size_t i = 0; i < cls.size(); i++) {
                 if (kind != TT_CHK && fast_covers(d, kind == TT_VAR ? d->var_fast[s] : d->dec_fast[s], i)) continue;
-                std::string src, err;
+                std::string src, log;
                 const bool full = kind == TT_CHK && s < d->chk_full_tab.size() && i < d->chk_full_tab[s].size() && d->chk_full_tab[s][i].second > 0;
-                const bool gen = kind == TT_CHK ? (full ? jit_cn_source(d->chk_prog_full[s][i], cls[i].deg, d->pack, d->chk_full_tab[s][i].second, src, err)
-                                                        : jit_cn_source(progs[i], cls[i].deg, d->pack, plan.P.seg[i].tab_bytes, src, err))
-                                                : jit_vn_source(progs[i], kind, cls[i].deg, d->pack, plan.P.seg[i].tab_bytes, src, err);
-                if (!gen) { d->jit_log = err; continue; }
-                JitRegistry &reg = jit_registry();
-                std::lock_guard<std::mutex> lock(reg.mu);
-                const std::string key = std::to_string(d->device) + "\n" + src;
-                auto it = reg.by_src.find(key);
-                if (it == reg.by_src.end()) {
-                    if (reg.by_src.size() >= kJitRegistryMax) { d->jit_log = "generated-kernel registry full"; continue; }
-                    std::vector<char> code;
-                    JitKernel k;
-                    std::string log;
-                    if (!jit_compile(src, code, log) || !jit_load(code, k, log)) { d->jit_log = log; reg.by_src[key] = JitKernel(); continue; }
-                    it = reg.by_src.emplace(key, k).first;
-                }
-                if (it->second.ok()) out[i] = &it->second;        // (std::map nodes are stable: the pointer outlives the lock)
+                if (!jit_class_source(d, full ? TT_CHK + 32 : kind, s, i, src, log)) { d->jit_log = log; continue; }
+                JitKernel *k = jit_get(d->device, src, log);
+                if (!k) { d->jit_log = "generated-kernel registry full"; continue; }
+                if (!log.empty()) d->jit_log = log;
+                if (k->ok()) out[i] = k;
             }
         }
 }

@@ -317,6 +317,8 @@ int upload_static(lutldpc_decoder *d);
 struct JitRegistry { std::mutex mu; std::map<std::string, JitKernel> by_src; };
 constexpr size_t kJitRegistryMax = 4096;
 JitRegistry &jit_registry();
+JitKernel *jit_get(int device, const std::string &src, std::string &log);      // registry look-up, else compile + load + remember
+bool jit_class_source(const lutldpc_decoder *d, int kind, size_t s, size_t i, std::string &src, std::string &err);
 
 // ---- decoder_batch.hip
 int ensure_batch(lutldpc_decoder *d, int B);

@@ -11,10 +11,13 @@
 // round-robin every pass.  Per iteration two (fixed work) or three (exit test on) workgroup barriers.  A set whose frames have
 // all left through the exit test costs nothing any more, a workgroup whose sets are all done returns: the retire grain of
 // parity_check_iter = true is 8 frames, not a 512-frame group.
-// The node updates are the node programs of lut_program.hpp emitted as straight-line code (like jit.hpp), the min-sum is
-// res_minsum (kernels_resident.hpp, the SWAR arithmetic of cn_minsum_body).
+// The node updates are the node programs of lut_program.hpp emitted as straight-line code by the emitters of jit.hpp
+// (emit_var_ops, emit_chk_ops: the statements of the streaming kernels), the min-sum is res_minsum (kernels_resident.hpp, the SWAR
+// arithmetic of cn_minsum_body).  The kernel's arguments, ResidentArgs, are declared once, in kernels_resident.hpp: the host
+// includes that header, the generated source starts with its text.
 #pragma once
 #include "jit.hpp"
+#include "kernels_resident.hpp"      // ResidentArgs: the one declaration host and generated source share
 #include "lut_program.hpp"
 
 #include <algorithm>
@@ -27,25 +30,6 @@ namespace lutldpc {
 static const char *const kResidentHeaderText =
 #include "kernels_resident.inc"
     ;
-
-struct ResidentArgs {              // kernel arguments (by value: 112 bytes)
-    const uint8_t *cha, *msg0;     // label rows [G][N][256 B]
-    uint8_t *hard;                 // decided-bit rows
-    uint8_t *state;                // per-frame state bytes
-    int32_t *iters;                // per-frame iteration codes
-    const uint8_t *tables;         // the decoder's table blob
-    const int32_t *idx;            // the decoder's dense index blob (build_fast_index)
-    int32_t n_sets;                // 64 * frame groups
-    int32_t max_iters, psc, pisc;
-    int32_t B;                     // frames of the batch (frame-major I/O: frames beyond it read as label 0)
-    // frame-major I/O (the C-ABI's own layout, [B][N] bytes): when fm_cha is set the kernel reads the labels and writes the decided
-    // bits there itself -- a thread's eight frames of a node are eight byte accesses, 64 lanes of consecutive nodes one 64-byte
-    // segment per frame -- and the three transposes around the decode disappear (9 % of a (6,32) N=2048 step)
-    const uint8_t *fm_cha, *fm_msg0;
-    uint8_t *fm_bits;
-    int32_t lim_cha, lim_msg;      // labels are clamped to the alphabets like the transposes do
-};
-static_assert(sizeof(ResidentArgs) <= 128, "kernel arguments stay small (DESIGN.md section 7.1)");
 
 struct ResidentClass { int deg = 0, n = 0, idx_off = 0, nidx_off = 0; };
 struct ResidentSpec {
@@ -64,117 +48,50 @@ struct ResidentSpec {
 
 namespace resident_detail {
 
-inline std::string S_(long long v) { return std::to_string(v); }
-
-// label expression of one look-up of a variable / decision program: operands are named values (one frame each)
-inline bool var_label(const Op &op, const std::vector<std::string> &name, std::string &label, std::string &err) {
-    bool all_pow2 = true;
-    for (int c = 0; c < op.nchild; c++) all_pow2 = all_pow2 && jit_pow2(op.mult[c]) && jit_pow2(op.childK[c]);
-    label.clear();
-    for (int c = 0; c < op.nchild; c++) {
-        const std::string &x = name[(size_t)op.child[c]];
-        if (x.empty()) { err = "operand read before it is written"; return false; }
-        if (c == 0) label = op.mult[c] == 1 ? x : "(" + x + " * " + S_(op.mult[c]) + "u)";
-        else if (all_pow2) label = "lshl_or(" + x + ", " + S_(__builtin_ctz(op.mult[c])) + ", " + label + ")";
-        else label = "(" + label + " + " + x + " * " + S_(op.mult[c]) + "u)";
-    }
-    return true;
-}
-
 // The frame loop of a variable (TT_VAR) / decision (TT_DEC) item: inputs raw[0..deg] (raw[deg] = channel dword), tables at
 // `tb` (uint8_t *, LDS); results out[0..deg-1] (VAR) / hardw (DEC).  U frames per trip (independent: ILP for the LDS latency).
 inline bool emit_var_frames(std::ostringstream &o, const Program &prog, int kind, int deg, int U, const std::string &ind, std::string &err) {
-    if (prog.n_in != deg + 1) { err = "unexpected input count"; return false; }
     o << ind << "#pragma unroll 1\n" << ind << "for (int fs = 0; fs < F * BITS; fs += " << U << " * BITS) {\n";
     for (int u = 0; u < U; u++) {
-        const std::string sfx = "_" + S_(u), sh = u ? "(uint32_t)(fs + " + S_(u) + " * BITS)" : "(uint32_t)fs";
-        std::vector<std::string> name((size_t)std::max(prog.n_slots, prog.n_in) + 1);
-        for (int k = 0; k <= deg; k++) {
-            o << ind << "    const uint32_t i" << k << sfx << " = __builtin_amdgcn_ubfe(raw[" << k << "], " << sh << ", (uint32_t)BITS);\n";
-            name[(size_t)k] = "i" + S_(k) + sfx;
-        }
-        for (size_t j = 0; j < prog.ops.size(); j++) {
-            const Op &op = prog.ops[j];
-            if (op.kind != 0) { err = "check-type look-up in a variable program"; return false; }
-            if ((size_t)op.dst >= name.size()) name.resize((size_t)op.dst + 1);
-            std::string label;
-            if (!var_label(op, name, label, err)) return false;
-            const std::string t = "t" + S_((long long)j) + sfx;
-            o << ind << "    const uint32_t " << t << " = tb[" << op.tab_off << "u + " << label << "];\n";
-            name[(size_t)op.dst] = t;
-            if (op.out_idx >= 0) {
-                if (kind == TT_DEC) o << ind << "    hardw = lshl_or(" << t << " < 1u ? 1u : 0u, " << sh << ", hardw);\n";      // src/LDPC_Code_LUT.cpp:342
-                else o << ind << "    out[" << op.out_idx << "] = lshl_or(" << t << ", " << sh << ", out[" << op.out_idx << "]);\n";
-            }
-        }
+        const std::string sh = u ? "(uint32_t)(fs + " + jit_num(u) + " * BITS)" : "(uint32_t)fs";
+        auto on_out = [&](const Op &op, const std::string &t) {
+            if (kind == TT_DEC) o << ind << "    hardw = lshl_or(" << t << " < 1u ? 1u : 0u, " << sh << ", hardw);\n";      // src/LDPC_Code_LUT.cpp:342
+            else o << ind << "    out[" << op.out_idx << "] = lshl_or(" << t << ", " << sh << ", out[" << op.out_idx << "]);\n";
+        };
+        if (!emit_var_ops(o, prog, deg, ind + "    ", "tb", sh, "_" + jit_num(u), on_out, err)) return false;
     }
     o << ind << "}\n";
     return true;
 }
 
-// The frame loop of a CHKTREE item (min_lut = false, src/LUT_Tree.cpp:792-807,420-445): inputs x[0..deg-1], outputs out[0..deg-1];
-// par_w collects the parity of the incoming signs (one bit per element) when `chk`.
+// The frame loop of a CHKTREE item: inputs x[0..deg-1], tables at `tc`, outputs out[0..deg-1]; par_w collects the parity of the
+// incoming signs (one bit per element) when `chk`.
 inline bool emit_chk_frames(std::ostringstream &o, const Program &prog, int deg, const std::string &ind, std::string &err) {
-    if (prog.kind != TT_CHK || prog.n_in != deg || prog.n_out != deg) { err = "not a check program of this degree"; return false; }
     o << ind << "#pragma unroll 1\n" << ind << "for (int fs = 0; fs < F * BITS; fs += BITS) {\n";
-    std::vector<std::string> name((size_t)std::max(prog.n_slots, prog.n_in) + 1), smname(name.size());
-    std::vector<int> sm_of(name.size(), 0);
-    for (int k = 0; k < deg; k++) {
-        o << ind << "    const uint32_t i" << k << " = __builtin_amdgcn_ubfe(x[" << k << "], (uint32_t)fs, (uint32_t)BITS);\n";
-        name[(size_t)k] = "i" + S_(k);
-    }
-    o << ind << "    if (chk) {\n" << ind << "        uint32_t par = 0;\n";
-    for (int k = 0; k < deg; k++) o << ind << "        par ^= i" << k << " < nz ? 1u : 0u;\n";
-    o << ind << "        par_w = lshl_or(par, fs, par_w);\n" << ind << "    }\n";
-    for (size_t j = 0; j < prog.ops.size(); j++) {
-        const Op &op = prog.ops[j];
-        if (op.kind != 1 && op.kind != 2) { err = "variable-type look-up in a check program"; return false; }
-        if ((size_t)op.dst >= name.size()) { name.resize((size_t)op.dst + 1); sm_of.resize(name.size(), 0); smname.resize(name.size()); }
-        if (op.kind == 2) {       // table over the children's full labels (lut_program.hpp: chk_full_label_program)
-            bool p2 = true;
-            for (int c = 0; c < op.nchild; c++) p2 = p2 && jit_pow2(op.mult[c]) && jit_pow2(op.childK[c]);
-            std::string label;
-            for (int c = 0; c < op.nchild; c++) {
-                const std::string &xn = name[(size_t)op.child[c]];
-                if (xn.empty()) { err = "operand read before it is written"; return false; }
-                if (c == 0) label = op.mult[c] == 1 ? xn : "(" + xn + " * " + S_(op.mult[c]) + "u)";
-                else if (p2) label = "lshl_or(" + xn + ", " + S_(__builtin_ctz(op.mult[c])) + ", " + label + ")";
-                else label = "(" + label + " + " + xn + " * " + S_(op.mult[c]) + "u)";
-            }
-            const std::string t = "t" + S_((long long)j);
-            o << ind << "    const uint32_t " << t << " = tc[" << op.tab_off << "u + " << label << "];\n";
-            name[(size_t)op.dst] = t;
-            if (op.out_idx >= 0) o << ind << "    out[" << op.out_idx << "] = lshl_or(" << t << ", fs, out[" << op.out_idx << "]);\n";
-            continue;
-        }
-        bool all_pow2 = jit_pow2(op.half_len);
-        for (int c = 0; c < op.nchild; c++) all_pow2 = all_pow2 && jit_pow2(op.mult[c]) && jit_pow2((uint32_t)op.childK[c] >> 1);
-        std::string label, par;
-        for (int c = 0; c < op.nchild; c++) {
-            const size_t sl = op.child[c];
-            const std::string &xn = name[sl];
-            if (xn.empty()) { err = "operand read before it is written"; return false; }
-            const int hh = op.childK[c] >> 1;
-            if (sm_of[sl] != hh || smname[sl] != xn) {
-                o << ind << "    const uint32_t n_" << xn << " = " << xn << " < " << hh << "u ? 1u : 0u, m_" << xn << " = n_" << xn << " ? " << hh - 1 << "u - " << xn
-                  << " : " << xn << " - " << hh << "u;\n";
-                sm_of[sl] = hh; smname[sl] = xn;
-            }
-            const std::string m = "m_" + xn, n = "n_" + xn;
-            if (c == 0) label = op.mult[c] == 1 ? m : "(" + m + " * " + S_(op.mult[c]) + "u)";
-            else if (all_pow2) label = "lshl_or(" + m + ", " + S_(__builtin_ctz(op.mult[c])) + ", " + label + ")";
-            else label = "(" + label + " + " + m + " * " + S_(op.mult[c]) + "u)";
-            par = c == 0 ? n : par + " ^ " + n;
-        }
-        const std::string idx = all_pow2 ? "lshl_or((" + par + ") ^ 1u, " + S_(__builtin_ctz(op.half_len)) + ", " + label + ")"
-                                         : "(" + label + " + ((" + par + ") ? 0u : " + S_(op.half_len) + "u))";
-        const std::string t = "t" + S_((long long)j);
-        o << ind << "    const uint32_t " << t << " = tc[" << op.tab_off << "u + " << idx << "];\n";
-        name[(size_t)op.dst] = t;
-        if (op.out_idx >= 0) o << ind << "    out[" << op.out_idx << "] = lshl_or(" << t << ", fs, out[" << op.out_idx << "]);\n";
-    }
+    if (!emit_chk_ops(o, prog, deg, ind + "    ", "tc", "fs", "par_w", "", err)) return false;
     o << ind << "}\n";
     return true;
+}
+
+// Min-sum of a check wider than 16 edges: two sweeps over its messages in LDS (re-read instead of held in registers).  `rd1` /
+// `rd2` name the message of edge k in the first / second sweep, `decl2` (may be empty) is declared first in the second.
+inline void emit_wide_minsum(std::ostringstream &o, int deg, const std::string &ind, const char *pragma, const std::string &rd1, const std::string &decl2,
+                             const std::string &rd2) {
+    o << ind << "uint32_t max1 = 0u, max2 = 0u, spp = 0u;      // the two LARGEST complemented magnitudes = the two smallest magnitudes\n" << pragma << "\n"
+      << ind << "for (int k = 0; k < " << deg << "; k++) {\n"
+      << ind << "    const uint32_t xh = " << rd1 << ";\n" << ind << "    const uint32_t pos = xh & SB, mc = (xh ^ (pos - (pos >> sbit))) & LOW;\n"
+      << ind << "    spp ^= xh;\n" << ind << "    const uint32_t g1 = xad(max1, LOW, mc) & SB, k1 = g1 - (g1 >> sbit);      // mc > max1\n"
+      << ind << "    const uint32_t hi = bfi(k1, mc, max1), lo = xor3(mc, max1, hi);\n"
+      << ind << "    const uint32_t g2 = xad(max2, LOW, lo) & SB, k2 = g2 - (g2 >> sbit);\n"
+      << ind << "    max2 = bfi(k2, lo, max2);\n" << ind << "    max1 = hi;\n" << ind << "}\n"
+      << ind << "const uint32_t tn = (spp ^ " << ((deg & 1) ? "SB" : "0u") << ") & SB;\n"
+      << ind << "if (chk) flag(s, (tn >> sbit) & a);\n"
+      << pragma << "\n" << ind << "for (int k = 0; k < " << deg << "; k++) {\n";
+    if (!decl2.empty()) o << ind << "    " << decl2 << "\n";
+    o << ind << "    const uint32_t xh = " << rd2 << ";\n" << ind << "    const uint32_t pos = xh & SB, mc = (xh ^ (pos - (pos >> sbit))) & LOW;\n"
+      << ind << "    const uint32_t eq = ~(((mc ^ max1) | SB) - ONE) & SB, ke = eq - (eq >> sbit);\n"
+      << ind << "    const uint32_t sel = bfi(ke, max2, max1), po = (tn ^ xh) & SB, kp = po - (po >> sbit);\n"
+      << ind << "    " << rd2 << " = bfi(am, xor_or(sel, kp, po), xh);\n" << ind << "}\n";
 }
 
 inline void emit_int_array(std::ostringstream &o, const std::string &name, const std::vector<int> &v) {
@@ -224,9 +141,7 @@ inline bool jit_resident_source(const ResidentSpec &R, std::string &src, std::st
 
     std::ostringstream o;
     o << kCommonHeaderText << "\n" << kResidentHeaderText << "\nusing namespace lutldpc;\n"
-      << "struct ResidentArgs { const uint8_t *cha, *msg0; uint8_t *hard; uint8_t *state; int32_t *iters; const uint8_t *tables; const int32_t *idx;\n"
-      << "                      int32_t n_sets, max_iters, psc, pisc, B; const uint8_t *fm_cha, *fm_msg0; uint8_t *fm_bits; int32_t lim_cha, lim_msg; };\n"
-      << "extern \"C\" __global__ __launch_bounds__(" << NT << ") " << (R.waves_eu > 0 ? "__attribute__((amdgpu_waves_per_eu(" + S_(R.waves_eu) + ", 8))) " : "")
+      << "extern \"C\" __global__ __launch_bounds__(" << NT << ") " << (R.waves_eu > 0 ? "__attribute__((amdgpu_waves_per_eu(" + jit_num(R.waves_eu) + ", 8))) " : "")
       << "void lutldpc_jit_pass(ResidentArgs A)\n{\n"
       << "    constexpr int PACK = " << PACK << ", BITS = " << BITS << ", F = 4 * PACK, S = " << S << ", NT = " << NT << ", E = " << E << ", N = " << N << ", I = " << I << ";\n"
       << "    constexpr uint32_t ONE = PACK == 2 ? 0x11111111u : 0x01010101u;\n"
@@ -242,13 +157,12 @@ inline bool jit_resident_source(const ResidentSpec &R, std::string &src, std::st
       << "    (void)I; (void)N; (void)TC;\n";
     // ---- per-iteration / per-set constants
     {
-        std::vector<int> nz, dec_ok((size_t)n_sets_tree, 0);
+        std::vector<int> nz;
         for (int q : R.nq_msg) nz.push_back(q / 2);
         nz.push_back(R.nq_msg.back() / 2);
         emit_int_array(o, "kNz", nz);
         emit_int_array(o, "kSet", R.iter_set);
     }
-    const int tid_items_note = 0; (void)tid_items_note;
     // XCD-aware set order: workgroups are dealt round-robin to the 8 XCDs (one L2 each), and a workgroup reads / writes 4 * S bytes of
     // every label row -- a 64-byte sector of a row holds 16 sets.  Giving XCD k the contiguous sets [k * Q/8, (k+1) * Q/8) makes the
     // workgroups that share a sector neighbours in time on ONE L2 (measured before: 549 MB of fabric reads for 61 MB of labels).
@@ -307,7 +221,7 @@ inline bool jit_resident_source(const ResidentSpec &R, std::string &src, std::st
         int base = 0;
         for (size_t c : order) {
             const int cnt = S * R.vcls[c].n;
-            for (int r = base / NT; cnt > 0 && r <= (base + cnt - 1) / NT; r++) items.push_back({(int)c, r, base, "_" + S_((long long)c) + "_" + S_(r)});
+            for (int r = base / NT; cnt > 0 && r <= (base + cnt - 1) / NT; r++) items.push_back({(int)c, r, base, "_" + jit_num((long long)c) + "_" + jit_num(r)});
             base += cnt;
         }
     }
@@ -348,12 +262,12 @@ inline bool jit_resident_source(const ResidentSpec &R, std::string &src, std::st
     // first item of class c this thread handles: slots tid, tid + NT, ... at or beyond the class base
     auto cn_loop = [&](size_t c) {
         const int b = cbase[c];
-        return "for (int it = tid + ((" + S_(b) + " - tid + NT - 1) / NT) * NT - " + S_(b) + "; it < S * " + S_(R.ccls[c].n) + "; it += NT) {\n";
+        return "for (int it = tid + ((" + jit_num(b) + " - tid + NT - 1) / NT) * NT - " + jit_num(b) + "; it < S * " + jit_num(R.ccls[c].n) + "; it += NT) {\n";
     };
     if (R.cn_persistent && R.min_lut) {
         for (size_t c : corder) {
             const int cnt = S * R.ccls[c].n;
-            for (int r = cbase[c] / NT; cnt > 0 && r <= (cbase[c] + cnt - 1) / NT; r++) citems.push_back({c, r, "_" + S_((long long)c) + "_" + S_(r)});
+            for (int r = cbase[c] / NT; cnt > 0 && r <= (cbase[c] + cnt - 1) / NT; r++) citems.push_back({c, r, "_" + jit_num((long long)c) + "_" + jit_num(r)});
         }
         for (auto &ci : citems) {
             const ResidentClass &C = R.ccls[ci.c];
@@ -413,20 +327,9 @@ inline bool jit_resident_source(const ResidentSpec &R, std::string &src, std::st
                   << "                const uint32_t tn = res_minsum<" << C.deg << ", PACK>(x, r, sbit, SB, LOW);\n"
                   << "                if (chk) flag(s, (tn >> sbit) & a);\n"
                   << "#pragma unroll\n                for (int k = 0; k < " << C.deg << "; k++) M[ce" << ci.sfx << "[k]] = bfi(am, r[k], x[k]);\n";
-            } else {      // wide checks: two sweeps over LDS, the addresses stay in registers
-                o << "                uint32_t max1 = 0u, max2 = 0u, spp = 0u;      // the two LARGEST complemented magnitudes = the two smallest magnitudes\n#pragma unroll\n                for (int k = 0; k < " << C.deg << "; k++) {\n"
-                  << "                    const uint32_t xh = M[ce" << ci.sfx << "[k]];\n                    const uint32_t pos = xh & SB, mc = (xh ^ (pos - (pos >> sbit))) & LOW;\n"
-                  << "                    spp ^= xh;\n                    const uint32_t g1 = xad(max1, LOW, mc) & SB, k1 = g1 - (g1 >> sbit);      // mc > max1\n"
-                  << "                    const uint32_t hi = bfi(k1, mc, max1), lo = xor3(mc, max1, hi);\n"
-                  << "                    const uint32_t g2 = xad(max2, LOW, lo) & SB, k2 = g2 - (g2 >> sbit);\n"
-                  << "                    max2 = bfi(k2, lo, max2);\n                    max1 = hi;\n                }\n"
-                  << "                const uint32_t tn = (spp ^ " << ((C.deg & 1) ? "SB" : "0u") << ") & SB;\n"
-                  << "                if (chk) flag(s, (tn >> sbit) & a);\n"
-                  << "#pragma unroll\n                for (int k = 0; k < " << C.deg << "; k++) {\n"
-                  << "                    const uint32_t xh = M[ce" << ci.sfx << "[k]];\n                    const uint32_t pos = xh & SB, mc = (xh ^ (pos - (pos >> sbit))) & LOW;\n"
-                  << "                    const uint32_t eq = ~(((mc ^ max1) | SB) - ONE) & SB, ke = eq - (eq >> sbit);\n"
-                  << "                    const uint32_t sel = bfi(ke, max2, max1), po = (tn ^ xh) & SB, kp = po - (po >> sbit);\n"
-                  << "                    M[ce" << ci.sfx << "[k]] = bfi(am, xor_or(sel, kp, po), xh);\n                }\n";
+            } else {      // wide checks: the addresses stay in registers
+                const std::string m = "M[ce" + ci.sfx + "[k]]";
+                emit_wide_minsum(o, C.deg, "                ", "#pragma unroll", m, "", m);
             }
             o << "            }\n        }\n";
         }
@@ -446,20 +349,7 @@ inline bool jit_resident_source(const ResidentSpec &R, std::string &src, std::st
                   << "            if (chk) flag(s, (tn >> sbit) & a);\n"
                   << "#pragma unroll\n            for (int k = 0; k < " << C.deg << "; k++) Ms[e[k]] = bfi(am, r[k], x[k]);\n";
             } else {
-                // wide checks: two sweeps over the check's edges (the messages are re-read from LDS instead of held in registers)
-                o << "            uint32_t max1 = 0u, max2 = 0u, spp = 0u;      // the two LARGEST complemented magnitudes = the two smallest magnitudes\n#pragma unroll 4\n            for (int k = 0; k < " << C.deg << "; k++) {\n"
-                  << "                const uint32_t xh = Ms[ed[k * ES]];\n                const uint32_t pos = xh & SB, mc = (xh ^ (pos - (pos >> sbit))) & LOW;\n"
-                  << "                spp ^= xh;\n                const uint32_t g1 = xad(max1, LOW, mc) & SB, k1 = g1 - (g1 >> sbit);      // mc > max1\n"
-                  << "                const uint32_t hi = bfi(k1, mc, max1), lo = xor3(mc, max1, hi);\n"
-                  << "                const uint32_t g2 = xad(max2, LOW, lo) & SB, k2 = g2 - (g2 >> sbit);\n"
-                  << "                max2 = bfi(k2, lo, max2);\n                max1 = hi;\n            }\n"
-                  << "            const uint32_t tn = (spp ^ " << ((C.deg & 1) ? "SB" : "0u") << ") & SB;\n"
-                  << "            if (chk) flag(s, (tn >> sbit) & a);\n"
-                  << "#pragma unroll 4\n            for (int k = 0; k < " << C.deg << "; k++) {\n"
-                  << "                const int ek = ed[k * ES];\n                const uint32_t xh = Ms[ek];\n                const uint32_t pos = xh & SB, mc = (xh ^ (pos - (pos >> sbit))) & LOW;\n"
-                  << "                const uint32_t eq = ~(((mc ^ max1) | SB) - ONE) & SB, ke = eq - (eq >> sbit);\n"
-                  << "                const uint32_t sel = bfi(ke, max2, max1), po = (tn ^ xh) & SB, kp = po - (po >> sbit);\n"
-                  << "                Ms[ek] = bfi(am, xor_or(sel, kp, po), xh);\n            }\n";
+                emit_wide_minsum(o, C.deg, "            ", "#pragma unroll 4", "Ms[ed[k * ES]]", "const int ek = ed[k * ES];", "Ms[ek]");
             }
             o << "        }\n";
         }
@@ -479,7 +369,7 @@ inline bool jit_resident_source(const ResidentSpec &R, std::string &src, std::st
                 if (v == bodies.size()) bodies.push_back(b.str());
                 variant_of[s] = (int)v;
             }
-            emit_int_array(o, "kChkVar" + S_((long long)c), variant_of);
+            emit_int_array(o, "kChkVar" + jit_num((long long)c), variant_of);
             o << "        " << cn_loop(c)
               << "            const int s = it / " << C.n << ", j = it - s * " << C.n << ";\n"
               << "            const uint32_t a = L_act[s];\n            if (!a) continue;\n            const uint32_t am = res_mask<PACK>(a);\n"
@@ -519,7 +409,7 @@ inline bool jit_resident_source(const ResidentSpec &R, std::string &src, std::st
                 if (v == bodies[c].size()) bodies[c].push_back(b.str());
                 variant_of[c][s] = (int)v;
             }
-            emit_int_array(o, (kind == TT_VAR ? "kVarV" : "kDecV") + S_((long long)c), variant_of[c]);
+            emit_int_array(o, (kind == TT_VAR ? "kVarV" : "kDecV") + jit_num((long long)c), variant_of[c]);
         }
         for (auto &it : items) {
             const ResidentClass &C = R.vcls[(size_t)it.c];

@@ -99,4 +99,24 @@ __device__ __forceinline__ uint32_t res_mask(uint32_t one_bits) { return one_bit
 template <int PACK>
 __device__ __forceinline__ int res_frame_of_element(int n) { return PACK == 2 ? ((n & 1) * 4 + (n >> 1)) : n; }
 
+struct ResidentArgs {              // arguments of the generated kernel (by value: 112 bytes), filled in by launch_resident
+    // (the ONE declaration: the host includes this header for it, the generated source starts with this header's text)
+    const uint8_t *cha, *msg0;     // label rows [G][N][256 B]
+    uint8_t *hard;                 // decided-bit rows
+    uint8_t *state;                // per-frame state bytes
+    int32_t *iters;                // per-frame iteration codes
+    const uint8_t *tables;         // the decoder's table blob
+    const int32_t *idx;            // the decoder's dense index blob (build_fast_index)
+    int32_t n_sets;                // 64 * frame groups
+    int32_t max_iters, psc, pisc;
+    int32_t B;                     // frames of the batch (frame-major I/O: frames beyond it read as label 0)
+    // frame-major I/O (the C-ABI's own layout, [B][N] bytes): when fm_cha is set the kernel reads the labels and writes the decided
+    // bits there itself -- a thread's eight frames of a node are eight byte accesses, 64 lanes of consecutive nodes one 64-byte
+    // segment per frame -- and the three transposes around the decode disappear (9 % of a (6,32) N=2048 step)
+    const uint8_t *fm_cha, *fm_msg0;
+    uint8_t *fm_bits;
+    int32_t lim_cha, lim_msg;      // labels are clamped to the alphabets like the transposes do
+};
+static_assert(sizeof(ResidentArgs) <= 128, "kernel arguments stay small (DESIGN.md section 7.1)");
+
 }  // namespace lutldpc

@@ -123,7 +123,8 @@ class Decoder:
         return json.loads(lib.lutldpc_decoder_describe(self._h).decode())
 
     def jit_source(self, kind: int, tree_set: int, cls: int, compile: bool = False) -> str:
-        """HIP source generated for a variable (0) / decision (2) class; compile=True also runs hiprtc (no GPU needed)."""
+        """HIP source generated for a variable (0) / check-tree (1; 1 + 32: over full labels) / decision (2) class; compile=True also
+        runs hiprtc (no GPU needed)."""
         n = lib.lutldpc_selftest_jit_source(self._h, kind, tree_set, cls, None, 0, int(compile))
         if n < 0:
             check(int(n))

@@ -91,11 +91,15 @@ def test_jit_source_compiles_without_a_gpu(name):
 
 @pytest.mark.parametrize("name", ["c5_chklut", "reg36_n1000_q3_chklut"])
 def test_jit_check_tree_source_compiles(name):
-    """CHKTREE check update (min_lut = false): sign/magnitude look-ups, one statement per shared look-up."""
+    """CHKTREE check update (min_lut = false): sign/magnitude look-ups and full-label look-ups, one statement per shared look-up."""
     cd = oracle_codec(name)
     dec = product_decoder(cd, device=-1)
     src = dec.jit_source(1, 0, 0, compile=True)
     assert src.count("= tab[") == dec.program_stats(1, 0, 0)["ops"]
+    # the program the check kernels run by default: tables over the children's full labels (CHK + 32), with its own table size
+    full = dec.jit_source(1 + 32, 0, 0, compile=True)
+    assert full.count("= tab[") == dec.program_stats(1 + 32, 0, 0)["ops"]
+    assert full != src and "lutldpc_jit_pass" in full
     dec.close()
 
 

@@ -1,0 +1,67 @@
+#!/usr/bin/env python3
+"""Write every HIP source the two run-time generators (csrc/hip/jit.hpp, jit_resident.hpp) produce for the configurations of
+tests/helpers.py, so that two builds can be compared text by text (host only, no GPU; the oracle designs the LUTs).
+Usage: tools/dump_generated_sources.py OUTDIR [--compile]
+OUTDIR/<sha256>.hip holds one distinct text each, OUTDIR/index.txt one line `config kind set class hash` per source: kinds
+0 / 1 / 2 / 33 are the streaming pass kernels of Decoder.jit_source (variable, check tree, decision, full-label check tree),
+`resident` lines carry the frame groups G and SxNT in the set / class columns (hash `refused`: resident_pick declined).
+--compile runs hiprtc (gfx950, the options of jit_compile) on every distinct text and stores OUTDIR/<sha256>.co.
+The LUTLDPC_* knobs of the environment apply, LUTLDPC_LIB selects another build: call it once per setting to sweep them."""
+import ctypes as C
+import hashlib
+import sys
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path[:0] = [str(ROOT), str(ROOT / "tests")]
+
+import lut_ldpc_amd as L  # noqa: E402
+from helpers import CONFIGS, oracle_codec, product_decoder  # noqa: E402
+
+out = Path(sys.argv[1])
+out.mkdir(parents=True, exist_ok=True)
+texts, index = {}, []
+
+
+def record(key, src):
+    h = hashlib.sha256(src.encode()).hexdigest()
+    texts[h] = src
+    index.append(f"{key} {h}")
+
+
+for name in CONFIGS:
+    cd = oracle_codec(name)
+    dec = product_decoder(cd, device=-1)
+    for kind in (0, 1, 2, 33):
+        for s in range(cd.n_sets()):
+            try:
+                for cls in range(1 << 20):
+                    record(f"{name} {kind} {s} {cls}", dec.jit_source(kind, s, cls))
+            except L.LutLdpcError:      # past the last class, or no program of this kind in this set
+                pass
+    for G in (1, 2, 3, 8, 64):
+        try:
+            src, (S, NT, _) = dec.resident_source(G)
+            record(f"{name} resident {G} {S}x{NT}", src)
+        except L.LutLdpcError:
+            index.append(f"{name} resident {G} - refused")
+    dec.close()
+
+for h, src in texts.items():
+    (out / f"{h}.hip").write_text(src)
+(out / "index.txt").write_text("\n".join(index) + "\n")
+print(f"{len(index)} index entries, {len(texts)} distinct texts")
+
+if "--compile" in sys.argv[2:]:
+    rtc = C.CDLL("libhiprtc.so")        # (already loaded: liblut_ldpc_amd.so links it)
+    opts = (C.c_char_p * 3)(b"--offload-arch=gfx950", b"-O3", b"-std=c++17")
+    for h, src in texts.items():
+        prog, n = C.c_void_p(), C.c_size_t()
+        assert rtc.hiprtcCreateProgram(C.byref(prog), src.encode(), b"lutldpc_jit_pass.hip", 0, None, None) == 0
+        assert rtc.hiprtcCompileProgram(prog, 3, opts) == 0, f"hiprtc failed on {h}"
+        assert rtc.hiprtcGetCodeSize(prog, C.byref(n)) == 0
+        code = C.create_string_buffer(n.value)
+        assert rtc.hiprtcGetCode(prog, code) == 0
+        (out / f"{h}.co").write_bytes(code.raw)
+        rtc.hiprtcDestroyProgram(C.byref(prog))
+    print(f"compiled {len(texts)} texts")
