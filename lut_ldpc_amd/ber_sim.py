@@ -157,28 +157,18 @@ class BerSim:
         return buf.value.decode()
 
 
-def _placement_policy(params, world: int):
-    """The same rule as the C++ driver (ber_sim_driver.cpp, ber_sim_main): the placement search of the row buffers (0.1-0.4 s per
-    batch size for +2-6 % of the streaming kernels' rate) is left to runs in which a rank sees at least 64 full batches of an
-    SNR point; LUTLDPC_PLACE set by the user wins (the library reads it when the decoder is created)."""
-    import re
-    try:
-        txt = open(params).read()
-    except OSError:
-        return False
-    def key(name, default):
-        m = re.search(r"^[ \t]*" + name + r"[ \t]*=[ \t]*([-+0-9.eE]+)", txt, re.M)
-        try:
-            return float(m.group(1)) if m else default
-        except ValueError:
-            return default
-    if "LUTLDPC_PLACE" not in os.environ and key("Nframes", 1e2) / (max(world, 1) * max(1.0, key("batch_frames", 32768.0))) < 64.0:
+def _placement_policy(sim: BerSim, world: int):
+    """The same rule as the C++ driver (ber_sim_driver.cpp, placement_search_pays): the placement search of the row buffers
+    (0.1-0.4 s per batch size for +2-6 % of the streaming kernels' rate) is left to runs in which a rank sees at least 64 full
+    batches of an SNR point; LUTLDPC_PLACE set by the user wins.  The library reads the variable when the decoder is created,
+    which is at the first batch: `sim` exists, its decoder does not yet."""
+    if "LUTLDPC_PLACE" not in os.environ and sim.nframes / (max(world, 1) * max(1, sim.batch_frames)) < 64.0:
         os.environ["LUTLDPC_PLACE"] = "0"
         return True
     return False
 
 
-def _run(params, base_dir, seed=0, custom_name="", comm: Optional[Comm] = None, device=0, save=True, quiet=False, batch_override=None):
+def run(params, base_dir, seed=0, custom_name="", comm: Optional[Comm] = None, device=0, save=True, quiet=False, batch_override=None):
     """LDPC_BER_Sim::run (src/LDPC_BER_Sim.cpp:121-155) + save(), sharded over comm.
 
     batch_override(sim, snr_index, frame0, B) -> [B, 4] replaces the device batch (sampler + decode + counting); the CPU
@@ -186,6 +176,17 @@ def _run(params, base_dir, seed=0, custom_name="", comm: Optional[Comm] = None, 
     comm = comm or Comm()
     sim = BerSim(params, base_dir, seed, custom_name, -1 if batch_override else device)
     batch = (lambda i, f, b: batch_override(sim, i, f, b)) if batch_override else sim.batch
+    # (the variable stays set for the whole run and is removed afterwards: a caller's later decoders decide for themselves)
+    policy_set = _placement_policy(sim, comm.world)
+    try:
+        return _sweep(sim, batch, comm, save, quiet)
+    finally:
+        sim.close()
+        if policy_set:
+            os.environ.pop("LUTLDPC_PLACE", None)
+
+
+def _sweep(sim: BerSim, batch, comm: Comm, save: bool, quiet: bool):
     t0 = time.perf_counter()
     points = []
     stop_sweep = False
@@ -210,20 +211,7 @@ def _run(params, base_dir, seed=0, custom_name="", comm: Optional[Comm] = None, 
             path = sim.results_path()
         if not quiet:
             print(f"Done simulating. Runtime = {runtime:g} seconds", flush=True)
-    sim.close()
     return points, path
-
-
-def run(params, base_dir, seed=0, custom_name="", comm: Optional[Comm] = None, device=0, save=True, quiet=False, batch_override=None):
-    """`_run` under the placement policy of this run (the decoder is created at the first batch, so the variable stays set for the
-    whole run and is removed afterwards: a caller's later decoders decide for themselves)."""
-    comm = comm or Comm()
-    policy_set = _placement_policy(params, comm.world)
-    try:
-        return _run(params, base_dir, seed, custom_name, comm, device, save, quiet, batch_override)
-    finally:
-        if policy_set:
-            os.environ.pop("LUTLDPC_PLACE", None)
 
 
 def main(argv=None):

@@ -6,7 +6,6 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstring>
 #include <filesystem>
 #include <fstream>
 #include <iomanip>
@@ -95,32 +94,26 @@ ChannelCellTable make_channel_cells(double N0, const vec &qb_Cha, const vec &qb_
     return C;
 }
 
-namespace {
-inline void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-    c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+ChannelCellTable channel_cells_at(const LDPC_Code_LUT &C, double snr_db) {
+    const int mode = C.get_initial_message_mode() == LDPC_Code_LUT::QCHA ? 1 : 0;
+    return make_channel_cells(noise_n0(snr_db, C.get_rate()), C.get_qb_Cha(), C.get_qb_Msg(), mode, C.get_Nq_Cha_2_Nq_Msg_map());
 }
-}  // namespace
+
+void philox4x32_10(uint32_t (&c)[4], uint64_t seed) {
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    for (int r = 0; r < 10; r++, k0 += 0x9E3779B9u, k1 += 0xBB67AE85u) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
+        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+    }
+}
 
 void random_info_bits(uint64_t seed, uint32_t stream, uint64_t frame, int K, unsigned char *out) {
     for (int k0 = 0; k0 < K; k0 += 128) {
         uint32_t c[4] = {(uint32_t)frame, (uint32_t)(frame >> 32), (uint32_t)(k0 / 128), stream | 0x80000000u};
-        uint32_t ka = (uint32_t)seed, kb = (uint32_t)(seed >> 32);
-        for (int r = 0; r < 10; r++) { philox_round(c, ka, kb); ka += 0x9E3779B9u; kb += 0xBB67AE85u; }
+        philox4x32_10(c, seed);
         for (int k = k0; k < std::min(K, k0 + 128); k++) out[k] = (unsigned char)((c[(k - k0) / 32] >> ((k - k0) % 32)) & 1u);
     }
-}
-
-bool accumulate_in_order(const FrameStats *st, int n, int K, int64_t Nfers, SnrPointCounters &c) {
-    for (int i = 0; i < n; i++) {
-        c.frames++; c.databits += K;
-        c.frame_errors += st[i].frame_error ? 1 : 0;
-        c.data_bit_errors += st[i].bit_errors;
-        c.uncoded_bit_errors += st[i].uncoded_errors;
-        if (c.frame_errors > Nfers) return true;          // src/LDPC_BER_Sim.cpp:289
-    }
-    return false;
 }
 
 // ------------------------------------------------------------------ LDPC_BER_Sim
@@ -167,19 +160,84 @@ std::string LDPC_BER_Sim::gen_filename() const {
     return fn.str();
 }
 
-void LDPC_BER_Sim::run() {
+void LDPC_BER_Sim::run(const CounterExchange &ex) {
     if (!decoder_set) throw std::logic_error("LDPC_BER_Sim::run(): Decoder has not been set!");
     const auto t0 = std::chrono::steady_clock::now();
     size_t ss = 0;
     while (ss < SNRdB.size()) {
-        const bool exit_cond = sim_snr_point(SNRdB[ss], (int)ss);
+        const bool exit_cond = sim_snr_point(SNRdB[ss], (int)ss, ex);
         ss++;
         if (exit_cond) break;
     }
     for (; ss < SNRdB.size(); ss++) results.add_snr_point(SNRdB[ss], 0, 0, 0, 0, 0);     // :142-149
     const double runtime = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     results.save_runtime(runtime);
-    if (!quiet) std::cout << "Done simulating. Runtime = " << runtime << " seconds" << std::endl;
+    if (ex.rank == 0 && !quiet) std::cout << "Done simulating" << ex.layout() << ". Runtime = " << runtime << " seconds" << std::endl;
+}
+
+// :246-311.  c = {frames, data bits, frame errors, data bit errors, uncoded bit errors} of the point so far, identical on every
+// rank.  Per round two exchanges: all-gather of {frames, frame errors} of every rank's batch, which tells every rank where in rank
+// order the frame-error count first exceeds Nfers, and all-reduce of the rank's share of the five counters -- a batch before
+// the stopping frame whole, the batch that holds it up to and including that frame, later ones nothing.
+bool LDPC_BER_Sim::sim_snr_point(double snr, int snr_index, const CounterExchange &ex) {
+    const int N = codeword_length, K = dataword_length, R = ex.ranks, rank = ex.rank;
+    const int64_t total = (int64_t)Nframes;
+    const auto past_nfers = [this](int64_t frame_errors) { return frame_errors > Nfers; };      // the stop rule, src/LDPC_BER_Sim.cpp:289
+    int64_t c[5] = {0, 0, 0, 0, 0};
+    int64_t f0 = 0;
+    int batch = std::min(512, batch_frames);            // one full frame group of nibble rows (a 256-frame start ran half-empty groups)
+    std::vector<FrameStats> stats;
+    std::vector<int64_t> all((size_t)R * 2);
+    for (bool stop = false; !stop && f0 < total; f0 += (int64_t)R * batch, batch = std::min(batch * 4, batch_frames)) {
+        const int64_t lo = std::min(total, f0 + (int64_t)rank * batch);
+        const int B = (int)(std::min(total, lo + batch) - lo);
+        stats.assign((size_t)B, FrameStats{});
+        if (B > 0) sim_batch(snr, snr_index, lo, B, stats.data());
+        int64_t mine[2] = {B, 0};
+        for (const FrameStats &st : stats) mine[1] += st.frame_error ? 1 : 0;
+        ex.all_gather2(mine, all.data());
+        int64_t ferr = c[2], run = c[2];                // frame errors before this rank's batch / up to rank r's, in frame order
+        for (int r = 0; r < rank; r++) ferr += all[(size_t)r * 2 + 1];
+        int first_stop = R;                             // the first rank whose batch holds the stopping frame
+        for (int r = 0; r < R && first_stop == R; r++) if (past_nfers(run += all[(size_t)r * 2 + 1])) first_stop = r;
+        stop = first_stop < R;
+        int64_t share[5] = {0, 0, 0, 0, 0};
+        for (int i = 0; i < B && rank <= first_stop; i++) {
+            const FrameStats &st = stats[(size_t)i];
+            share[0]++; share[1] += K; share[2] += st.frame_error ? 1 : 0; share[3] += st.bit_errors; share[4] += st.uncoded_errors;
+            if (past_nfers(ferr += st.frame_error ? 1 : 0)) break;
+        }
+        ex.all_reduce5(share);
+        for (int k = 0; k < 5; k++) c[k] += share[k];
+    }
+    const double ber = c[1] ? (double)c[3] / (double)c[1] : 0.0;
+    const double uber = c[0] ? (double)c[4] / ((double)c[0] * N) : 0.0;
+    const double fer = c[0] ? (double)c[2] / (double)c[0] : 0.0;
+    if (rank == 0 && !quiet)
+        std::cout << "SNR = " << snr << "  Simulated " << c[0] << " frames and " << c[1] << " data bits. "
+                  << "Obtained " << c[3] << " data bit errors. " << " Data BER: " << ber << " Uncoded BER: " << uber
+                  << " FER: " << fer << std::endl << std::flush;
+    results.add_snr_point(snr, c[0], c[1], c[2], c[3], c[4]);
+    return ber < ber_min || fer < fer_min;       // :307
+}
+
+void LDPC_BER_Sim::load_parity_and_generator() {
+    const fs::path parity_path = fs::path(codes_path) / (parity_filename + ".alist");
+    if (!fs::exists(parity_path)) throw std::runtime_error("Parity file" + parity_path.string() + " does not exist!");
+    H.reset(new LDPC_Parity(parity_path.string()));
+    if (zero_codeword) return;
+    const fs::path gen_path = fs::path(codes_path) / (parity_filename + ".gen.it");
+    G.reset(new LDPC_Generator_Systematic());
+    if (fs::exists(gen_path)) G->load(gen_path.string());
+    if (!G->is_initialized()) {
+        G->construct(H.get());
+        if (save_permuted) {
+            H->save_alist(parity_path.string());
+            { it_file_writer f(gen_path.string()); f.write("Fileversion", 2); f.close(); }
+            G->save(gen_path.string());
+        }
+    }
+    encoder_set = true;
 }
 
 std::string LDPC_BER_Sim::results_file_path() const {
@@ -229,23 +287,7 @@ LDPC_BER_Sim_LUT::LDPC_BER_Sim_LUT(const std::string &params, const std::string 
 
 void LDPC_BER_Sim_LUT::load() {
     if (codec_filename.empty()) {     // design the codec, :436-521
-        const fs::path parity_path = fs::path(codes_path) / (parity_filename + ".alist");
-        if (!fs::exists(parity_path)) throw std::runtime_error("Parity file" + parity_path.string() + " does not exist!");
-        H.reset(new LDPC_Parity(parity_path.string()));
-        if (!zero_codeword) {
-            const fs::path gen_path = fs::path(codes_path) / (parity_filename + ".gen.it");
-            G.reset(new LDPC_Generator_Systematic());
-            if (fs::exists(gen_path)) G->load(gen_path.string());
-            if (!G->is_initialized()) {
-                G->construct(H.get());
-                if (save_permuted) {
-                    H->save_alist(parity_path.string());
-                    { it_file_writer f(gen_path.string()); f.write("Fileversion", 2); f.close(); }
-                    G->save(gen_path.string());
-                }
-            }
-            encoder_set = true;
-        }
+        load_parity_and_generator();
         C.reset(new LDPC_Code_LUT());
         C->set_device(device);
         C->set_code_with_rank(H.get(), G.get(), known_rank);
@@ -271,7 +313,7 @@ void LDPC_BER_Sim_LUT::load() {
         if (initial_message_mode == "from_continuous_input") C->set_initial_message_mode(LDPC_Code_LUT::CONT);
         else if (initial_message_mode == "from_quantized_channel_llrs") C->set_initial_message_mode(LDPC_Code_LUT::QCHA);
         else throw std::runtime_error("LDPC_BER_Sim_LUT::load(): Initial message mode undefined!");
-        if (rand_seed == save_codec) {
+        if (codec_writer && rand_seed == save_codec) {
             const fs::path sub = fs::path(results_path) / gen_filename();
             fs::create_directories(sub);
             C->save_code((sub / "lut_codec.it").string());
@@ -301,10 +343,8 @@ std::string LDPC_BER_Sim_LUT::gen_filename() const {
 }
 
 void LDPC_BER_Sim_LUT::sim_batch(double snr, int snr_index, int64_t frame0, int B, FrameStats *stats) {
-    const double N0 = std::pow(10.0, -snr / 10.0) / C->get_rate();      // :248
     const int N = codeword_length, K = dataword_length;
-    const int mode = C->get_initial_message_mode() == LDPC_Code_LUT::QCHA ? 1 : 0;
-    const ChannelCellTable cells = make_channel_cells(N0, C->get_qb_Cha(), C->get_qb_Msg(), mode, C->get_Nq_Cha_2_Nq_Msg_map());
+    const ChannelCellTable cells = channel_cells_at(*C, snr);
     const lutldpc_channel_cells view = cells.view();
     const uint64_t seed = (uint64_t)(int64_t)(rand_seed + rand_seed_offset);      // RNG_reset(rand_seed + rand_seed_offset), :129
     if (!zero_codeword && !encoder_set) throw std::runtime_error("Non zero codewords require the encoder to be set!");
@@ -313,17 +353,8 @@ void LDPC_BER_Sim_LUT::sim_batch(double snr, int snr_index, int64_t frame0, int 
     // device encoder's size keep the host encoder
     const bool device_codewords = !zero_codeword && decoder_output_verbosity <= 1 && C->has_device_generator();
     std::vector<unsigned char> codewords;
-    const uint8_t *cwp = nullptr;
-    if (!zero_codeword && !device_codewords) {
-        bvec info((size_t)K), cw;
-        codewords.resize((size_t)B * N);
-        for (int i = 0; i < B; i++) {
-            random_info_bits(seed, (uint32_t)snr_index, (uint64_t)(frame0 + i), K, info.data());
-            C->encode(info, cw);
-            std::memcpy(&codewords[(size_t)i * N], cw.data(), (size_t)N);
-        }
-        cwp = codewords.data();
-    }
+    if (!zero_codeword && !device_codewords) codewords = random_codewords(*C, seed, (uint32_t)snr_index, (uint64_t)frame0, B, N, K);
+    const uint8_t *cwp = codewords.empty() ? nullptr : codewords.data();
     if (decoder_output_verbosity > 1) {
         // output_verbosity 2 / 3: the message dumps of lut_decode (src/LDPC_Code_LUT.cpp:292-298,311-317,331-337) on top of the
         // stimuli.  A debug path: the labels of the batch come back to the host (same sampler, same frames), lut_decode_batch
@@ -358,32 +389,6 @@ void LDPC_BER_Sim_LUT::sim_batch(double snr, int snr_index, int64_t frame0, int 
     for (int i = 0; i < B && !cha_dump.empty(); i++) C->print_stimuli(&cha_dump[(size_t)i * N], &bits_dump[(size_t)i * N]);
 }
 
-bool LDPC_BER_Sim::sim_snr_point(double snr, int snr_index) {
-    const int N = codeword_length, K = dataword_length;
-    SnrPointCounters c;
-    const int64_t total = (int64_t)Nframes;
-    int64_t f = 0;
-    int batch = std::min(512, batch_frames);            // one full frame group of nibble rows (a 256-frame start ran half-empty groups)
-    std::vector<FrameStats> stats;
-    while (f < total) {
-        const int B = (int)std::min<int64_t>(batch, total - f);
-        stats.assign((size_t)B, FrameStats{});
-        sim_batch(snr, snr_index, f, B, stats.data());
-        f += B;
-        if (accumulate_in_order(stats.data(), B, K, Nfers, c)) break;
-        batch = std::min(batch * 4, batch_frames);
-    }
-    const double ber = c.databits ? (double)c.data_bit_errors / (double)c.databits : 0.0;
-    const double uber = c.frames ? (double)c.uncoded_bit_errors / ((double)c.frames * N) : 0.0;
-    const double fer = c.frames ? (double)c.frame_errors / (double)c.frames : 0.0;
-    if (!quiet)
-        std::cout << "SNR = " << snr << "  Simulated " << c.frames << " frames and " << c.databits << " data bits. "
-                  << "Obtained " << c.data_bit_errors << " data bit errors. " << " Data BER: " << ber << " Uncoded BER: " << uber
-                  << " FER: " << fer << std::endl << std::flush;
-    results.add_snr_point(snr, c.frames, c.databits, c.frame_errors, c.data_bit_errors, c.uncoded_bit_errors);
-    return ber < ber_min || fer < fer_min;       // :307
-}
-
 // ------------------------------------------------------------------ LDPC_BER_Sim_BP
 void awgn_llr_frames(uint64_t seed, uint32_t stream, uint64_t frame0, int B, int N, double N0, const unsigned char *codewords, double *llr, int32_t *uncoded) {
     const double sigma = std::sqrt(N0 / 2), two_pi = 6.283185307179586476925286766559;
@@ -393,8 +398,7 @@ void awgn_llr_frames(uint64_t seed, uint32_t stream, uint64_t frame0, int B, int
         for (int p = 0; p < (N + 1) / 2; p++) {
             // one Philox block per bit pair: two 53-bit uniforms -> one Box-Muller pair
             uint32_t c[4] = {(uint32_t)frame, (uint32_t)(frame >> 32), (uint32_t)p, stream | 0x40000000u};
-            uint32_t ka = (uint32_t)seed, kb = (uint32_t)(seed >> 32);
-            for (int r = 0; r < 10; r++) { philox_round(c, ka, kb); ka += 0x9E3779B9u; kb += 0xBB67AE85u; }
+            philox4x32_10(c, seed);
             const double u1 = ((double)((((uint64_t)c[0] << 32) | c[1]) >> 11) + 1.0) * (1.0 / 9007199254740992.0);    // (0, 1]
             const double u2 = (double)((((uint64_t)c[2] << 32) | c[3]) >> 11) * (1.0 / 9007199254740992.0);            // [0, 1)
             const double rad = std::sqrt(-2.0 * std::log(u1));
@@ -427,23 +431,7 @@ LDPC_BER_Sim_BP::~LDPC_BER_Sim_BP() { if (dec) lutldpc_bp_destroy(dec); }
 void LDPC_BER_Sim_BP::load() {
     if (!codec_filename.empty())
         throw std::runtime_error("LDPC_BER_Sim::load(): loading an IT++ bp_codec.it file is not supported (the IT++ fork's file layout is absent); give LDPC.parity_filename");
-    const fs::path parity_path = fs::path(codes_path) / (parity_filename + ".alist");
-    if (!fs::exists(parity_path)) throw std::runtime_error("Parity file" + parity_path.string() + " does not exist!");
-    H.reset(new LDPC_Parity(parity_path.string()));
-    if (!zero_codeword) {
-        const fs::path gen_path = fs::path(codes_path) / (parity_filename + ".gen.it");
-        G.reset(new LDPC_Generator_Systematic());
-        if (fs::exists(gen_path)) G->load(gen_path.string());
-        if (!G->is_initialized()) {
-            G->construct(H.get());
-            if (save_permuted) {
-                H->save_alist(parity_path.string());
-                { it_file_writer f(gen_path.string()); f.write("Fileversion", 2); f.close(); }
-                G->save(gen_path.string());
-            }
-        }
-        encoder_set = true;
-    }
+    load_parity_and_generator();
     // the decoder sees the (possibly column-permuted) matrix through the same index arrays as the LUT decoder
     LDPC_Code_LUT graph;
     graph.set_device(-1);
@@ -461,19 +449,11 @@ void LDPC_BER_Sim_BP::load() {
 
 void LDPC_BER_Sim_BP::sim_batch(double snr, int snr_index, int64_t frame0, int B, FrameStats *stats) {
     const int N = codeword_length, K = dataword_length;
-    const double N0 = std::pow(10.0, -snr / 10.0) / code_rate;      // :248
+    const double N0 = noise_n0(snr, code_rate);
     const uint64_t seed = (uint64_t)(int64_t)(rand_seed + rand_seed_offset);
     if (!zero_codeword && !encoder_set) throw std::runtime_error("Non zero codewords require the encoder to be set!");
     std::vector<unsigned char> codewords;
-    if (!zero_codeword) {
-        bvec info((size_t)K), cw;
-        codewords.resize((size_t)B * N);
-        for (int i = 0; i < B; i++) {
-            random_info_bits(seed, (uint32_t)snr_index, (uint64_t)(frame0 + i), K, info.data());
-            G->encode(info, cw);
-            std::memcpy(&codewords[(size_t)i * N], cw.data(), (size_t)N);
-        }
-    }
+    if (!zero_codeword) codewords = random_codewords(*G, seed, (uint32_t)snr_index, (uint64_t)frame0, B, N, K);
     std::vector<double> llr((size_t)B * N);
     std::vector<int32_t> unc((size_t)B), iters((size_t)B);
     std::vector<uint8_t> bits((size_t)B * N);
@@ -497,6 +477,35 @@ void LDPC_BER_Sim_BP::sim_batch(double snr, int snr_index, int64_t frame0, int B
 }
 
 // ------------------------------------------------------------------ ber_sim main
+std::unique_ptr<LDPC_BER_Sim> make_ber_sim(const std::string &params_path, const std::string &base_dir, int seed, const std::string &custom_name, int device) {
+    const Ini ini(params_path);
+    const std::string codec_type = ini.get("Sim.codec_type", "none");
+    std::unique_ptr<LDPC_BER_Sim> sim;
+    if (ini.has_section("LUT") || codec_type == "LUT") sim.reset(new LDPC_BER_Sim_LUT(params_path, base_dir));
+    else if (ini.has_section("BP") || codec_type == "BP") sim.reset(new LDPC_BER_Sim_BP(params_path, base_dir));
+    else throw std::runtime_error("You must specify the type of decoder in the params file ([LUT] or [BP] section, or Sim.codec_type)");
+    sim->rand_seed = seed;
+    sim->device = device;
+    sim->append_custom_name(custom_name);
+    return sim;
+}
+
+namespace {
+// The placement search of the row buffers (decoder_batch.hip: place_rows, 0.1-0.4 s per batch size for +2-6 % of the streaming
+// kernels' rate) pays for itself after some eight seconds of decoding at that size: a rank that sees fewer than 64 full batches
+// of its largest SNR point runs without (config 4 on eight GPUs: four batches per rank).  The same rule: lut_ldpc_amd/ber_sim.py.
+bool placement_search_pays(double Nframes, int ranks, int batch_frames) { return Nframes / ((double)ranks * std::max(1, batch_frames)) >= 64.0; }
+
+// LUTLDPC_PLACE=0 for the lifetime of the guard (decoders read the variable when they are created, at the first batch of a run);
+// a value set by the user wins and is left alone
+struct PlacementSearchOff {
+    const bool mine;
+    explicit PlacementSearchOff(bool off) : mine(off && !std::getenv("LUTLDPC_PLACE") && setenv("LUTLDPC_PLACE", "0", 0) == 0) {}
+    ~PlacementSearchOff() { if (mine) unsetenv("LUTLDPC_PLACE"); }
+    PlacementSearchOff(const PlacementSearchOff &) = delete;
+};
+}  // namespace
+
 int ber_sim_main(int argc, char **argv) {
     int seed = 0, device = 0, lanes = 0;
     std::vector<int> devices;
@@ -559,9 +568,9 @@ int ber_sim_main(int argc, char **argv) {
     try {
         std::string params_path = fs::path(params).is_relative() ? (fs::path(base_dir) / params).string() : params;
         if (!fs::exists(params_path)) throw std::runtime_error("Parameter file" + params_path + " does not exist!");
-        Ini ini(params_path);
-        const std::string codec_type = ini.get("Sim.codec_type", "none");
         if (devices.empty()) devices.push_back(device);
+        const std::unique_ptr<LDPC_BER_Sim> sim = make_ber_sim(params_path, base_dir, seed, custom_name, device);
+        const auto *lut = dynamic_cast<const LDPC_BER_Sim_LUT *>(sim.get());
         if (const char *e = std::getenv("LUTLDPC_LANES")) lanes = std::atoi(e);
         if (lanes == 0) {
             // auto: two lanes hide the sampler, the transfers and the host prefix of one batch behind the decode of the other -- worth
@@ -569,33 +578,17 @@ int ber_sim_main(int argc, char **argv) {
             // leaves nothing to overlap with, and the second lane's set-up (its own decoder, generated kernels, placement search)
             // costs a 1e6-frame point 5 % (profiles/r03_config4_one_gpu_ber_sim.txt: 4.11 s against 4.31 s)
             lanes = 2;
-            const std::string codes_dir = ini.get("Sim.codes_dir", "codes"), parity = ini.get("LDPC.parity_filename", "");
-            std::ifstream al(fs::path(join(base_dir, codes_dir)) / (parity + ".alist"));
+            std::ifstream al(fs::path(join(base_dir, sim->codes_dir)) / (sim->parity_filename + ".alist"));
             long long n_var = 0;
-            if (al && (al >> n_var) && n_var > 0 && n_var * (long long)ini.get("Sim.batch_frames", 32768) >= (1ll << 30)) lanes = 1;
+            if (al && (al >> n_var) && n_var > 0 && n_var * (long long)sim->batch_frames >= (1ll << 30)) lanes = 1;
         }
-        const bool is_bp = !(ini.has_section("LUT") || codec_type == "LUT");
-        if (is_bp && devices.size() == 1) lanes = 1;               // (the [BP] comparison decoder draws its noise on all host cores already)
+        if (!lut && devices.size() == 1) lanes = 1;                // (the [BP] comparison decoder draws its noise on all host cores already)
         // output_verbosity > 0 prints every frame's stimuli / message dumps to std::cout in frame order (src/LDPC_Code_LUT.cpp:228-238,
         // 292-337): that text is only meaningful from ONE thread
-        if (ini.get("LUT.output_verbosity", 0) > 0) { lanes = 1; if (devices.size() > 1) devices.resize(1); }
-        // The placement search of the row buffers (decoder_batch.hip: place_rows, 0.1-0.4 s per batch size for +2-6 % of the streaming
-        // kernels' rate) pays for itself after some eight seconds of decoding at that size: a rank that sees fewer than 64
-        // full batches of its largest SNR point runs without (config 4 on eight GPUs: four batches per rank).  LUTLDPC_PLACE
-        // set by the user wins; the variable is read when a decoder is created.
-        {
-            const double per_rank = ini.get("Sim.Nframes", 1e2) / ((double)devices.size() * (double)std::max(lanes, 1) * (double)std::max(1, ini.get("Sim.batch_frames", 32768)));
-            if (per_rank < 64.0) setenv("LUTLDPC_PLACE", "0", 0);
-        }
-        if (devices.size() > 1 || lanes > 1)
+        if (lut && lut->decoder_output_verbosity > 0) { lanes = 1; devices.resize(1); }
+        const PlacementSearchOff no_search(!placement_search_pays(sim->Nframes, (int)devices.size() * std::max(lanes, 1), sim->batch_frames));
+        if (devices.size() > 1 || lanes > 1)       // (every rank makes its own simulation object; this one only answered the questions above)
             return ber_sim_run_multi(params_path, base_dir, seed, custom_name, devices, lanes, exchange, false);
-        std::unique_ptr<LDPC_BER_Sim> sim;
-        if (ini.has_section("LUT") || codec_type == "LUT") sim.reset(new LDPC_BER_Sim_LUT(params_path, base_dir));
-        else if (ini.has_section("BP") || codec_type == "BP") sim.reset(new LDPC_BER_Sim_BP(params_path, base_dir));
-        else throw std::runtime_error("You must specify the type of decoder in the params file ([LUT] section or Sim.codec_type)");
-        sim->rand_seed = seed;
-        sim->device = device;
-        sim->append_custom_name(custom_name);
         sim->load();
         sim->run();
         sim->save();

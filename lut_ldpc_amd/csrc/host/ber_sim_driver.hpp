@@ -15,8 +15,9 @@
 #include "lut_ldpc_hip.h"
 #include "lut_ldpc_bp.h"
 
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
-#include <functional>
 #include <memory>
 #include <optional>
 #include <string>
@@ -48,28 +49,63 @@ struct ChannelCellTable {
 // LDPC_Code_LUT::initial_message_mode_t (QCHA derives the message label from the channel label)
 ChannelCellTable make_channel_cells(double N0, const vec &qb_Cha, const vec &qb_Msg, int initial_message_mode, const ivec &cha2msg_map);
 
+// N0 of an SNR point: Eb/N0 = SNRdB at unit bit energy (src/LDPC_BER_Sim.cpp:248)
+inline double noise_n0(double snr_db, double code_rate) { return std::pow(10.0, -snr_db / 10.0) / code_rate; }
+// the cell table of codec C at this SNR
+ChannelCellTable channel_cells_at(const LDPC_Code_LUT &C, double snr_db);
+
+// Philox4x32-10 block of (counter, seed): the host twin of the device generator (kernels_frontend.hpp)
+void philox4x32_10(uint32_t (&counter)[4], uint64_t seed);
 // Philox-addressed data bits of frame f (zero_codeword = false), shared with the tests
 void random_info_bits(uint64_t seed, uint32_t stream, uint64_t frame, int K, unsigned char *out);
+// the codewords of frames frame0 .. frame0+B-1 made on the host (random_info_bits + enc.encode): B rows of N bytes
+template <class Encoder>
+std::vector<unsigned char> random_codewords(Encoder &enc, uint64_t seed, uint32_t stream, uint64_t frame0, int B, int N, int K) {
+    std::vector<unsigned char> codewords((size_t)B * N);
+    bvec info((size_t)K), cw;
+    for (int i = 0; i < B; i++) {
+        random_info_bits(seed, stream, frame0 + (uint64_t)i, K, info.data());
+        enc.encode(info, cw);
+        std::copy_n(cw.data(), (size_t)N, &codewords[(size_t)i * N]);
+    }
+    return codewords;
+}
 
 // per-frame result of one simulated frame: {lut_decode code, frame error, data bit errors, uncoded errors}
 struct FrameStats { int32_t iters, frame_error, bit_errors, uncoded_errors; };
-struct SnrPointCounters { int64_t frames = 0, databits = 0, frame_errors = 0, data_bit_errors = 0, uncoded_bit_errors = 0; };
 
-// Apply the stop rule of sim_snr_point to frames given in order; returns true when the frame loop
-// must stop (frame errors > Nfers) after consuming a prefix of `stats`.
-bool accumulate_in_order(const FrameStats *stats, int n, int K, int64_t Nfers, SnrPointCounters &c);
+// The counter exchange of the frame loop: rank `rank` of `ranks` takes every ranks-th batch of an SNR point and meets the others
+// twice per round.  This class is the single-rank exchange (no threads, no barrier, no HIP call); ber_sim_multi.cpp overrides it
+// for the lanes and devices of one run -- a rank that cannot complete an exchange there throws, which is how "another rank
+// failed" reaches the frame loop.
+class CounterExchange {
+public:
+    explicit CounterExchange(int rank_ = 0, int ranks_ = 1) : rank(rank_), ranks(ranks_) {}
+    virtual ~CounterExchange() = default;
+    // every rank contributes mine[2]; afterwards all[ranks][2] holds every rank's pair, in rank order
+    virtual void all_gather2(const int64_t *mine, int64_t *all) const { all[0] = mine[0]; all[1] = mine[1]; }
+    // sum of every rank's v[5], returned in v on every rank
+    virtual void all_reduce5(int64_t *) const {}
+    // what the closing line of run() says between "Done simulating" and ". Runtime"
+    virtual std::string layout() const { return ""; }
+    const int rank, ranks;
+};
 
 class LDPC_BER_Sim {
 public:
     LDPC_BER_Sim(const std::string &params_file_path, const std::string &base_dir_path);   // src/LDPC_BER_Sim.cpp:42-102
     virtual ~LDPC_BER_Sim() = default;
     virtual void load() = 0;
-    virtual void run();                                          // :121-155
+    // every rank of `ex` runs the same sweep and takes the same decisions; rank 0 prints
+    virtual void run(const CounterExchange &ex = CounterExchange());   // :121-155
     virtual void save();                                         // :317-340
     std::string results_file_path() const;                       // <results_dir>/<gen_filename>/<gen_filename>_rseedNNNN.it
-    virtual bool sim_snr_point(double snr, int snr_index);       // :246-311 (batched through sim_batch)
+    virtual bool sim_snr_point(double snr, int snr_index) { return sim_snr_point(snr, snr_index, CounterExchange()); }   // :246-311
+    // the frame loop, batched through sim_batch and sharded over the ranks of `ex`: rank r takes the batch [f0 + r * batch, + batch)
+    // of every round, and the stop rule of :289 is applied in global frame order, so the counters are those of the frame-by-frame loop
+    bool sim_snr_point(double snr, int snr_index, const CounterExchange &ex);
     // frames frame0 .. frame0+B-1 of SNR point `snr_index` (any order, any sharding): the body of the
-    // frame loop, :262-286.  The stop rule is applied by the caller (accumulate_in_order).
+    // frame loop, :262-286.  The stop rule is applied by the caller (sim_snr_point).
     virtual void sim_batch(double snr, int snr_index, int64_t frame0, int B, FrameStats *stats) = 0;
     int get_codeword_length() const { return codeword_length; }
     int get_dataword_length() const { return dataword_length; }
@@ -91,12 +127,18 @@ public:
     int device = 0;
     int batch_frames = 32768;        // frames per device call (upper bound; INI key Sim.batch_frames)
     bool quiet = false;
+    bool codec_writer = true;        // load() writes lut_codec.it when rand_seed == save_codec (:512); false on all ranks of a run but one
 
 protected:
+    // H from <codes_dir>/<parity_filename>.alist and, for zero_codeword = false, G from <parity_filename>.gen.it or constructed
+    // from H (save_permuted: both written back), :436-470 and :159-190
+    void load_parity_and_generator();
     std::string params_file_path, base_dir, codes_path, results_path;
     int codeword_length = 0, dataword_length = 0;
     bool decoder_set = false, encoder_set = false;
     double code_rate = 0;
+    std::unique_ptr<LDPC_Parity> H;
+    std::unique_ptr<LDPC_Generator_Systematic> G;
 };
 
 class LDPC_BER_Sim_LUT : public LDPC_BER_Sim {
@@ -119,8 +161,6 @@ public:
 
 private:
     std::string trees_path;
-    std::unique_ptr<LDPC_Parity> H;
-    std::unique_ptr<LDPC_Generator_Systematic> G;
     std::unique_ptr<LDPC_Code_LUT> C;
 };
 
@@ -142,8 +182,6 @@ public:
     lutldpc_bp_decoder *decoder() { return dec; }
 
 private:
-    std::unique_ptr<LDPC_Parity> H;
-    std::unique_ptr<LDPC_Generator_Systematic> G;
     lutldpc_bp_decoder *dec = nullptr;
 };
 
@@ -152,6 +190,11 @@ private:
 // ("host": ranks may share a device) or whichever applies ("auto").  Writes the same result file as the single-device run.
 int ber_sim_run_multi(const std::string &params_path, const std::string &base_dir, int seed, const std::string &custom_name,
                       const std::vector<int> &devices, int lanes, const std::string &exchange_mode, bool quiet);
+
+// prog/ber_sim.cpp:128-142: the section present in the parameter file (or Sim.codec_type) picks the simulation class; the object
+// comes back with its seed, custom name and device set, ready for load()
+std::unique_ptr<LDPC_BER_Sim> make_ber_sim(const std::string &params_path, const std::string &base_dir, int seed = 0,
+                                           const std::string &custom_name = "", int device = 0);
 
 // ber_sim's main (prog/ber_sim.cpp:46-160): returns the process exit code
 int ber_sim_main(int argc, char **argv);

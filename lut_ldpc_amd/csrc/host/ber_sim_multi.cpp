@@ -2,7 +2,9 @@
 //
 // The reference runs one single-threaded process per seed and adds the result files up afterwards
 // (scripts/aggregate_results.m:73-84).  Here ONE run of a parameter file shards the frames of every SNR point over the devices:
-//   * one host thread, one LDPC_BER_Sim_LUT (its own codec replica, decoder handle and HIP stream) per *lane*; `lanes` lanes per
+//   * one host thread, one simulation object (its own codec replica, decoder handle and HIP stream) per *lane*, each running
+//     LDPC_BER_Sim::run -- the sweep and the frame loop of the single-device run -- with its rank's view of the exchange below;
+//     this file holds what is specific to several ranks: the barrier, RCCL, the exchange, the threads; `lanes` lanes per
 //     device (default 2: while lane A's decode occupies the device, lane B's sampler runs and lane A's counters of the batch
 //     before go back over PCIe and through the host prefix -- the overlap a double buffer would give, without sharing buffers);
 //   * frames are Philox-addressed (kernels_frontend.hpp), so rank r of R simply takes the batch [f0 + r * batch, + batch) of every
@@ -10,19 +12,17 @@
 //   * per round two tiny exchanges: all-gather of {frames, frame errors} per rank (2 x int64) and all-reduce of the rank's
 //     contribution to the five counters of src/LDPC_BER_Sim.hpp:80-85 -- the batch before the stopping frame whole, the batch
 //     containing it truncated, later ones nothing -- so that the stop rule of src/LDPC_BER_Sim.cpp:289 (`> Nfers`) is applied
-//     in global frame order and the counters equal those of the frame-by-frame loop (same rule as lut_ldpc_amd/ber_sim.py:73-108);
+//     in global frame order and the counters equal those of the frame-by-frame loop (same rule as lut_ldpc_amd/ber_sim.py:73-108 and LDPC_BER_Sim::sim_snr_point);
 //   * the exchanges run over RCCL (ncclAllGather / ncclAllReduce on the devices' own communicators, ncclCommInitAll; xGMI between
 //     the GPUs of a node) with the lanes of a device folded on the host first; `host` exchange (threads + barrier only) is the
 //     rehearsal mode for ranks that share a device, which RCCL refuses.
 // librccl is loaded with dlopen: the library itself does not depend on it.
 #include "ber_sim_driver.hpp"
-#include "ini.hpp"
 
 #include <hip/hip_runtime_api.h>
 #include <dlfcn.h>
 
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <cstring>
 #include <iostream>
@@ -179,61 +179,22 @@ struct Exchange {
     }
 };
 
-// counters of the frames of st[0..n) (in order) up to and including the one that makes the running frame-error count exceed
-// nfers (lut_ldpc_amd/ber_sim.py: _prefix_until_stop)
-void prefix_until_stop(const FrameStats *st, int n, int K, int64_t nfers, int64_t ferr_before, int64_t out[5]) {
-    int64_t run = ferr_before;
-    int m = n;
-    for (int i = 0; i < n; i++) { run += st[i].frame_error ? 1 : 0; if (run > nfers) { m = i + 1; break; } }
-    out[0] = m; out[1] = (int64_t)m * K; out[2] = out[3] = out[4] = 0;
-    for (int i = 0; i < m; i++) { out[2] += st[i].frame_error ? 1 : 0; out[3] += st[i].bit_errors; out[4] += st[i].uncoded_errors; }
-}
+// rank `rank` of the run's exchange, as the frame loop sees it
+struct RankExchange : CounterExchange {
+    RankExchange(Exchange &ex_, int rank_) : CounterExchange(rank_, ex_.R), ex(ex_) {}
+    void all_gather2(const int64_t *mine, int64_t *all) const override { ex.all_gather2(rank, mine, all); }
+    void all_reduce5(int64_t *v) const override { ex.all_reduce5(rank, v); }
+    std::string layout() const override {
+        return " on " + std::to_string(ex.n_dev) + " device(s) x " + std::to_string(ex.lanes) + " lane(s), counters over " + (ex.use_rccl ? "RCCL" : "the host");
+    }
+    Exchange &ex;
+};
 
 }  // namespace
-
-// The frame loop of sim_snr_point (src/LDPC_BER_Sim.cpp:260-291) of one rank among ex.R; returns the counters of the point
-// (identical on every rank).
-static SnrPointCounters sim_snr_point_sharded(LDPC_BER_Sim &sim, Exchange &ex, int rank, double snr, int snr_index) {
-    const int K = sim.get_dataword_length(), R = ex.R;
-    const int64_t total_frames = (int64_t)sim.Nframes, nfers = sim.Nfers;
-    int64_t tot[5] = {0, 0, 0, 0, 0};
-    int64_t f0 = 0;
-    int batch = std::min(512, sim.batch_frames);            // one full frame group of nibble rows
-    std::vector<FrameStats> stats;
-    std::vector<int64_t> all((size_t)R * 2);
-    while (f0 < total_frames) {
-        const int64_t lo = std::min(total_frames, f0 + (int64_t)rank * batch), hi = std::min(total_frames, lo + batch);
-        const int B = (int)(hi - lo);
-        stats.assign((size_t)std::max(B, 0), FrameStats{});
-        if (B > 0) sim.sim_batch(snr, snr_index, lo, B, stats.data());
-        int64_t mine[2] = {B, 0};
-        for (int i = 0; i < B; i++) mine[1] += stats[(size_t)i].frame_error ? 1 : 0;
-        ex.all_gather2(rank, mine, all.data());
-        int64_t ferr_before = tot[2], run = tot[2];
-        for (int r = 0; r < rank; r++) ferr_before += all[(size_t)r * 2 + 1];
-        int first_stop = -1;
-        for (int r = 0; r < R; r++) { run += all[(size_t)r * 2 + 1]; if (run > nfers) { first_stop = r; break; } }
-        int64_t contrib[5] = {0, 0, 0, 0, 0};
-        if (first_stop < 0 || rank < first_stop) prefix_until_stop(stats.data(), B, K, INT64_MAX / 2, 0, contrib);
-        else if (rank == first_stop) prefix_until_stop(stats.data(), B, K, nfers, ferr_before, contrib);
-        ex.all_reduce5(rank, contrib);
-        for (int k = 0; k < 5; k++) tot[k] += contrib[k];
-        if (first_stop >= 0) break;
-        f0 += (int64_t)R * batch;
-        batch = std::min(batch * 4, sim.batch_frames);
-    }
-    SnrPointCounters c;
-    c.frames = tot[0]; c.databits = tot[1]; c.frame_errors = tot[2]; c.data_bit_errors = tot[3]; c.uncoded_bit_errors = tot[4];
-    return c;
-}
 
 int ber_sim_run_multi(const std::string &params_path, const std::string &base_dir, int seed, const std::string &custom_name,
                       const std::vector<int> &devices, int lanes, const std::string &exchange_mode, bool quiet) {
     if (devices.empty() || lanes < 1 || lanes > 8) throw std::runtime_error("ber_sim: need at least one device and 1..8 lanes");
-    Ini ini(params_path);
-    const bool is_lut = ini.has_section("LUT") || ini.get("Sim.codec_type", "none") == "LUT";
-    const bool is_bp = !is_lut && (ini.has_section("BP") || ini.get("Sim.codec_type", "none") == "BP");
-    if (!is_lut && !is_bp) throw std::runtime_error("You must specify the type of decoder in the params file ([LUT] section or Sim.codec_type)");
     Exchange ex;
     ex.init(devices, lanes, exchange_mode);
     const int R = ex.R;
@@ -243,35 +204,13 @@ int ber_sim_run_multi(const std::string &params_path, const std::string &base_di
     Barrier start(R);
     auto worker = [&](int rank) {
         try {
-            std::unique_ptr<LDPC_BER_Sim> sim;
-            if (is_lut) sim.reset(new LDPC_BER_Sim_LUT(params_path, base_dir)); else sim.reset(new LDPC_BER_Sim_BP(params_path, base_dir));
-            sim->rand_seed = seed;
-            sim->device = devices[(size_t)(rank % ex.n_dev)];
-            sim->append_custom_name(custom_name);
-            sim->quiet = true;
-            if (rank != 0) sim->save_codec = -1 - seed;             // one rank writes lut_codec.it
-            sim->load();
-            sims[(size_t)rank] = std::move(sim);
+            sims[(size_t)rank] = make_ber_sim(params_path, base_dir, seed, custom_name, devices[(size_t)(rank % ex.n_dev)]);
             LDPC_BER_Sim &S = *sims[(size_t)rank];
+            S.quiet = quiet;
+            S.codec_writer = rank == 0;                              // one rank writes lut_codec.it
+            S.load();
             start.wait();
-            const auto t0 = std::chrono::steady_clock::now();
-            size_t ss = 0;
-            const int N = S.get_codeword_length();
-            while (ss < S.SNRdB.size()) {                            // src/LDPC_BER_Sim.cpp:121-155 on every rank, same decisions everywhere
-                const SnrPointCounters c = sim_snr_point_sharded(S, ex, rank, S.SNRdB[ss], (int)ss);
-                const double ber = c.databits ? (double)c.data_bit_errors / (double)c.databits : 0.0;
-                const double uber = c.frames ? (double)c.uncoded_bit_errors / ((double)c.frames * N) : 0.0;
-                const double fer = c.frames ? (double)c.frame_errors / (double)c.frames : 0.0;
-                if (rank == 0 && !quiet)
-                    std::cout << "SNR = " << S.SNRdB[ss] << "  Simulated " << c.frames << " frames and " << c.databits << " data bits. "
-                              << "Obtained " << c.data_bit_errors << " data bit errors. " << " Data BER: " << ber << " Uncoded BER: " << uber
-                              << " FER: " << fer << std::endl << std::flush;
-                S.results.add_snr_point(S.SNRdB[ss], c.frames, c.databits, c.frame_errors, c.data_bit_errors, c.uncoded_bit_errors);
-                ss++;
-                if (ber < S.ber_min || fer < S.fer_min) break;       // :307
-            }
-            for (; ss < S.SNRdB.size(); ss++) S.results.add_snr_point(S.SNRdB[ss], 0, 0, 0, 0, 0);     // :142-149
-            S.results.save_runtime(std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+            S.run(RankExchange(ex, rank));                           // src/LDPC_BER_Sim.cpp:121-155 on every rank, same decisions everywhere
         } catch (const std::exception &e) {
             errors[(size_t)rank] = e.what();
             failed = true;
@@ -289,9 +228,6 @@ int ber_sim_run_multi(const std::string &params_path, const std::string &base_di
         for (int r = 0; r < R; r++) if (!errors[(size_t)r].empty() && errors[(size_t)r] != "another rank failed") msg += "rank " + std::to_string(r) + ": " + errors[(size_t)r] + "; ";
         throw std::runtime_error(msg.empty() ? "a rank failed" : msg);
     }
-    if (!quiet)
-        std::cout << "Done simulating on " << ex.n_dev << " device(s) x " << lanes << " lane(s), counters over " << (ex.use_rccl ? "RCCL" : "the host")
-                  << ". Runtime = " << sims[0]->results.runtime << " seconds" << std::endl;
     sims[0]->save();
     return 0;
 }

@@ -2,9 +2,7 @@
 #include "lut_ldpc_host.h"
 #include "ldpc_code_lut.hpp"
 #include "ber_sim_driver.hpp"
-#include "ini.hpp"
 
-#include <cmath>
 #include <vector>
 
 #include <cstring>
@@ -176,38 +174,16 @@ int lutldpc_codec_encode(lutldpc_codec *c, const uint8_t *info, uint8_t *codewor
     });
 }
 
-}  // extern "C"
-
-namespace {
-ChannelCellTable cells_for(lutldpc_codec *c, double snr_db) {
-    const double N0 = std::pow(10.0, -snr_db / 10.0) / c->C->get_rate();
-    const int mode = c->C->get_initial_message_mode() == LDPC_Code_LUT::QCHA ? 1 : 0;
-    return make_channel_cells(N0, c->C->get_qb_Cha(), c->C->get_qb_Msg(), mode, c->C->get_Nq_Cha_2_Nq_Msg_map());
-}
-void make_codewords(lutldpc_codec *c, uint64_t seed, uint32_t stream, uint64_t frame0, int B, std::vector<unsigned char> &cw) {
-    const int N = c->C->get_nvar(), K = c->C->get_ninfo();
-    cw.resize((size_t)B * N);
-    bvec info((size_t)K), one;
-    for (int i = 0; i < B; i++) {
-        random_info_bits(seed, stream, frame0 + (uint64_t)i, K, info.data());
-        c->C->encode(info, one);
-        std::memcpy(&cw[(size_t)i * N], one.data(), (size_t)N);
-    }
-}
-}  // namespace
-
-extern "C" {
-
 int lutldpc_codec_sim_batch(lutldpc_codec *c, double snr_db, uint64_t seed, uint32_t stream, uint64_t frame0, int B, int zero_codeword, int32_t *stats) {
     return guarded([&] {
         if (!c || !stats || B <= 0) throw std::invalid_argument("NULL / bad argument");
-        const ChannelCellTable cells = cells_for(c, snr_db);
+        const ChannelCellTable cells = channel_cells_at(*c->C, snr_db);
         const lutldpc_channel_cells view = cells.view();
         // random codewords: made on the device (generators beyond the device encoder's size: on the host, as before)
         if (!zero_codeword && c->C->has_device_generator())
             return lutldpc_decoder_sim_batch_random(c->C->device_handle(), &view, seed, stream, frame0, B, c->C->get_ninfo(), stats, nullptr, nullptr);
         std::vector<unsigned char> cw;
-        if (!zero_codeword) make_codewords(c, seed, stream, frame0, B, cw);
+        if (!zero_codeword) cw = random_codewords(*c->C, seed, stream, frame0, B, c->C->get_nvar(), c->C->get_ninfo());
         return lutldpc_decoder_sim_batch(c->C->device_handle(), &view, seed, stream, frame0, B, zero_codeword ? nullptr : cw.data(), c->C->get_ninfo(), stats, nullptr, nullptr);
     });
 }
@@ -224,10 +200,10 @@ int lutldpc_codec_sample_labels(lutldpc_codec *c, double snr_db, uint64_t seed, 
                                 uint8_t *cha, uint8_t *msg0, uint8_t *codewords) {
     return guarded([&] {
         if (!c || !cha || !msg0 || B <= 0) throw std::invalid_argument("NULL / bad argument");
-        const ChannelCellTable cells = cells_for(c, snr_db);
+        const ChannelCellTable cells = channel_cells_at(*c->C, snr_db);
         const lutldpc_channel_cells view = cells.view();
         std::vector<unsigned char> cw;
-        if (!zero_codeword) make_codewords(c, seed, stream, frame0, B, cw);
+        if (!zero_codeword) cw = random_codewords(*c->C, seed, stream, frame0, B, c->C->get_nvar(), c->C->get_ninfo());
         if (codewords) { if (zero_codeword) std::memset(codewords, 0, (size_t)B * c->C->get_nvar()); else std::memcpy(codewords, cw.data(), cw.size()); }
         return lutldpc_decoder_sample_labels(c->C->device_handle(), &view, seed, stream, frame0, B, zero_codeword ? nullptr : cw.data(), cha, msg0);
     });
@@ -237,7 +213,7 @@ int lutldpc_codec_channel_cells(lutldpc_codec *c, double snr_db, uint64_t *thr, 
     int n = 0;
     int rc = guarded([&] {
         if (!c || !thr || !cha || !msg || !neg || !cha_m || !msg_m) throw std::invalid_argument("NULL argument");
-        const ChannelCellTable t = cells_for(c, snr_db);
+        const ChannelCellTable t = channel_cells_at(*c->C, snr_db);
         n = (int)t.cha.size();
         if (n > 72) throw std::invalid_argument("more than 72 cells");
         std::memcpy(thr, t.thr.data(), sizeof(uint64_t) * t.thr.size());
@@ -248,24 +224,14 @@ int lutldpc_codec_channel_cells(lutldpc_codec *c, double snr_db, uint64_t *thr, 
     return rc == LUTLDPC_OK ? n : rc;
 }
 
-// prog/ber_sim.cpp:128-142: the section present in the parameter file (or Sim.codec_type) picks the simulation class
-static std::unique_ptr<LDPC_BER_Sim> make_sim(const char *params_path, const char *base_dir) {
-    Ini ini(params_path);
-    const std::string codec_type = ini.get("Sim.codec_type", "none");
-    if (ini.has_section("LUT") || codec_type == "LUT") return std::unique_ptr<LDPC_BER_Sim>(new LDPC_BER_Sim_LUT(params_path, base_dir));
-    if (ini.has_section("BP") || codec_type == "BP") return std::unique_ptr<LDPC_BER_Sim>(new LDPC_BER_Sim_BP(params_path, base_dir));
-    throw std::runtime_error("You must specify the type of decoder in the params file ([LUT] or [BP] section, or Sim.codec_type)");
-}
-
 int lutldpc_ber_sim_run(const char *params_path, const char *base_dir, int seed, const char *custom_name, int device, int save_results, int quiet,
                         double *snr, int64_t *counters, int cap) {
     int n = 0;
     int rc = guarded([&] {
         if (!params_path || !base_dir) throw std::invalid_argument("NULL argument");
-        std::unique_ptr<LDPC_BER_Sim> simp = make_sim(params_path, base_dir);
+        const std::unique_ptr<LDPC_BER_Sim> simp = make_ber_sim(params_path, base_dir, seed, custom_name ? custom_name : "", device);
         LDPC_BER_Sim &sim = *simp;
-        sim.rand_seed = seed; sim.device = device; sim.quiet = quiet != 0;
-        if (custom_name) sim.append_custom_name(custom_name);
+        sim.quiet = quiet != 0;
         sim.load();
         sim.run();
         if (save_results) sim.save();
@@ -313,9 +279,8 @@ int lutldpc_bersim_create(const char *params_path, const char *base_dir, int see
     return guarded([&] {
         if (!params_path || !base_dir || !out) throw std::invalid_argument("NULL argument");
         std::unique_ptr<lutldpc_bersim> s(new lutldpc_bersim);
-        s->sim = make_sim(params_path, base_dir);
-        s->sim->rand_seed = seed; s->sim->device = device; s->sim->quiet = true;
-        if (custom_name) s->sim->append_custom_name(custom_name);
+        s->sim = make_ber_sim(params_path, base_dir, seed, custom_name ? custom_name : "", device);
+        s->sim->quiet = true;
         s->sim->load();
         *out = s.release();
         return LUTLDPC_OK;

@@ -4,6 +4,7 @@
 #include "lut_ldpc_hip.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -306,7 +307,8 @@ bool LDPC_Code_LUT::load_design(const std::string &path, const std::string &key,
 }
 
 void LDPC_Code_LUT::store_design(const std::string &path, const std::string &key) const {
-    const std::string tmp = path + ".tmp" + std::to_string((long long)::getpid());
+    static std::atomic<unsigned> serial{0};                     // the lanes of one process store the same design at the same time
+    const std::string tmp = path + ".tmp" + std::to_string((long long)::getpid()) + "." + std::to_string(serial++);
     {
         std::error_code ec;                                     // a fresh checkout has no cache directory yet
         const auto dir = std::filesystem::path(path).parent_path();

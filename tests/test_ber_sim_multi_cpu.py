@@ -81,3 +81,37 @@ def test_rccl_refuses_ranks_that_share_a_device(tmp_path):
     argv = ["ber_sim", "-p", str(params), "-b", str(base), "-d", "0,0", "--exchange", "rccl"]
     r = subprocess.run([sys.executable, "-c", CHILD.format(root=str(ROOT), argv=argv)], env=env, cwd=str(ROOT), capture_output=True, text=True, timeout=600)
     assert r.returncode == 1 and "one device per rank" in r.stderr
+
+
+LEAK_CHILD = r"""
+import ctypes as C, os, sys
+sys.path.insert(0, {root!r})
+from lut_ldpc_amd._capi import lib
+libc = C.CDLL(None)
+libc.getenv.restype = C.c_char_p          # (the C environment itself: os.environ is Python's copy and does not see a setenv of the library)
+argv = {argv!r}
+arr = (C.c_char_p * len(argv))(*[a.encode() for a in argv])
+lib.lutldpc_ber_sim_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
+assert libc.getenv(b"LUTLDPC_PLACE") is None
+assert lib.lutldpc_ber_sim_main(len(argv), arr) == 0
+assert libc.getenv(b"LUTLDPC_PLACE") is None, libc.getenv(b"LUTLDPC_PLACE")
+os.environ["LUTLDPC_PLACE"] = "5"
+assert lib.lutldpc_ber_sim_main(len(argv), arr) == 0
+assert libc.getenv(b"LUTLDPC_PLACE") == b"5", libc.getenv(b"LUTLDPC_PLACE")
+print("environment ok")
+"""
+
+
+def test_ber_sim_main_leaves_the_placement_variable_as_it_found_it(tmp_path):
+    """ber_sim_main runs in the caller's process (lutldpc_ber_sim_main).  A short run switches the placement search off through
+    LUTLDPC_PLACE=0 (600 frames: under 64 full batches per rank); afterwards the variable is gone again, so that decoders the process
+    creates later decide for themselves, and a value the caller had set is still there."""
+    base, params = _basedir(tmp_path, 600)
+    sys.path.insert(0, str(HERE / "fakehip"))
+    import replay
+    subprocess.run(["make", "-s", "-j8", "-C", str(HERE / "fakehip")], check=True)
+    env = replay.sanitizer_env()
+    env.pop("LUTLDPC_PLACE", None)
+    argv = ["ber_sim", "-p", str(params), "-b", str(base), "-d", "0"]
+    r = subprocess.run([sys.executable, "-c", LEAK_CHILD.format(root=str(ROOT), argv=argv)], env=env, cwd=str(ROOT), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "environment ok" in r.stdout, (r.stdout[-2000:], r.stderr[-6000:])
