@@ -172,6 +172,43 @@ int lutldpc_decoder_sim_batch_random(lutldpc_decoder *d, const lutldpc_channel_c
 int lutldpc_decoder_sample_labels(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream,
                                   uint64_t frame0, int B, const uint8_t *codewords, uint8_t *cha, uint8_t *msg0);
 
+/*
+ * Message-label histograms per dump, counted on the device (lut_ldpc_amd/csrc/hip/kernels_stats.hpp): the distribution of the
+ * edge-message labels of a finite-length decode, to hold against the densities the LUT design assumed.
+ *
+ * Dumps are those of set_output_verbosity(level), in the order and number of lutldpc_decoder_decode_batch_trace:
+ * n_dumps = 1 + max_iters * (level - 1); level 2: the initial messages and the messages after every variable update, level 3:
+ * after every check update as well; the dump after the last iteration is kept.  The result is
+ *     hist[dump][group][x][label]   int64, label < n_labels, x = sent bit of the edge's variable node (0 for the all-zero codeword),
+ *                                   group = edge_group[e]; hist_cap = number of int64 the caller's array holds
+ * and both calls ADD into hist, so that a caller can loop over batches of any size.  n_labels must be at least the largest
+ * message alphabet.  mode decides which (frame, dump) pairs are counted:
+ *   0 (all)     every frame at every dump; the exit tests are off for the counted run, as in density evolution
+ *   1 (active)  the dumps the reference would have PRINTED for the frame under the decoder's exit conditions, from its lut_decode
+ *               return value c: c = 0 none, |c| = max_iters all, 0 < c < max_iters the first (level - 1) * c (it returns before
+ *               the dump of its last variable update)
+ * The return values come from a normal decode of the batch (any path), which also gives out_bits / out_iters; the messages are
+ * then counted in a second pass with the exit tests off (a frame evolves the same whether or not others leave) -- per-class
+ * streaming launches, no graph replay.  The exit conditions of the handle are the same before and after the call.
+ *
+ * set_edge_groups: edge_group[E] in VN-major edge order, values in [0, n_groups); NULL = one group (the default); n_groups 1..256.
+ *   ERR_ARG for a count or an id out of range.  Works on a host-only handle (the tables are kept for a later device).
+ * histogram_shape: out[4] = {n_dumps for `level`, n_groups, largest message alphabet, E}.
+ * histogram_batch: lutldpc_decoder_decode_batch with the counting; sent = host [B*nvar] sent bits or NULL (all-zero codeword);
+ *   out_bits / out_iters may be NULL.
+ * sim_batch_histogram: sampler (+ encoder) + counted decode for frames frame0 .. frame0+B-1 as lutldpc_decoder_sim_batch sends
+ *   them: codewords = host [B*nvar] or NULL; device_codewords != 0: the random codewords of lutldpc_decoder_sim_batch_random.
+ * ERR_ARG: level other than 2 / 3, mode other than 0 / 1, n_labels too small, hist_cap short, NULL hist; ERR_STATE: host-only
+ * handle, device_codewords without a generator.
+ */
+int lutldpc_decoder_set_edge_groups(lutldpc_decoder *d, const int32_t *edge_group, int n_groups);
+int lutldpc_decoder_histogram_shape(lutldpc_decoder *d, int level, int32_t *out4);
+int lutldpc_decoder_histogram_batch(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0, const uint8_t *sent, int B, int level, int mode,
+                                    int n_labels, uint8_t *out_bits, int32_t *out_iters, int64_t *hist, int64_t hist_cap, int32_t *n_dumps);
+int lutldpc_decoder_sim_batch_histogram(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0,
+                                        int B, const uint8_t *codewords, int device_codewords, int level, int mode, int n_labels,
+                                        int64_t *hist, int64_t hist_cap, int32_t *n_dumps);
+
 /* The decoder's HIP stream (hipStream_t as void*), for callers that enqueue their own work. */
 void *lutldpc_decoder_stream(lutldpc_decoder *d);
 
@@ -185,7 +222,8 @@ void *lutldpc_decoder_stream(lutldpc_decoder *d);
 #define LUTLDPC_K_FRONTEND  5   /* channel sampler + error counting                */
 #define LUTLDPC_K_FUSED_PASS 6  /* skewed pipeline: check pass of one half + variable pass of the other */
 #define LUTLDPC_K_RESIDENT  7   /* LDS-resident decode: all iterations of a batch in one launch */
-#define LUTLDPC_K_COUNT     8
+#define LUTLDPC_K_HISTOGRAM 8   /* message-label histogram of one dump (counted decode)              */
+#define LUTLDPC_K_COUNT     9
 
 /* When enabled every launch is bracketed by HIP events recorded on the decoder's stream. */
 int lutldpc_decoder_set_profiling(lutldpc_decoder *d, int enable);

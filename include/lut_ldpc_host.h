@@ -78,6 +78,11 @@ int lutldpc_codec_encode_random(lutldpc_codec *c, uint64_t seed, uint32_t stream
 /* the labels (and sent codewords, may be NULL) of those frames, for tests */
 int lutldpc_codec_sample_labels(lutldpc_codec *c, double snr_db, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
                                 int zero_codeword, uint8_t *cha, uint8_t *msg0, uint8_t *codewords);
+/* Message-label histograms (lutldpc_decoder_sim_batch_histogram) of the frames lutldpc_codec_sim_batch would simulate: same cells,
+ * same sent codewords (zero_codeword = 0: made on the device where the generator is there, else by the host encoder).  Adds into
+ * hist[n_dumps][n_groups][2][n_labels]; the edge grouping is that of lutldpc_codec_decoder(c). */
+int lutldpc_codec_message_histogram(lutldpc_codec *c, double snr_db, uint64_t seed, uint32_t stream, uint64_t frame0, int B, int zero_codeword,
+                                    int level, int mode, int n_labels, int64_t *hist, int64_t hist_cap, int32_t *n_dumps);
 /* the channel cell table for that SNR (see lut_ldpc_hip.h): returns n_cells; arrays need 72 entries */
 int lutldpc_codec_channel_cells(lutldpc_codec *c, double snr_db, uint64_t *thr, uint8_t *cha, uint8_t *msg, uint8_t *neg,
                                 uint8_t *cha_m, uint8_t *msg_m);
@@ -97,6 +102,14 @@ int lutldpc_bersim_destroy(lutldpc_bersim *s);
 int lutldpc_bersim_info(lutldpc_bersim *s, int64_t *info, double *limits, double *snr, int snr_cap);
 /* frames frame0..frame0+B-1 of SNR point snr_index -> stats[B*4] (see lutldpc_decoder_sim_batch) */
 int lutldpc_bersim_batch(lutldpc_bersim *s, int snr_index, int64_t frame0, int B, int32_t *stats);
+/* the same frames -> message-label histograms (lutldpc_decoder_sim_batch_histogram) with the simulation's own seed, stream
+ * (= snr_index) and codeword setting; [LUT] simulations only (ERR_STATE for [BP]) */
+int lutldpc_bersim_message_histogram(lutldpc_bersim *s, int snr_index, int64_t frame0, int B, int level, int mode, int n_labels,
+                                     int64_t *hist, int64_t hist_cap, int32_t *n_dumps);
+/* the decoder handle of a [LUT] simulation (edge groups, shapes; NULL + error otherwise) and its code: dims[4] = {nvar, nchk, E,
+ * max_iter}; dv[nvar], dc[nchk], cn_msg_idx[E], nq_msg[max_iter] are filled where not NULL */
+lutldpc_decoder *lutldpc_bersim_decoder(lutldpc_bersim *s);
+int lutldpc_bersim_code(lutldpc_bersim *s, int32_t *dims, int32_t *dv, int32_t *dc, int32_t *cn_msg_idx, int32_t *nq_msg);
 /* results.add_snr_point / save_runtime + save() */
 int lutldpc_bersim_add_point(lutldpc_bersim *s, double snr, const int64_t *counters5);
 int lutldpc_bersim_save(lutldpc_bersim *s, double runtime_s);

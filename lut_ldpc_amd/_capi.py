@@ -15,8 +15,8 @@ if os.environ.get("LUTLDPC_LIB"):          # A/B runs of two builds of the same 
     LIB_PATH = Path(os.environ["LUTLDPC_LIB"])
 
 OK, ERR_ARG, ERR_PARSE, ERR_UNSUPPORTED, ERR_HIP, ERR_STATE = 0, -1, -2, -3, -4, -5
-K_CN_PASS, K_VN_PASS, K_DECISION, K_SYNDROME, K_LAYOUT, K_FRONTEND, K_FUSED_PASS, K_RESIDENT, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8
-KIND_NAMES = ["cn_pass", "vn_pass", "decision", "syndrome", "layout", "frontend", "fused_pass", "resident"]
+K_CN_PASS, K_VN_PASS, K_DECISION, K_SYNDROME, K_LAYOUT, K_FRONTEND, K_FUSED_PASS, K_RESIDENT, K_HISTOGRAM, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
+KIND_NAMES = ["cn_pass", "vn_pass", "decision", "syndrome", "layout", "frontend", "fused_pass", "resident", "histogram"]
 
 
 class LutLdpcError(RuntimeError):
@@ -37,6 +37,7 @@ def _load() -> C.CDLL:
 lib = _load()
 
 _vp, _ip, _u8p, _dp, _cp = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_char_p
+_i64p = C.POINTER(C.c_int64)
 _SIGNATURES = {
     "lutldpc_last_error": (_cp, []),
     "lutldpc_version": (_cp, []),
@@ -62,6 +63,11 @@ _SIGNATURES = {
     "lutldpc_decoder_set_generator": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "lutldpc_decoder_encode_random": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p]),
     "lutldpc_decoder_sim_batch_random": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, _ip, _u8p, _u8p]),
+    "lutldpc_decoder_set_edge_groups": (C.c_int, [_vp, _ip, C.c_int]),
+    "lutldpc_decoder_histogram_shape": (C.c_int, [_vp, C.c_int, _ip]),
+    "lutldpc_decoder_histogram_batch": (C.c_int, [_vp, _u8p, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, _ip, _i64p, C.c_int64, _ip]),
+    "lutldpc_decoder_sim_batch_histogram": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                      _i64p, C.c_int64, _ip]),
 }
 for _name, (_res, _args) in _SIGNATURES.items():
     if hasattr(lib, _name):
@@ -128,6 +134,11 @@ _SIM_SIGNATURES = {
     "lutldpc_bersim_add_point": (C.c_int, [_vp, C.c_double, _i64p]),
     "lutldpc_bersim_save": (C.c_int, [_vp, C.c_double]),
     "lutldpc_bersim_results_path": (C.c_int64, [_vp, C.c_char_p, C.c_int64]),
+    "lutldpc_codec_message_histogram": (C.c_int, [_vp, C.c_double, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  _i64p, C.c_int64, _ip]),
+    "lutldpc_bersim_message_histogram": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _i64p, C.c_int64, _ip]),
+    "lutldpc_bersim_decoder": (_vp, [_vp]),
+    "lutldpc_bersim_code": (C.c_int, [_vp, _ip, _ip, _ip, _ip, _ip]),
 }
 for _name, (_res, _args) in _SIM_SIGNATURES.items():
     if hasattr(lib, _name):

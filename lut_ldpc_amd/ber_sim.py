@@ -143,6 +143,38 @@ class BerSim:
         self._check(self._lib.lutldpc_bersim_batch(self._h, int(snr_index), int(frame0), int(B), stats.ctypes.data_as(C.POINTER(C.c_int32))))
         return stats
 
+    def decoder(self):
+        """The HIP decoder of a [LUT] simulation (borrowed handle: edge groups, histogram shapes)."""
+        from .decoder import Decoder
+        h = self._lib.lutldpc_bersim_decoder(self._h)
+        if not h:
+            self._check(-5)
+        d = Decoder.__new__(Decoder)
+        d._h, d._owned, d._owner = C.c_void_p(h), False, self
+        d.nvar, d.max_iters, d.device = self.nvar, self.max_iter, 0
+        return d
+
+    def code(self):
+        """(dv, dc, cn_msg_idx, nq_msg) of a [LUT] simulation."""
+        dims = (C.c_int32 * 4)()
+        self._check(self._lib.lutldpc_bersim_code(self._h, dims, None, None, None, None))
+        dv, dc, cn, nq = (np.zeros(dims[k], np.int32) for k in (0, 1, 2, 3))
+        ip = C.POINTER(C.c_int32)
+        self._check(self._lib.lutldpc_bersim_code(self._h, dims, dv.ctypes.data_as(ip), dc.ctypes.data_as(ip), cn.ctypes.data_as(ip), nq.ctypes.data_as(ip)))
+        return dv, dc, cn, nq
+
+    def message_histogram(self, snr_index: int, frame0: int, B: int, level=3, mode="all", n_labels=None, hist=None) -> np.ndarray:
+        """Message-label histograms hist[dump, group, sent bit, label] (int64) of frames frame0..frame0+B-1 of an SNR point, with the
+        simulation's own seed, stream and codeword setting (as `batch`); added into `hist` when given."""
+        from .decoder import MODES
+        hist = self.decoder().new_histogram(level, n_labels) if hist is None else hist
+        got = C.c_int32()
+        self._check(self._lib.lutldpc_bersim_message_histogram(self._h, int(snr_index), int(frame0), int(B), int(level),
+                                                               MODES[mode] if isinstance(mode, str) else int(mode), hist.shape[3],
+                                                               hist.ctypes.data_as(C.POINTER(C.c_int64)), hist.size, C.byref(got)))
+        assert got.value == hist.shape[0]
+        return hist
+
     def add_point(self, snr: float, counters):
         c = np.ascontiguousarray(counters, np.int64)
         self._check(self._lib.lutldpc_bersim_add_point(self._h, float(snr), c.ctypes.data_as(C.POINTER(C.c_int64))))

@@ -153,6 +153,18 @@ class Codec:
         check(lib.lutldpc_codec_sim_batch(self._h, float(snr_db), int(seed), int(stream), int(frame0), int(B), int(zero_codeword), _p(stats, C.c_int32)))
         return stats
 
+    def message_histogram(self, snr_db, seed, stream, frame0, B, zero_codeword=True, level=3, mode="all", n_labels=None, hist=None) -> np.ndarray:
+        """Message-label histograms hist[dump, group, sent bit, label] (int64) of the frames sim_batch would simulate, counted on the
+        device (Decoder.message_histogram); added into `hist` when given.  The edge grouping is that of self.decoder()."""
+        from .decoder import MODES
+        hist = self.decoder().new_histogram(level, n_labels) if hist is None else hist
+        got = C.c_int32()
+        check(lib.lutldpc_codec_message_histogram(self._h, float(snr_db), int(seed), int(stream), int(frame0), int(B), int(zero_codeword), int(level),
+                                                  MODES[mode] if isinstance(mode, str) else int(mode), hist.shape[3], _p(hist, C.c_int64), hist.size,
+                                                  C.byref(got)))
+        assert got.value == hist.shape[0]
+        return hist
+
     def sample_labels(self, snr_db, seed, stream, frame0, B, zero_codeword=True):
         cha, msg = np.empty((B, self.nvar), np.uint8), np.empty((B, self.nvar), np.uint8)
         cw = np.empty((B, self.nvar), np.uint8)

@@ -12,7 +12,7 @@ hipError_t preload_frontend_kernels() {
     return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&encode_random_kernel));
 }
 
-static int fill_cells(const lutldpc_channel_cells *c, const lutldpc_decoder *d, ChannelCells &C) {
+int fill_cells(const lutldpc_channel_cells *c, const lutldpc_decoder *d, ChannelCells &C) {
     if (!c || !c->thr || !c->cha_label || !c->msg_label || !c->slicer_neg || !c->cha_label_mirror || !c->msg_label_mirror)
         return fail(LUTLDPC_ERR_ARG, "channel cells: NULL member");
     if (c->n_cells < 1 || c->n_cells > kMaxCells) return fail(LUTLDPC_ERR_ARG, "channel cells: n_cells outside [1,72]");
@@ -30,8 +30,8 @@ static int fill_cells(const lutldpc_channel_cells *c, const lutldpc_decoder *d, 
 
 // sampler -> d_cha_t / d_msg0_t (tile layout); stats zeroed and slicer errors accumulated.  sent_rows (device, d_sent): the
 // codewords as sent-bit rows, made by encode_tiles; otherwise codewords_host (frame-major, uploaded) or none (all-zero)
-static int sample_tiles(lutldpc_decoder *d, const ChannelCells &C, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *codewords_host,
-                 const uint8_t *sent_rows = nullptr) {
+int sample_tiles(lutldpc_decoder *d, const ChannelCells &C, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *codewords_host,
+                 const uint8_t *sent_rows) {
     int rc = ensure_batch(d, B);
     if (rc) return rc;
     const int Bpad = d->bpad(B), G = Bpad / d->tile(), N = d->nvar;
@@ -58,7 +58,7 @@ static int sample_tiles(lutldpc_decoder *d, const ChannelCells &C, uint64_t seed
 }
 
 // random codewords of frames frame0 .. frame0+B-1 -> d_sent (sent-bit rows of bpad(B) frames; pad frames zero)
-static int encode_tiles(lutldpc_decoder *d, uint64_t seed, uint32_t stream, uint64_t frame0, int B) {
+int encode_tiles(lutldpc_decoder *d, uint64_t seed, uint32_t stream, uint64_t frame0, int B) {
     if (!d->gen_set) return fail(LUTLDPC_ERR_STATE, "no generator set: random codewords on the device need lutldpc_decoder_set_generator first");
     const int Bpad = d->bpad(B), G = Bpad / d->tile(), N = d->nvar;
     const int RB = d->pack == 2 ? sent_row_bytes<2>() : sent_row_bytes<1>();

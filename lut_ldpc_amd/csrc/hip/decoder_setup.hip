@@ -405,6 +405,7 @@ static int preload_code_objects(int device) {
     HIP_TRY((preload_vn_fast<TT_VAR, 1>())); HIP_TRY((preload_vn_fast<TT_VAR, 2>())); HIP_TRY((preload_vn_fast<TT_DEC, 2>()));
     HIP_TRY((preload_cn_fast<2>()));
     HIP_TRY(preload_compact_kernels());
+    HIP_TRY(preload_stats_kernels());
     HIP_TRY(hipDeviceSynchronize());
     done.push_back(device);
     return LUTLDPC_OK;

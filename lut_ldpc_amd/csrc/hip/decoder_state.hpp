@@ -9,6 +9,7 @@
 //   decoder_skew.hip       skewed two-half pipeline through pass_fused_kernel, compaction                     (kernels_compact.hpp)
 //   decoder_resident.hip   LDS-resident decoder (jit_resident.hpp)
 //   decoder_frontend.hip   channel sampler, encoder, error counters and their C-ABI entries    (kernels_frontend.hpp, kernels_encode.hpp)
+//   decoder_stats.hip      message-label histograms per dump: edge groups, the counted decode, C-ABI   (kernels_stats.hpp)
 #pragma once
 #include "../../../include/lut_ldpc_hip.h"
 #include "kernels_common.hpp"
@@ -30,6 +31,7 @@
 #include <vector>
 
 namespace lutldpc { LUTLDPC_FAST_LAUNCHERS(extern) }     // instantiated in fast_*.hip / fused_b*.hip
+namespace lutldpc { struct ChannelCells; }               // kernels_frontend.hpp
 
 using namespace lutldpc;
 
@@ -211,9 +213,22 @@ struct lutldpc_decoder {
     // message dumps of output_verbosity >= 2 (src/LDPC_Code_LUT.cpp:292-298,311-317,331-337): a small-batch debug path -- per-class
     // streaming launches, the edge rows copied out after the edge initialisation, (level > 2) every check pass and every
     // variable pass.  host: [dump][B][E] bytes, dumps in the reference's print order.
-    struct Trace { int level = 0; uint8_t *host = nullptr; size_t cap = 0; int n = 0; int B = 0; };
+    // The sink of a dump is either that host copy, or (hist != nullptr) a histogram: the labels of the dump are counted on the device
+    // into hist[dump][group][sent bit][n_labels] 64-bit totals, nothing is copied (decoder_stats.hip: hist_dump) -- any batch size.
+    // sent: sent-bit rows or null (all-zero codeword); last_dump[f]: how many dumps of frame f are counted.
+    struct Trace {
+        int level = 0; uint8_t *host = nullptr; size_t cap = 0; int n = 0; int B = 0;
+        unsigned long long *hist = nullptr; const uint8_t *sent = nullptr; const int32_t *last_dump = nullptr; int n_labels = 0, n_dumps = 0;
+    };
     Trace trace;
     DevBuf<uint8_t> d_trace;
+    // edge grouping of the histograms (lutldpc_decoder_set_edge_groups): the edges sorted by group, where every group's run
+    // begins, and the runs cut into chunks {first, count, group} of hist_chunk_edges edges (decoder_stats.hip:
+    // upload_edge_groups; 0 = not cut / uploaded yet).  hist_edges empty = never set (one group)
+    int hist_groups = 1, hist_chunk_edges = 0;
+    std::vector<int32_t> hist_edges, hist_run, hist_chunks;
+    DevBuf<int32_t> d_hist_edges, d_hist_chunks, d_last_dump;
+    DevBuf<unsigned long long> d_hist;
     // LDS-resident decoder (jit_resident.hpp): codes whose edge messages fit the LDS of a compute unit are decoded by ONE generated
     // kernel per decode -- all iterations inside, no HBM traffic between the labels and the decided bits.
     // frame-major label / bit buffers of the current decode_device call, handed to the resident kernel (it reads and writes them
@@ -329,6 +344,7 @@ hipError_t preload_stream_kernels();
 // frames f0 .. f1-1 (both multiples of 256); default: the whole padded batch
 // `sel`: which of the two flag buffers the exit test reads and clears (always 0 outside the skewed pipeline)
 int launch_state(lutldpc_decoder *d, int B, int Bpad, int mode, int value, int f0 = 0, int f1 = -1, int sel = 0);
+int launch_transpose_in(lutldpc_decoder *d, const uint8_t *src, uint8_t *dst_rows, int B, int G, int limit);
 int launch_transpose_out(lutldpc_decoder *d, const uint8_t *src_rows, uint8_t *dst, int B, int G, int rows = 0);
 int launch_quantize_llr(lutldpc_decoder *d, size_t n, int n_qb_Cha, int n_qb_Msg, int mode);
 bool chain_active(const lutldpc_decoder *d, int set);
@@ -357,5 +373,14 @@ int launch_resident(lutldpc_decoder *d, int G, int B);
 
 // ---- decoder_frontend.hip (home of the kernels of kernels_frontend.hpp and kernels_encode.hpp)
 hipError_t preload_frontend_kernels();
+int fill_cells(const lutldpc_channel_cells *c, const lutldpc_decoder *d, ChannelCells &C);
+// sampler -> d_cha_t / d_msg0_t; the sent bits: sent_rows (device, sent-bit rows), else codewords_host (frame-major), else all-zero
+int sample_tiles(lutldpc_decoder *d, const ChannelCells &C, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *codewords_host,
+                 const uint8_t *sent_rows = nullptr);
+int encode_tiles(lutldpc_decoder *d, uint64_t seed, uint32_t stream, uint64_t frame0, int B);       // random codewords -> d_sent
+
+// ---- decoder_stats.hip (home of the kernels of kernels_stats.hpp)
+hipError_t preload_stats_kernels();
+int hist_dump(lutldpc_decoder *d);           // one dump of a counted decode: the message rows into d->trace.hist (decode_tiles_launch)
 
 #pragma GCC visibility pop

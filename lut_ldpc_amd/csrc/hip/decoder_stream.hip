@@ -53,7 +53,7 @@ static int launch_syndrome_of_labels(lutldpc_decoder *d, int G) {
 }
 
 // frame-major [B][N] <-> rows; the dword-vectorised kernels need N % 4 == 0 and a 4-byte aligned buffer
-static int launch_transpose_in(lutldpc_decoder *d, const uint8_t *src, uint8_t *dst_rows, int B, int G, int limit) {
+int launch_transpose_in(lutldpc_decoder *d, const uint8_t *src, uint8_t *dst_rows, int B, int G, int limit) {
     const int N = d->nvar;
     if (N % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 3u) == 0)
         PACK_DISPATCH(d, launch_k(transpose_in_vec_kernel<PK>, dim3((unsigned)((N + 127) / 128), (unsigned)G), dim3(256), 0, d->stream, src, dst_rows, B, N, limit));
@@ -233,6 +233,7 @@ int launch_late_hard(lutldpc_decoder *d, bool skewed, int g0, int G, const int32
 // one message dump of the trace: the E edge rows of all frames, frame-major, to the next slot of the host buffer (synchronous)
 static int trace_dump(lutldpc_decoder *d) {
     lutldpc_decoder::Trace &T = d->trace;
+    if (T.hist) return hist_dump(d);               // the sink is a histogram on the device (decoder_stats.hip): nothing is copied
     const size_t one = (size_t)T.B * (size_t)d->E;
     if ((size_t)(T.n + 1) * one > T.cap) return fail(LUTLDPC_ERR_ARG, "trace buffer too small");
     const int G = d->bpad(T.B) / d->tile();
@@ -317,6 +318,10 @@ static int decode_tiles_launch(lutldpc_decoder *d, int B) {
         }
         if (tracing && (rc = trace_dump(d))) return rc;                         // :331-337 (printed after the last iteration too)
     }
+    if (d->trace.hist) {                            // a counted decode ends with its last dump: bits and iteration codes are those of the decode before it
+        if (d->profiling && d->ev_live.size() > 8192) prof_fold(d);
+        return LUTLDPC_OK;
+    }
     {   // decided bits of the frames that left through the exit test, from their frozen messages (see late_hard_active)
         Timed t(d, LUTLDPC_K_LAYOUT);
         if ((rc = launch_late_hard(d, skewed, 0, G, nullptr))) return rc;
@@ -347,7 +352,7 @@ static int decode_tiles_launch(lutldpc_decoder *d, int B) {
 // are launch-bound, for them this is worth ~20 %.  Off while kernel events are being recorded.
 int decode_tiles(lutldpc_decoder *d, int B) {
     if (int rc = check_batch_buffers(d, d->bpad(B))) return rc;
-    if (resident_active(d)) {                     // generate / compile / load outside any stream capture
+    if (resident_active(d) && !d->trace.hist) {   // generate / compile / load outside any stream capture (a counted decode streams)
         lutldpc_decoder::ResidentPlan *pl = nullptr;
         if (int rc = resident_plan_for(d, d->bpad(B) / d->tile(), &pl)) return rc;
     }

@@ -389,6 +389,21 @@ void LDPC_BER_Sim_LUT::sim_batch(double snr, int snr_index, int64_t frame0, int 
     for (int i = 0; i < B && !cha_dump.empty(); i++) C->print_stimuli(&cha_dump[(size_t)i * N], &bits_dump[(size_t)i * N]);
 }
 
+// the frames of sim_batch -- same seed, same stream, same codewords -- with their edge messages counted instead of their errors
+int LDPC_BER_Sim_LUT::message_histogram(double snr, int snr_index, int64_t frame0, int B, int level, int mode, int n_labels, int64_t *hist, int64_t hist_cap,
+                                        int32_t *n_dumps) {
+    const ChannelCellTable cells = channel_cells_at(*C, snr);
+    const lutldpc_channel_cells view = cells.view();
+    const uint64_t seed = (uint64_t)(int64_t)(rand_seed + rand_seed_offset);
+    if (!zero_codeword && !encoder_set) throw std::runtime_error("Non zero codewords require the encoder to be set!");
+    lutldpc_decoder *d = C->device_handle();
+    const bool device_codewords = !zero_codeword && C->has_device_generator();
+    std::vector<unsigned char> codewords;
+    if (!zero_codeword && !device_codewords) codewords = random_codewords(*C, seed, (uint32_t)snr_index, (uint64_t)frame0, B, codeword_length, dataword_length);
+    return lutldpc_decoder_sim_batch_histogram(d, &view, seed, (uint32_t)snr_index, (uint64_t)frame0, B, codewords.empty() ? nullptr : codewords.data(),
+                                               device_codewords ? 1 : 0, level, mode, n_labels, hist, hist_cap, n_dumps);
+}
+
 // ------------------------------------------------------------------ LDPC_BER_Sim_BP
 void awgn_llr_frames(uint64_t seed, uint32_t stream, uint64_t frame0, int B, int N, double N0, const unsigned char *codewords, double *llr, int32_t *uncoded) {
     const double sigma = std::sqrt(N0 / 2), two_pi = 6.283185307179586476925286766559;

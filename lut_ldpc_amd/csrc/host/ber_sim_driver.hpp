@@ -107,6 +107,10 @@ public:
     // frames frame0 .. frame0+B-1 of SNR point `snr_index` (any order, any sharding): the body of the
     // frame loop, :262-286.  The stop rule is applied by the caller (sim_snr_point).
     virtual void sim_batch(double snr, int snr_index, int64_t frame0, int B, FrameStats *stats) = 0;
+    // message-label histograms of the same frames (lutldpc_decoder_sim_batch_histogram), added into hist; returns its code
+    virtual int message_histogram(double, int, int64_t, int, int, int, int, int64_t *, int64_t, int32_t *) {
+        throw std::logic_error("message histograms exist for [LUT] simulations only");
+    }
     int get_codeword_length() const { return codeword_length; }
     int get_dataword_length() const { return dataword_length; }
     virtual std::string gen_filename() const;                    // :104-115
@@ -146,6 +150,8 @@ public:
     LDPC_BER_Sim_LUT(const std::string &params_file_path, const std::string &base_dir_path);   // src/LDPC_BER_Sim.cpp:376-430
     void load() override;                                        // :434-550
     void sim_batch(double snr, int snr_index, int64_t frame0, int B, FrameStats *stats) override;
+    int message_histogram(double snr, int snr_index, int64_t frame0, int B, int level, int mode, int n_labels, int64_t *hist, int64_t hist_cap,
+                          int32_t *n_dumps) override;
     std::string gen_filename() const override;                   // :553-568
     LDPC_Code_LUT *codec() { return C.get(); }
 

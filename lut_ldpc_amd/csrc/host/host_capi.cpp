@@ -188,6 +188,22 @@ int lutldpc_codec_sim_batch(lutldpc_codec *c, double snr_db, uint64_t seed, uint
     });
 }
 
+int lutldpc_codec_message_histogram(lutldpc_codec *c, double snr_db, uint64_t seed, uint32_t stream, uint64_t frame0, int B, int zero_codeword,
+                                    int level, int mode, int n_labels, int64_t *hist, int64_t hist_cap, int32_t *n_dumps) {
+    return guarded([&] {
+        if (!c || !hist || B <= 0) throw std::invalid_argument("NULL / bad argument");
+        const ChannelCellTable cells = channel_cells_at(*c->C, snr_db);
+        const lutldpc_channel_cells view = cells.view();
+        lutldpc_decoder *d = c->C->device_handle();
+        // the sent codewords as lutldpc_codec_sim_batch chooses them: device encoder where the generator is there, else the host's
+        const bool on_device = !zero_codeword && c->C->has_device_generator();
+        std::vector<unsigned char> cw;
+        if (!zero_codeword && !on_device) cw = random_codewords(*c->C, seed, stream, frame0, B, c->C->get_nvar(), c->C->get_ninfo());
+        return lutldpc_decoder_sim_batch_histogram(d, &view, seed, stream, frame0, B, cw.empty() ? nullptr : cw.data(), on_device ? 1 : 0, level, mode, n_labels,
+                                                   hist, hist_cap, n_dumps);
+    });
+}
+
 int lutldpc_codec_encode_random(lutldpc_codec *c, uint64_t seed, uint32_t stream, uint64_t frame0, int B, uint8_t *codewords) {
     return guarded([&] {
         if (!c || !codewords || B <= 0) throw std::invalid_argument("NULL / bad argument");
@@ -303,6 +319,38 @@ int lutldpc_bersim_batch(lutldpc_bersim *s, int snr_index, int64_t frame0, int B
         if (!s || !stats || B <= 0) throw std::invalid_argument("NULL / bad argument");
         if (snr_index < 0 || snr_index >= (int)s->sim->SNRdB.size()) throw std::invalid_argument("snr_index out of range");
         s->sim->sim_batch(s->sim->SNRdB[(size_t)snr_index], snr_index, frame0, B, reinterpret_cast<FrameStats *>(stats));
+        return LUTLDPC_OK;
+    });
+}
+int lutldpc_bersim_message_histogram(lutldpc_bersim *s, int snr_index, int64_t frame0, int B, int level, int mode, int n_labels,
+                                     int64_t *hist, int64_t hist_cap, int32_t *n_dumps) {
+    return guarded([&] {
+        if (!s || !hist || B <= 0) throw std::invalid_argument("NULL / bad argument");
+        if (snr_index < 0 || snr_index >= (int)s->sim->SNRdB.size()) throw std::invalid_argument("snr_index out of range");
+        return s->sim->message_histogram(s->sim->SNRdB[(size_t)snr_index], snr_index, frame0, B, level, mode, n_labels, hist, hist_cap, n_dumps);
+    });
+}
+lutldpc_decoder *lutldpc_bersim_decoder(lutldpc_bersim *s) {
+    lutldpc_decoder *d = nullptr;
+    guarded([&] {
+        auto *lut = s ? dynamic_cast<LDPC_BER_Sim_LUT *>(s->sim.get()) : nullptr;
+        if (!lut) throw std::logic_error("not a [LUT] simulation");
+        d = lut->codec()->device_handle();
+        return LUTLDPC_OK;
+    });
+    return d;
+}
+int lutldpc_bersim_code(lutldpc_bersim *s, int32_t *dims, int32_t *dv, int32_t *dc, int32_t *cn_msg_idx, int32_t *nq_msg) {
+    return guarded([&] {
+        auto *lut = s ? dynamic_cast<LDPC_BER_Sim_LUT *>(s->sim.get()) : nullptr;
+        if (!lut) throw std::logic_error("not a [LUT] simulation");
+        if (!dims) throw std::invalid_argument("NULL argument");
+        LDPC_Code_LUT &C = *lut->codec();
+        dims[0] = C.get_nvar(); dims[1] = C.get_nchk(); dims[2] = (int32_t)C.get_cn_msg_idx().size(); dims[3] = C.get_nrof_iterations();
+        if (dv) std::memcpy(dv, C.get_dv_vec().data(), sizeof(int32_t) * C.get_dv_vec().size());
+        if (dc) std::memcpy(dc, C.get_dc_vec().data(), sizeof(int32_t) * C.get_dc_vec().size());
+        if (cn_msg_idx) std::memcpy(cn_msg_idx, C.get_cn_msg_idx().data(), sizeof(int32_t) * C.get_cn_msg_idx().size());
+        if (nq_msg) for (int i = 0; i < dims[3]; i++) nq_msg[i] = C.Nq_Msg[(size_t)i];
         return LUTLDPC_OK;
     });
 }

@@ -23,6 +23,9 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
+MODES = {"all": 0, "active": 1}      # counting modes of the message histograms (include/lut_ldpc_hip.h)
+
+
 class Decoder:
     def __init__(self, nvar, nchk, dv, dc, cn_msg_idx, nq_cha, nq_msg, reuse_vec, max_iters, min_lut,
                  var_trees_txt, chk_trees_txt="", device=0):
@@ -77,6 +80,53 @@ class Decoder:
                                                      _p(trace, C.c_uint8), trace.size, C.byref(got)))
         assert got.value == n_dumps
         return out, iters, trace
+
+    # ---- message-label histograms (lut_ldpc_amd/msg_stats.py works on their result) ------------------------
+    def set_edge_groups(self, edge_group=None, n_groups=1):
+        """Grouping of the histograms: edge_group[E] (VN-major edge order) with values in [0, n_groups), or None for one group."""
+        if edge_group is None:
+            check(lib.lutldpc_decoder_set_edge_groups(self._h, None, int(n_groups)))
+        else:
+            eg = _i32(edge_group)
+            if eg.shape != (self.histogram_shape(2)[3],):
+                raise ValueError("edge_group must hold one entry per edge")
+            check(lib.lutldpc_decoder_set_edge_groups(self._h, _p(eg, C.c_int32), int(n_groups)))
+
+    def histogram_shape(self, level=3):
+        """(n_dumps of `level`, n_groups, largest message alphabet, edges)"""
+        out = (C.c_int32 * 4)()
+        check(lib.lutldpc_decoder_histogram_shape(self._h, int(level), out))
+        return tuple(out)
+
+    def new_histogram(self, level=3, n_labels=None) -> np.ndarray:
+        n_dumps, n_groups, nq, _ = self.histogram_shape(level)
+        return np.zeros((n_dumps, n_groups, 2, int(n_labels or nq)), np.int64)
+
+    def message_histogram(self, cha, msg0, sent=None, level=3, mode="all", n_labels=None, hist=None, decode=True):
+        """Counts the edge-message labels of every dump of output_verbosity = level on the device: hist[dump, group, sent bit, label]
+        (int64), ADDED into `hist` when given.  mode "all": every frame at every dump (exit tests off); "active": the dumps the
+        reference would have printed under the decoder's exit conditions.  sent: [B, nvar] sent bits or None (all-zero codeword).
+        Returns (hist, bits, iters) with decode=True (the decode of the same call), else hist alone."""
+        cha = np.ascontiguousarray(cha, np.uint8); msg0 = np.ascontiguousarray(msg0, np.uint8)
+        B, N = cha.shape
+        if N != self.nvar or msg0.shape != cha.shape:
+            raise ValueError("cha/msg0 must be [B, nvar]")
+        if sent is not None:
+            sent = np.ascontiguousarray(sent, np.uint8)
+            if sent.shape != cha.shape:
+                raise ValueError("sent must be [B, nvar]")
+        hist = self.new_histogram(level, n_labels) if hist is None else hist
+        if hist.dtype != np.int64 or not hist.flags.c_contiguous or hist.ndim != 4:
+            raise ValueError("hist must be a C-contiguous int64 array [dump, group, 2, label]")
+        bits = np.empty((B, N), np.uint8) if decode else None
+        iters = np.empty(B, np.int32) if decode else None
+        got = C.c_int32()
+        check(lib.lutldpc_decoder_histogram_batch(self._h, _p(cha, C.c_uint8), _p(msg0, C.c_uint8), _p(sent, C.c_uint8) if sent is not None else None, B,
+                                                  int(level), MODES[mode] if isinstance(mode, str) else int(mode), hist.shape[3],
+                                                  _p(bits, C.c_uint8) if decode else None, _p(iters, C.c_int32) if decode else None,
+                                                  _p(hist, C.c_int64), hist.size, C.byref(got)))
+        assert got.value == hist.shape[0]
+        return (hist, bits, iters) if decode else hist
 
     def decode_llr_batch(self, llr, qb_cha, qb_msg, mode=0, cha2msg_map=None):
         llr = np.ascontiguousarray(llr, np.float64)
