@@ -209,6 +209,59 @@ int lutldpc_decoder_sim_batch_histogram(lutldpc_decoder *d, const lutldpc_channe
                                         int B, const uint8_t *codewords, int device_codewords, int level, int mode, int n_labels,
                                         int64_t *hist, int64_t hist_cap, int32_t *n_dumps);
 
+/*
+ * Failed frames captured on the device (lut_ldpc_amd/csrc/hip/kernels_events.hpp): which variable nodes of a frame were decided
+ * wrongly, which checks stayed unsatisfied, how heavy both patterns are and whether the decoder knew -- without the decided bits
+ * leaving the device.  Frames are Philox-addressed, so (seed, stream, frame) replays a captured frame exactly.
+ *
+ * For EVERY frame of the batch the device counts cw_errors (decided bits over all nvar nodes that differ from the sent ones) and
+ * unsat_checks (parity checks the decided bits violate).  A frame is SELECTED by `select`:
+ *   LUTLDPC_EV_CODEWORD   (0)  cw_errors > 0
+ *   LUTLDPC_EV_INFO       (1)  data-bit errors > 0 (what the counters call a frame error)
+ *   LUTLDPC_EV_FAILED     (2)  iteration code < 0
+ *   LUTLDPC_EV_UNDETECTED (3)  cw_errors > 0 and iteration code >= 0
+ * Selected frames get slots in ascending frame order; the first max_frames of them are KEPT and written:
+ *   events[slot][8]          {frame offset in the batch, iteration code, cw_errors, data-bit errors, unsat_checks, uncoded errors
+ *                             (0 for events_batch: no channel), positions stored, checks stored}; the weights are the true ones
+ *                             even where the lists are cut short
+ *   positions[slot][max_pos] the wrong nodes, ascending, the first max_pos of them; unused entries -1
+ *   checks[slot][max_chk]    the unsatisfied checks, likewise
+ * Rows from n_stored on are left untouched.  n_selected = number of selected frames (may exceed max_frames), n_stored = kept.
+ * positions / checks may be NULL when their maximum is 0.  node_errors[nvar] / check_fails[nchk] (optional, may be NULL): the
+ * number of frames of the batch in which a node is wrong / a check unsatisfied -- over ALL frames, not only the selected ones --
+ * ADDED into the caller's arrays, so that a caller can loop over batches.  Everything is integer arithmetic: the result is
+ * bit-reproducible, the lists are sorted by construction.
+ *
+ * events_batch: lutldpc_decoder_decode_batch plus the capture.  sent = host [B*nvar] bits the decided ones are compared with, or
+ *   NULL (all-zero codeword); it need not be a codeword.  K_info = number of leading bits counted as data bits.  out_bits /
+ *   out_iters may be NULL.
+ * sim_batch_events: the frames of lutldpc_decoder_sim_batch (device_codewords = 0; codewords = host [B*nvar] or NULL) or
+ *   lutldpc_decoder_sim_batch_random (device_codewords != 0), the same frame_stats, and the capture on top.
+ * ERR_ARG: NULL request, NULL events, a negative size, select out of range, NULL positions / checks with a positive maximum, bad
+ * B / K_info; ERR_STATE: host-only handle, device_codewords without a generator.
+ */
+#define LUTLDPC_EV_CODEWORD   0
+#define LUTLDPC_EV_INFO       1
+#define LUTLDPC_EV_FAILED     2
+#define LUTLDPC_EV_UNDETECTED 3
+typedef struct {
+    int32_t select;
+    int32_t max_frames, max_pos, max_chk;
+    int32_t *events;        /* [max_frames][8]       */
+    int32_t *positions;     /* [max_frames][max_pos] */
+    int32_t *checks;        /* [max_frames][max_chk] */
+    int64_t *node_errors;   /* [nvar], added into; or NULL */
+    int64_t *check_fails;   /* [nchk], added into; or NULL */
+    int32_t n_selected;     /* out */
+    int32_t n_stored;       /* out */
+} lutldpc_event_request;
+
+int lutldpc_decoder_events_batch(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0, const uint8_t *sent, int B, int K_info,
+                                 uint8_t *out_bits, int32_t *out_iters, lutldpc_event_request *req);
+int lutldpc_decoder_sim_batch_events(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0,
+                                     int B, const uint8_t *codewords, int device_codewords, int K_info, int32_t *frame_stats,
+                                     lutldpc_event_request *req);
+
 /* The decoder's HIP stream (hipStream_t as void*), for callers that enqueue their own work. */
 void *lutldpc_decoder_stream(lutldpc_decoder *d);
 

@@ -83,6 +83,11 @@ int lutldpc_codec_sample_labels(lutldpc_codec *c, double snr_db, uint64_t seed, 
  * hist[n_dumps][n_groups][2][n_labels]; the edge grouping is that of lutldpc_codec_decoder(c). */
 int lutldpc_codec_message_histogram(lutldpc_codec *c, double snr_db, uint64_t seed, uint32_t stream, uint64_t frame0, int B, int zero_codeword,
                                     int level, int mode, int n_labels, int64_t *hist, int64_t hist_cap, int32_t *n_dumps);
+/* Failed frames of the batch lutldpc_codec_sim_batch would simulate, captured on the device (lutldpc_decoder_sim_batch_events, see
+ * lut_ldpc_hip.h for the request): same cells, same sent codewords, chosen by the same rule.  events[slot][0] is the frame's offset
+ * in the batch: frame0 + that offset replays it. */
+int lutldpc_codec_error_events(lutldpc_codec *c, double snr_db, uint64_t seed, uint32_t stream, uint64_t frame0, int B, int zero_codeword,
+                               lutldpc_event_request *req);
 /* the channel cell table for that SNR (see lut_ldpc_hip.h): returns n_cells; arrays need 72 entries */
 int lutldpc_codec_channel_cells(lutldpc_codec *c, double snr_db, uint64_t *thr, uint8_t *cha, uint8_t *msg, uint8_t *neg,
                                 uint8_t *cha_m, uint8_t *msg_m);
@@ -106,6 +111,9 @@ int lutldpc_bersim_batch(lutldpc_bersim *s, int snr_index, int64_t frame0, int B
  * (= snr_index) and codeword setting; [LUT] simulations only (ERR_STATE for [BP]) */
 int lutldpc_bersim_message_histogram(lutldpc_bersim *s, int snr_index, int64_t frame0, int B, int level, int mode, int n_labels,
                                      int64_t *hist, int64_t hist_cap, int32_t *n_dumps);
+/* the same frames -> captured failed frames (lutldpc_decoder_sim_batch_events) with the simulation's own seed, stream (= snr_index)
+ * and codeword setting, device or host codewords by the rule of lutldpc_bersim_batch; [LUT] simulations only (ERR_STATE for [BP]) */
+int lutldpc_bersim_error_events(lutldpc_bersim *s, int snr_index, int64_t frame0, int B, lutldpc_event_request *req);
 /* the decoder handle of a [LUT] simulation (edge groups, shapes; NULL + error otherwise) and its code: dims[4] = {nvar, nchk, E,
  * max_iter}; dv[nvar], dc[nchk], cn_msg_idx[E], nq_msg[max_iter] are filled where not NULL */
 lutldpc_decoder *lutldpc_bersim_decoder(lutldpc_bersim *s);

@@ -38,6 +38,16 @@ lib = _load()
 
 _vp, _ip, _u8p, _dp, _cp = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_char_p
 _i64p = C.POINTER(C.c_int64)
+
+
+class EventRequest(C.Structure):
+    """lutldpc_event_request (include/lut_ldpc_hip.h): what a capture of failed frames selects, how much it keeps, where it goes."""
+    _fields_ = [("select", C.c_int32), ("max_frames", C.c_int32), ("max_pos", C.c_int32), ("max_chk", C.c_int32),
+                ("events", _ip), ("positions", _ip), ("checks", _ip), ("node_errors", _i64p), ("check_fails", _i64p),
+                ("n_selected", C.c_int32), ("n_stored", C.c_int32)]
+
+
+_evp = C.POINTER(EventRequest)
 _SIGNATURES = {
     "lutldpc_last_error": (_cp, []),
     "lutldpc_version": (_cp, []),
@@ -68,6 +78,8 @@ _SIGNATURES = {
     "lutldpc_decoder_histogram_batch": (C.c_int, [_vp, _u8p, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, _ip, _i64p, C.c_int64, _ip]),
     "lutldpc_decoder_sim_batch_histogram": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                       _i64p, C.c_int64, _ip]),
+    "lutldpc_decoder_events_batch": (C.c_int, [_vp, _u8p, _u8p, _u8p, C.c_int, C.c_int, _u8p, _ip, _evp]),
+    "lutldpc_decoder_sim_batch_events": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p, C.c_int, C.c_int, _ip, _evp]),
 }
 for _name, (_res, _args) in _SIGNATURES.items():
     if hasattr(lib, _name):
@@ -137,6 +149,8 @@ _SIM_SIGNATURES = {
     "lutldpc_codec_message_histogram": (C.c_int, [_vp, C.c_double, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                   _i64p, C.c_int64, _ip]),
     "lutldpc_bersim_message_histogram": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _i64p, C.c_int64, _ip]),
+    "lutldpc_codec_error_events": (C.c_int, [_vp, C.c_double, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, _evp]),
+    "lutldpc_bersim_error_events": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int, _evp]),
     "lutldpc_bersim_decoder": (_vp, [_vp]),
     "lutldpc_bersim_code": (C.c_int, [_vp, _ip, _ip, _ip, _ip, _ip]),
 }

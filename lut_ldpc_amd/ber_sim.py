@@ -175,6 +175,16 @@ class BerSim:
         assert got.value == hist.shape[0]
         return hist
 
+    def error_events(self, snr_index: int, frame0: int, B: int, select="codeword", max_frames=1024, max_pos=64, max_chk=64, profiles=None):
+        """Failed frames among frames frame0..frame0+B-1 of an SNR point, captured on the device, with the simulation's own seed,
+        stream and codeword setting (as `batch`): an `ErrorEvents` (lut_ldpc_amd/err_events.py); events[:, 0] counts from frame0."""
+        from .err_events import _Request
+        dims = (C.c_int32 * 4)()
+        self._check(self._lib.lutldpc_bersim_code(self._h, dims, None, None, None, None))
+        rq = _Request(int(dims[0]), int(dims[1]), select, max_frames, max_pos, max_chk, profiles)
+        self._check(self._lib.lutldpc_bersim_error_events(self._h, int(snr_index), int(frame0), int(B), C.byref(rq.c)))
+        return rq.result()
+
     def add_point(self, snr: float, counters):
         c = np.ascontiguousarray(counters, np.int64)
         self._check(self._lib.lutldpc_bersim_add_point(self._h, float(snr), c.ctypes.data_as(C.POINTER(C.c_int64))))

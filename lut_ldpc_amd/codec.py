@@ -165,6 +165,14 @@ class Codec:
         assert got.value == hist.shape[0]
         return hist
 
+    def error_events(self, snr_db, seed, stream, frame0, B, zero_codeword=True, select="codeword", max_frames=1024, max_pos=64, max_chk=64, profiles=None):
+        """Failed frames of the batch sim_batch would simulate, captured on the device (Decoder.error_events): an `ErrorEvents`.
+        events[:, 0] is the offset in the batch: frame0 + offset replays the frame."""
+        from .err_events import _Request
+        rq = _Request(self.nvar, self.nchk, select, max_frames, max_pos, max_chk, profiles)
+        check(lib.lutldpc_codec_error_events(self._h, float(snr_db), int(seed), int(stream), int(frame0), int(B), int(zero_codeword), C.byref(rq.c)))
+        return rq.result()
+
     def sample_labels(self, snr_db, seed, stream, frame0, B, zero_codeword=True):
         cha, msg = np.empty((B, self.nvar), np.uint8), np.empty((B, self.nvar), np.uint8)
         cw = np.empty((B, self.nvar), np.uint8)

@@ -84,8 +84,8 @@ static int launch_sent_to_bytes(lutldpc_decoder *d, uint8_t *dst, int B) {
 
 // lutldpc_decoder_sim_batch (codewords: host, frame-major, or null) and lutldpc_decoder_sim_batch_random (device_codewords:
 // made by the encoder on the device from (seed, stream, frame))
-static int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
-                   const uint8_t *codewords, bool device_codewords, int K_info, int32_t *frame_stats, uint8_t *cha_out, uint8_t *bits_out) {
+int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
+                   const uint8_t *codewords, bool device_codewords, int K_info, int32_t *frame_stats, uint8_t *cha_out, uint8_t *bits_out, lutldpc_event_request *req) {
     if (!d || !frame_stats) return fail(LUTLDPC_ERR_ARG, "NULL argument");
     if (d->device < 0) return fail(LUTLDPC_ERR_STATE, "decoder was created without a device (host-only handle)");
     if (B <= 0 || K_info < 0 || K_info > d->nvar) return fail(LUTLDPC_ERR_ARG, "bad B / K_info");
@@ -128,6 +128,11 @@ static int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells
             LAUNCH_CHECK();
             HIP_TRY(hipMemcpyAsync(bits_out, d->d_out_bits.p, n, hipMemcpyDeviceToHost, d->stream));
         }
+    }
+    if (req) {
+        // the capture reads sent-bit rows in all three cases: the encoder's, the caller's codewords converted once, or none
+        if (codewords && (rc = sent_rows_from_device(d, B))) return rc;
+        if ((rc = capture_events(d, B, K_info, device_codewords || codewords ? d->d_sent.p : nullptr, d->d_stats.p, req))) return rc;
     }
     HIP_TRY(hipStreamSynchronize(d->stream));
     return LUTLDPC_OK;

@@ -10,6 +10,7 @@
 //   decoder_resident.hip   LDS-resident decoder (jit_resident.hpp)
 //   decoder_frontend.hip   channel sampler, encoder, error counters and their C-ABI entries    (kernels_frontend.hpp, kernels_encode.hpp)
 //   decoder_stats.hip      message-label histograms per dump: edge groups, the counted decode, C-ABI   (kernels_stats.hpp)
+//   decoder_events.hip     failed frames captured on the device: weights, selection, sorted error / syndrome lists, C-ABI   (kernels_events.hpp)
 #pragma once
 #include "../../../include/lut_ldpc_hip.h"
 #include "kernels_common.hpp"
@@ -229,6 +230,14 @@ struct lutldpc_decoder {
     std::vector<int32_t> hist_edges, hist_run, hist_chunks;
     DevBuf<int32_t> d_hist_edges, d_hist_chunks, d_last_dump;
     DevBuf<unsigned long long> d_hist;
+    // capture of failed frames (decoder_events.hip; allocated by the first capture call, never by a plain decode): per-frame
+    // weights [bpad][4], slot of every frame, {selected, stored}, the records and lists of the kept frames, the byte counts of
+    // every node / check run [run][bpad] with their prefix sums per kept frame [run][slots], the two profiles
+    struct Events {
+        DevBuf<int32_t> frame_w, slot_of, counters, records, positions, checks, off_n, off_c;
+        DevBuf<uint8_t> cnt_n, cnt_c;
+        DevBuf<unsigned long long> node_errors, check_fails;
+    } ev;
     // LDS-resident decoder (jit_resident.hpp): codes whose edge messages fit the LDS of a compute unit are decoded by ONE generated
     // kernel per decode -- all iterations inside, no HBM traffic between the labels and the decided bits.
     // frame-major label / bit buffers of the current decode_device call, handed to the resident kernel (it reads and writes them
@@ -378,9 +387,21 @@ int fill_cells(const lutldpc_channel_cells *c, const lutldpc_decoder *d, Channel
 int sample_tiles(lutldpc_decoder *d, const ChannelCells &C, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *codewords_host,
                  const uint8_t *sent_rows = nullptr);
 int encode_tiles(lutldpc_decoder *d, uint64_t seed, uint32_t stream, uint64_t frame0, int B);       // random codewords -> d_sent
+// lutldpc_decoder_sim_batch / _random; req != null: the capture of decoder_events.hip on top (lutldpc_decoder_sim_batch_events)
+int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *codewords,
+                   bool device_codewords, int K_info, int32_t *frame_stats, uint8_t *cha_out, uint8_t *bits_out, lutldpc_event_request *req = nullptr);
 
 // ---- decoder_stats.hip (home of the kernels of kernels_stats.hpp)
 hipError_t preload_stats_kernels();
 int hist_dump(lutldpc_decoder *d);           // one dump of a counted decode: the message rows into d->trace.hist (decode_tiles_launch)
+int sent_rows_from_device(lutldpc_decoder *d, int B);                              // d_codewords (frame-major, B frames) -> d_sent
+int sent_rows_from_host(lutldpc_decoder *d, const uint8_t *codewords, int B);     // host frame-major codewords -> d_codewords -> d_sent
+
+// ---- decoder_events.hip (home of the kernels of kernels_events.hpp)
+hipError_t preload_events_kernels();
+int event_request_check(const lutldpc_event_request *req);                         // LUTLDPC_ERR_ARG for a malformed request
+// after decode_tiles of B frames: weights, selection and lists of the batch in d_hard / d_iters into req.  sent_rows: sent-bit
+// rows of the batch or null (all-zero codeword); stats: the front end's per-frame counters (device) or null.  Synchronises.
+int capture_events(lutldpc_decoder *d, int B, int K_info, const uint8_t *sent_rows, const int32_t *stats, lutldpc_event_request *req);
 
 #pragma GCC visibility pop

@@ -88,17 +88,22 @@ static bool decode_moves_labels(const lutldpc_decoder *d, int G) {
     return !resident_active(d) && d->opt.skew && d->skew_ok && d->psc && compaction_on(d, G);
 }
 
-// host frame-major codewords -> d_sent (sent-bit rows of bpad(B) frames)
-static int sent_rows_from_host(lutldpc_decoder *d, const uint8_t *codewords, int B) {
+// frame-major codewords of B frames in d_codewords -> d_sent (sent-bit rows of bpad(B) frames)
+int sent_rows_from_device(lutldpc_decoder *d, int B) {
     const int G = d->bpad(B) / d->tile(), N = d->nvar;
     const size_t n_bytes = (size_t)G * N * (d->pack == 2 ? sent_row_bytes<2>() : sent_row_bytes<1>());
-    HIP_TRY(d->d_codewords.alloc((size_t)B * N));
     HIP_TRY(d->d_sent.alloc(n_bytes));
-    HIP_TRY(hipMemcpyAsync(d->d_codewords.p, codewords, (size_t)B * N, hipMemcpyHostToDevice, d->stream));
     Timed t(d, LUTLDPC_K_LAYOUT);
     PACK_DISPATCH(d, launch_k(bytes_to_sent_rows_kernel<PK>, dim3((unsigned)((n_bytes + 255) / 256)), dim3(256), 0, d->stream, d->d_codewords.p, B, N, n_bytes, d->d_sent.p));
     LAUNCH_CHECK();
     return LUTLDPC_OK;
+}
+
+// host frame-major codewords -> d_sent
+int sent_rows_from_host(lutldpc_decoder *d, const uint8_t *codewords, int B) {
+    HIP_TRY(d->d_codewords.alloc((size_t)B * d->nvar));
+    HIP_TRY(hipMemcpyAsync(d->d_codewords.p, codewords, (size_t)B * d->nvar, hipMemcpyHostToDevice, d->stream));
+    return sent_rows_from_device(d, B);
 }
 
 // restores the exit conditions and the trace sink of a handle on every way out of the counted pass

@@ -404,6 +404,20 @@ int LDPC_BER_Sim_LUT::message_histogram(double snr, int snr_index, int64_t frame
                                                device_codewords ? 1 : 0, level, mode, n_labels, hist, hist_cap, n_dumps);
 }
 
+// the frames of sim_batch -- same seed, same stream, same codewords, made where sim_batch makes them -- with the failed ones captured
+int LDPC_BER_Sim_LUT::error_events(double snr, int snr_index, int64_t frame0, int B, lutldpc_event_request *req) {
+    const ChannelCellTable cells = channel_cells_at(*C, snr);
+    const lutldpc_channel_cells view = cells.view();
+    const uint64_t seed = (uint64_t)(int64_t)(rand_seed + rand_seed_offset);
+    if (!zero_codeword && !encoder_set) throw std::runtime_error("Non zero codewords require the encoder to be set!");
+    const bool device_codewords = !zero_codeword && decoder_output_verbosity <= 1 && C->has_device_generator();
+    std::vector<unsigned char> codewords;
+    if (!zero_codeword && !device_codewords) codewords = random_codewords(*C, seed, (uint32_t)snr_index, (uint64_t)frame0, B, codeword_length, dataword_length);
+    std::vector<int32_t> stats((size_t)B * 4);
+    return lutldpc_decoder_sim_batch_events(C->device_handle(), &view, seed, (uint32_t)snr_index, (uint64_t)frame0, B, codewords.empty() ? nullptr : codewords.data(),
+                                            device_codewords ? 1 : 0, dataword_length, stats.data(), req);
+}
+
 // ------------------------------------------------------------------ LDPC_BER_Sim_BP
 void awgn_llr_frames(uint64_t seed, uint32_t stream, uint64_t frame0, int B, int N, double N0, const unsigned char *codewords, double *llr, int32_t *uncoded) {
     const double sigma = std::sqrt(N0 / 2), two_pi = 6.283185307179586476925286766559;

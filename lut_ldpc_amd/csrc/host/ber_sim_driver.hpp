@@ -111,6 +111,8 @@ public:
     virtual int message_histogram(double, int, int64_t, int, int, int, int, int64_t *, int64_t, int32_t *) {
         throw std::logic_error("message histograms exist for [LUT] simulations only");
     }
+    // failed frames of the same frames, captured on the device (lutldpc_decoder_sim_batch_events); returns its code
+    virtual int error_events(double, int, int64_t, int, lutldpc_event_request *) { throw std::logic_error("error events exist for [LUT] simulations only"); }
     int get_codeword_length() const { return codeword_length; }
     int get_dataword_length() const { return dataword_length; }
     virtual std::string gen_filename() const;                    // :104-115
@@ -152,6 +154,7 @@ public:
     void sim_batch(double snr, int snr_index, int64_t frame0, int B, FrameStats *stats) override;
     int message_histogram(double snr, int snr_index, int64_t frame0, int B, int level, int mode, int n_labels, int64_t *hist, int64_t hist_cap,
                           int32_t *n_dumps) override;
+    int error_events(double snr, int snr_index, int64_t frame0, int B, lutldpc_event_request *req) override;
     std::string gen_filename() const override;                   // :553-568
     LDPC_Code_LUT *codec() { return C.get(); }
 

@@ -204,6 +204,22 @@ int lutldpc_codec_message_histogram(lutldpc_codec *c, double snr_db, uint64_t se
     });
 }
 
+int lutldpc_codec_error_events(lutldpc_codec *c, double snr_db, uint64_t seed, uint32_t stream, uint64_t frame0, int B, int zero_codeword,
+                               lutldpc_event_request *req) {
+    return guarded([&] {
+        if (!c || !req || B <= 0) throw std::invalid_argument("NULL / bad argument");
+        const ChannelCellTable cells = channel_cells_at(*c->C, snr_db);
+        const lutldpc_channel_cells view = cells.view();
+        // the sent codewords as lutldpc_codec_sim_batch chooses them
+        const bool on_device = !zero_codeword && c->C->has_device_generator();
+        std::vector<unsigned char> cw;
+        if (!zero_codeword && !on_device) cw = random_codewords(*c->C, seed, stream, frame0, B, c->C->get_nvar(), c->C->get_ninfo());
+        std::vector<int32_t> stats((size_t)B * 4);
+        return lutldpc_decoder_sim_batch_events(c->C->device_handle(), &view, seed, stream, frame0, B, cw.empty() ? nullptr : cw.data(), on_device ? 1 : 0,
+                                                c->C->get_ninfo(), stats.data(), req);
+    });
+}
+
 int lutldpc_codec_encode_random(lutldpc_codec *c, uint64_t seed, uint32_t stream, uint64_t frame0, int B, uint8_t *codewords) {
     return guarded([&] {
         if (!c || !codewords || B <= 0) throw std::invalid_argument("NULL / bad argument");
@@ -328,6 +344,13 @@ int lutldpc_bersim_message_histogram(lutldpc_bersim *s, int snr_index, int64_t f
         if (!s || !hist || B <= 0) throw std::invalid_argument("NULL / bad argument");
         if (snr_index < 0 || snr_index >= (int)s->sim->SNRdB.size()) throw std::invalid_argument("snr_index out of range");
         return s->sim->message_histogram(s->sim->SNRdB[(size_t)snr_index], snr_index, frame0, B, level, mode, n_labels, hist, hist_cap, n_dumps);
+    });
+}
+int lutldpc_bersim_error_events(lutldpc_bersim *s, int snr_index, int64_t frame0, int B, lutldpc_event_request *req) {
+    return guarded([&] {
+        if (!s || !req || B <= 0) throw std::invalid_argument("NULL / bad argument");
+        if (snr_index < 0 || snr_index >= (int)s->sim->SNRdB.size()) throw std::invalid_argument("snr_index out of range");
+        return s->sim->error_events(s->sim->SNRdB[(size_t)snr_index], snr_index, frame0, B, req);
     });
 }
 lutldpc_decoder *lutldpc_bersim_decoder(lutldpc_bersim *s) {

@@ -128,6 +128,31 @@ class Decoder:
         assert got.value == hist.shape[0]
         return (hist, bits, iters) if decode else hist
 
+    # ---- failed frames captured on the device (lut_ldpc_amd/err_events.py) --------------------------------------
+    def error_events(self, cha, msg0, sent=None, select="codeword", max_frames=1024, max_pos=64, max_chk=64, profiles=None, k_info=None, decode=False):
+        """Decodes the batch and captures its failed frames on the device: an `ErrorEvents` with one record per kept frame, the
+        sorted indices of its wrong nodes (first max_pos) and unsatisfied checks (first max_chk), and the number selected.
+        sent: [B, nvar] bits the decided ones are compared with (None: all-zero codeword; need not be a codeword).  select:
+        "codeword" (any wrong node), "info" (a wrong data bit among the first k_info nodes, default nvar - nchk), "failed"
+        (iteration code < 0), "undetected" (wrong, but code >= 0).  profiles: None, True (new arrays) or (node_errors int64 [nvar],
+        check_fails int64 [nchk]) to add into.  decode=True returns (events, bits, iters)."""
+        from .err_events import _Request
+        cha = np.ascontiguousarray(cha, np.uint8); msg0 = np.ascontiguousarray(msg0, np.uint8)
+        B, N = cha.shape
+        if N != self.nvar or msg0.shape != cha.shape:
+            raise ValueError("cha/msg0 must be [B, nvar]")
+        if sent is not None:
+            sent = np.ascontiguousarray(sent, np.uint8)
+            if sent.shape != cha.shape:
+                raise ValueError("sent must be [B, nvar]")
+        rq = _Request(self.nvar, self.nchk, select, max_frames, max_pos, max_chk, profiles)
+        bits = np.empty((B, N), np.uint8) if decode else None
+        iters = np.empty(B, np.int32) if decode else None
+        check(lib.lutldpc_decoder_events_batch(self._h, _p(cha, C.c_uint8), _p(msg0, C.c_uint8), _p(sent, C.c_uint8) if sent is not None else None, B,
+                                               int(self.nvar - self.nchk if k_info is None else k_info), _p(bits, C.c_uint8) if decode else None,
+                                               _p(iters, C.c_int32) if decode else None, C.byref(rq.c)))
+        return (rq.result(), bits, iters) if decode else rq.result()
+
     def decode_llr_batch(self, llr, qb_cha, qb_msg, mode=0, cha2msg_map=None):
         llr = np.ascontiguousarray(llr, np.float64)
         B, N = llr.shape
