@@ -4,6 +4,8 @@ cross-platform float RNG equality)."""
 from __future__ import annotations
 
 import functools
+import re
+import zlib
 from pathlib import Path
 
 import numpy as np
@@ -100,19 +102,38 @@ def awgn_labels(cd, B, snr_db, seed, mode=0):
     return cha, msg, llr
 
 
-def compare(cd, dec, cha, msg, psc, pisc, max_iters=None, flat=False):
+def compare(cd, dec, cha, msg, psc, pisc, max_iters=None, flat=False, cache=None):
     """Decode the same labels with the oracle and through the C-ABI: every decided bit and every returned iteration
-    code (src/LDPC_Code_LUT.cpp:259-353) must be equal.  Returns the iteration codes."""
+    code (src/LDPC_Code_LUT.cpp:259-353) must be equal.  Returns the iteration codes.  cache: a dict that keeps the oracle's
+    result per (labels, exit conditions), for callers that decode the same labels with several decoders."""
     I = max_iters or cd.max_iters
     cd.set_exit_conditions(I, psc, pisc)
     dec.set_exit_conditions(I, psc, pisc)
-    # long codes: the oracle's flat-table mode on all cores (bit-identical to its faithful mode: tests/test_oracle_flat.py)
-    want_bits, want_it = (cd.lut_decode_batch_flat if (flat or cd.code.nvar >= 10000) else cd.lut_decode_batch)(cha, msg)
+    key = (I, bool(psc), bool(pisc), cha.shape, zlib.crc32(np.ascontiguousarray(cha)), zlib.crc32(np.ascontiguousarray(msg)))
+    if cache is not None and key in cache:
+        want_bits, want_it = cache[key]
+    else:
+        # long codes: the oracle's flat-table mode on all cores (bit-identical to its faithful mode: tests/test_oracle_flat.py)
+        want_bits, want_it = (cd.lut_decode_batch_flat if (flat or cd.code.nvar >= 10000) else cd.lut_decode_batch)(cha, msg)
+        if cache is not None:
+            cache[key] = (want_bits, want_it)
     got_bits, got_it = dec.lut_decode_batch(cha, msg)
     assert (want_it == got_it).all(), (np.flatnonzero(want_it != got_it)[:8], want_it[:8], got_it[:8])
     bad = np.argwhere(want_bits != got_bits)
     assert bad.size == 0, f"{len(bad)} bit mismatches, first at frame/bit {bad[:4].tolist()}"
     return want_it
+
+
+def resident_variant(src):
+    """Which variant of the LDS-resident kernel (jit_resident.hpp) a generated source is, read off the text Decoder.resident_source
+    returns: the one place that knows the generator's wording.  U: the set of frames-per-trip values of its look-up loops."""
+    reduced, per_lane = "res_flag<PACK>(L_fail, s_" in src, "atomicOr(&L_fail[s_]" in src
+    assert reduced != per_lane, "resident kernel source: exit-test flag statement not recognised"
+    waves = re.search(r"amdgpu_waves_per_eu\((\d+)", src)
+    U = {int(u) for u in re.findall(r"fs \+= (\d+) \* BITS", src)}
+    assert U, "resident kernel source: no look-up loop found"
+    return {"flag_reduce": int(reduced), "cn_persistent": int(re.search(r"\bint cs_\d", src) is not None), "xcd": int("(nb & 7) == 0" in src),
+            "waves_eu": int(waves.group(1)) if waves else 0, "U": U}
 
 
 def write_ira_alist(path, K, M, dv_info, seed=0):
