@@ -36,16 +36,16 @@ void make_describe(lutldpc_decoder *d) {
       << ",\"nodes_per_block\":" << d->opt.nodes_per_block << ",\"vn_edges_per_wave\":" << d->opt.vn_edges_per_wave << ",\"cn_edges_per_wave\":" << d->cn_epw() << ",\"use_fast\":" << d->opt.use_fast
       << ",\"vn_classes\":[";
     for (size_t i = 0; i < d->vclass.size(); i++) {
-        const bool f = d->opt.use_fast && !d->var_fast.empty() && i < d->var_fast[0].size() && d->var_fast[0][i].ok && d->vclass[i].deg <= kFastMaxDeg;
+        const bool f = !d->var_fast.empty() && i < d->var_fast[0].size() && fast_covers(d, d->var_fast[0][i], d->vclass[i].deg);
         o << (i ? "," : "") << "{\"deg\":" << d->vclass[i].deg << ",\"nodes\":" << d->vclass[i].nodes.size() << ",\"kernel\":\""
           << (f ? "vn_balanced_fast_kernel" : (!d->var_jit.empty() && i < d->var_jit[0].size() && d->var_jit[0][i]) ? "lutldpc_jit_pass" : "tree_pass_kernel<VAR>") << "\"}";
     }
     o << "],\"cn_classes\":[";
     for (size_t i = 0; i < d->cclass.size(); i++) {
-        // fill_cn_fast decides per iteration: a schedule that mixes power-of-two and other message alphabets runs both kernels
+        // cn_minsum_shape decides per iteration: a schedule that mixes power-of-two and other message alphabets runs both kernels
         int n_fast = 0;
         for (int nq : d->Nq_Msg)
-            n_fast += d->opt.use_fast && d->min_lut && d->cclass[i].deg >= 2 && d->cclass[i].deg <= kFastMaxCnDeg && is_pow2(nq / 2) && nq / 2 <= 64;
+            n_fast += d->opt.use_fast && d->min_lut && cn_minsum_shape(nq / 2, d->cclass[i].deg);
         const char *minsum = n_fast == (int)d->Nq_Msg.size() ? "cn_minsum_fast_kernel"
                            : n_fast == 0 ? "cn_minsum_generic_kernel" : "cn_minsum_fast_kernel+cn_minsum_generic_kernel";
         o << (i ? "," : "") << "{\"deg\":" << d->cclass[i].deg << ",\"nodes\":" << d->cclass[i].nodes.size() << ",\"kernel\":\""
@@ -111,7 +111,7 @@ static const Knob kKnobs[] = {
     KNOB_F("LUTLDPC_RESIDENT_CN_PERSISTENT", resident_cn_persistent, "check items keep their LDS addresses in registers (unset: where registers allow, resident_spec)"),
     KNOB_I("LUTLDPC_RESIDENT_WAVES_EU", resident_waves_eu, 0, 8, "amdgpu_waves_per_eu of the generated kernel (0: none)"),
     // ---- debugging
-    KNOB_F("LUTLDPC_VALIDATE", validate, "1: every role of a fused launch checked against the allocation sizes, stream synchronised after every launch so that a device fault names ONE launch; no graph replay"),
+    KNOB_F("LUTLDPC_VALIDATE", validate, "1: the class parameters of every per-class launch checked against the allocation sizes (fused roles always are), stream synchronised after every launch so that a device fault names ONE launch; no graph replay"),
     KNOB_F("LUTLDPC_DEBUG_ADDR", debug_addr, "1: print where the row buffers landed (tools/config4_place_ab.sh)"),
 };
 #undef KNOB_F

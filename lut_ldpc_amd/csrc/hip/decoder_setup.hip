@@ -263,7 +263,6 @@ int compile_all(lutldpc_decoder *d) {
         progs.resize(cls.size());
         if (fast) fast->assign(cls.size(), FastClassPlan());
         std::vector<size_t> op_off(cls.size()), tab_off(cls.size());
-        int node_off = 0;
         for (size_t i = 0; i < cls.size(); i++) {
             if (cls[i].tree_class >= (int)trees.size()) return fail(LUTLDPC_ERR_ARG, "tree set is missing a degree class");
             const Tree &t = trees[(size_t)cls[i].tree_class];
@@ -276,10 +275,8 @@ int compile_all(lutldpc_decoder *d) {
             if (fast) {
                 std::map<const TreeNode *, std::pair<uint32_t, uint32_t>> tab_of;
                 for (auto &nt : progs[i].node_tabs) tab_of[nt.first] = {(uint32_t)tab_off[i] + nt.second[0], nt.second[1]};
-                (*fast)[i] = plan_fast_vn(t, kind, cls[i].deg, tab_of, node_off, (int)cls[i].nodes.size());
-                (*fast)[i].P.idx_off = d->vn_idx_off[i];
+                (*fast)[i] = plan_fast_vn(t, kind, cls[i].deg, tab_of);
             }
-            node_off += (int)cls[i].nodes.size();
         }
         return build_plan(d, cls, &progs, &op_off, &tab_off, plan);
     };
@@ -349,11 +346,6 @@ int compile_all(lutldpc_decoder *d) {
     }
     if (d->min_lut) { int rc = build_plan(d, d->cclass, nullptr, nullptr, nullptr, d->cn_minsum_plan); if (rc) return rc; }
     return LUTLDPC_OK;
-}
-
-// is class i of a pass handled by a compile-time specialised kernel?
-static bool fast_covers(const lutldpc_decoder *d, const std::vector<FastClassPlan> &fast, size_t i) {
-    return d->opt.use_fast && i < fast.size() && fast[i].ok && fast[i].P.deg <= kFastMaxDeg;
 }
 
 // Process-wide registry of the run-time generated kernels, keyed by device + source text.  Decoders share the loaded
@@ -426,7 +418,7 @@ static void build_jit(lutldpc_decoder *d) {
             auto &out = kind == TT_VAR ? d->var_jit[s] : kind == TT_DEC ? d->dec_jit[s] : d->chk_jit[s];
             out.assign(cls.size(), nullptr);
             for (size_t i = 0; i < cls.size(); i++) {
-                if (kind != TT_CHK && fast_covers(d, kind == TT_VAR ? d->var_fast[s] : d->dec_fast[s], i)) continue;
+                if (kind != TT_CHK && fast_covers(d, (kind == TT_VAR ? d->var_fast[s] : d->dec_fast[s])[i], cls[i].deg)) continue;
                 std::string src, log;
                 const bool full = kind == TT_CHK && s < d->chk_full_tab.size() && i < d->chk_full_tab[s].size() && d->chk_full_tab[s][i].second > 0;
                 if (!jit_class_source(d, full ? TT_CHK + 32 : kind, s, i, src, log)) { d->jit_log = log; continue; }

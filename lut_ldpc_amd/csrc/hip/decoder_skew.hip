@@ -14,67 +14,28 @@ bool skew_eligible(const lutldpc_decoder *d) {
     if (!d->min_lut || !d->opt.use_fast) return false;
     if ((int)(d->cclass.size() + d->vclass.size()) > kFusedMaxRoles) return false;
     int max_cn = 0, max_vn = 0;
-    for (auto &c : d->cclass) { if (c.deg < 2) return false; max_cn = std::max(max_cn, c.deg); }
+    for (auto &c : d->cclass) max_cn = std::max(max_cn, c.deg);
     for (auto &c : d->vclass) max_vn = std::max(max_vn, c.deg);
     if (fused_bucket(max_vn, max_cn) < 0) return false;
-    for (int nq : d->Nq_Msg) if (!is_pow2(nq / 2) || nq / 2 > 64) return false;
+    for (int nq : d->Nq_Msg) for (auto &c : d->cclass) if (!cn_minsum_shape(nq / 2, c.deg)) return false;
     for (size_t s = 0; s < d->var_fast.size(); s++) {
         if (d->var_plan[s].valid == false) continue;          // decision-only set
-        for (auto &f : d->var_fast[s])
-            if (!f.ok || f.P.n_tables > kFusedMaxTables) return false;
+        for (auto &f : d->var_fast[s]) if (!f.ok) return false;       // (a balanced tree of a degree the bucket holds fits its table slots in LDS)
     }
     return true;
 }
 
-static void add_cn_roles(const lutldpc_decoder *d, FusedParams &FP, std::vector<int> &blocks, HalfRange h, int ii, int check) {
-    const int I = d->max_iters, nz = d->Nq_Msg[(size_t)ii] / 2;
-    const int buf_w = kVfailSlots * d->Bcap / 4;                      // words per flag buffer
-    const bool on = ii != I - 1 && chain_active(d, d->iter_set[(size_t)ii]);
-    // decided bits of the nodes updated here: stored by the check pass that reads their messages, unless they are recovered at
-    // the end with everything else (late_hard_active + chain_hard_kernel)
-    const bool hard = d->psc && ii >= 1 && chain_active(d, d->iter_set[(size_t)(ii - 1)]) && !late_hard_active(d, true, nullptr);
+// the roles of pass ii of one half: every class with work (a degree class emptied by chain fusion has none)
+static void add_cn_roles(const lutldpc_decoder *d, std::vector<ClassParams> &roles, HalfRange h, int ii, int check) {
     for (size_t i = 0; i < d->cclass.size(); i++) {
-        RoleParams R{};
-        R.vfail_off_w = (ii & 1) * buf_w;                             // parity flags: this iteration's exit test
-        if ((on || hard) && d->chain_idx_off[i] >= 0) {
-            R.chain.idx_off = d->chain_idx_off[i];
-            R.chain.hard = hard ? 1 : 0;
-            if (on) {
-                const FastParams &F2 = d->var_fast[(size_t)d->iter_set[(size_t)ii]][(size_t)d->chain_vclass].P;
-                R.chain.on = 1;
-                R.chain.tab_off = F2.tab_off[0]; R.chain.tab_len = F2.tab_len[0]; R.chain.tab_shift = F2.tab_shift[0];
-                R.chain.check = d->psc ? 1 : 0;
-                R.chain.vfail_off_w = ((ii + 1) & 1) * buf_w;         // unanimity of the nodes updated here: the next exit test
-                R.chain.sbit_out = __builtin_ctz((unsigned)(d->Nq_Msg[(size_t)(ii + 1)] / 2) | 0x100u);
-            }
-        }
-        const int npw = d->npw_cn_class(i);
-        R.kind = 0; R.deg = d->cclass[i].deg; R.g0 = h.g0; R.G = h.G;
-        R.n_nodes = (int)d->cclass[i].nodes.size(); R.nodes_per_wave = npw;
-        R.waves_per_group = (R.n_nodes + npw - 1) / npw;
-        R.idx_off = d->cn_idx_off[i]; R.E = d->E; R.N = d->nvar; R.nz = nz; R.check = check; R.vfail_stride_w = d->Bcap / 4;
-        if (ii == 0 && d->opt.first_from_nodes) { R.first = 1; R.nidx_off = d->cn_nidx_off[i]; }
-        FP.role[FP.n_roles++] = R;
-        blocks.push_back((R.waves_per_group * h.G + 3) / 4);
+        const ClassParams R = cn_class_params(d, i, h, d->Nq_Msg[(size_t)ii] / 2, check, ii);
+        if (class_blocks(R) > 0) roles.push_back(R);
     }
 }
-static void add_vn_roles(const lutldpc_decoder *d, FusedParams &FP, std::vector<int> &blocks, HalfRange h, int ii, int check, int write_hard) {
-    const int set = d->iter_set[(size_t)ii], nz = d->Nq_Msg[(size_t)(ii + 1)] / 2;
-    const bool chained = chain_active(d, set);
-    const int buf_w = kVfailSlots * d->Bcap / 4;
+static void add_vn_roles(const lutldpc_decoder *d, std::vector<ClassParams> &roles, HalfRange h, int ii, int check, int write_hard) {
     for (size_t i = 0; i < d->vclass.size(); i++) {
-        const FastParams &F = d->var_fast[(size_t)set][i].P;
-        const int npw = d->npw_vn(F.deg);
-        RoleParams R{};
-        R.kind = 1; R.deg = F.deg; R.g0 = h.g0; R.G = h.G;
-        R.n_nodes = F.n_nodes; R.nodes_per_wave = npw;
-        R.idx_off = F.idx_off;
-        if (chained && (int)i == d->chain_vclass) { R.n_nodes = d->vn_red_n[i]; R.idx_off = d->vn_red_off[i]; }   // the others were updated by the check pass
-        R.waves_per_group = (R.n_nodes + npw - 1) / npw; R.E = d->E; R.N = d->nvar; R.nz = nz; R.shift_msg = F.shift_msg; R.check = check; R.write_hard = write_hard; R.vfail_stride_w = d->Bcap / 4;
-        R.vfail_off_w = ((ii + 1) & 1) * buf_w;                       // unanimity flags: the exit test after the NEXT check pass
-        for (int t = 0; t < F.n_tables; t++) { R.tab_off[t] = F.tab_off[t]; R.tab_len[t] = F.tab_len[t]; R.tab_shift[t] = F.tab_shift[t]; }
-        FP.role[FP.n_roles++] = R;
-        blocks.push_back((R.waves_per_group * h.G + 3) / 4);
+        const ClassParams R = vn_class_params(d, TT_VAR, d->iter_set[(size_t)ii], i, h, d->Nq_Msg[(size_t)(ii + 1)] / 2, check, write_hard, ii);
+        if (class_blocks(R) > 0) roles.push_back(R);
     }
 }
 
@@ -107,59 +68,26 @@ static int item_table(lutldpc_decoder *d, const std::vector<int> &blocks, const 
     return LUTLDPC_OK;
 }
 
-// LUTLDPC_VALIDATE: the roles of one fused launch against the sizes of everything they address
-static int validate_fused(const lutldpc_decoder *d, const FusedParams &FP, const std::vector<int> &blocks) {
-    auto bad = [&](int r, const std::string &what) { return fail(LUTLDPC_ERR_STATE, "fused launch check failed, role " + std::to_string(r) + ": " + what); };
-    if (FP.n_roles < 0 || FP.n_roles > kFusedMaxRoles || (size_t)FP.n_roles != blocks.size()) return bad(-1, "role count");
-    const int groups = d->Bcap / d->tile();
-    const size_t idx_n = d->fast_idx.size(), tab_n = d->d_tables.n, vfail_w = d->d_vfail.n / 4;
-    for (int r = 0; r < FP.n_roles; r++) {
-        const RoleParams &R = FP.role[r];
-        if (R.G < 1 || R.g0 < 0 || R.g0 + R.G > groups) return bad(r, "frame groups outside the batch buffers");
-        if (R.E != d->E || R.N != d->nvar) return bad(r, "E / N");
-        if (R.n_nodes < 1 || R.nodes_per_wave < 1 || R.waves_per_group != (R.n_nodes + R.nodes_per_wave - 1) / R.nodes_per_wave) return bad(r, "waves per group");
-        if (blocks[(size_t)r] != (R.waves_per_group * R.G + 3) / 4) return bad(r, "block count");
-        if (R.vfail_stride_w != d->Bcap / 4 || R.vfail_off_w < 0 || (size_t)R.vfail_off_w + (size_t)kVfailSlots * (size_t)R.vfail_stride_w > vfail_w) return bad(r, "flag buffer");
-        if (R.kind == 0) {
-            if (R.deg < 2 || R.deg > kFusedCnDeg[d->fused_bucket_id]) return bad(r, "check degree outside the bucket");
-            if (R.idx_off < 0 || (size_t)R.idx_off + (size_t)R.n_nodes * (size_t)R.deg > idx_n) return bad(r, "edge table");
-            if (!is_pow2(R.nz) || R.nz > 64) return bad(r, "nz");
-            if (R.first && (R.nidx_off < 0 || (size_t)R.nidx_off + (size_t)R.n_nodes * (size_t)R.deg > idx_n || R.check || R.chain.hard)) return bad(r, "node table of the first check pass");
-            if (R.chain.on || R.chain.hard) {
-                if (R.chain.idx_off < 0 || (size_t)R.chain.idx_off + 2 * (size_t)R.n_nodes > idx_n) return bad(r, "chain link table");
-                if (R.chain.on && (R.chain.tab_off < 0 || R.chain.tab_len < 4 || R.chain.tab_len > 1024 || (size_t)R.chain.tab_off + (size_t)R.chain.tab_len > tab_n)) return bad(r, "chain table");
-                if (R.chain.on && R.chain.check && (R.chain.vfail_off_w < 0 || (size_t)R.chain.vfail_off_w + (size_t)kVfailSlots * (size_t)R.vfail_stride_w > vfail_w)) return bad(r, "chain flag buffer");
-            }
-        } else {
-            if (R.deg < 1 || R.deg > kFusedVnDeg[d->fused_bucket_id]) return bad(r, "variable degree outside the bucket");
-            if (R.idx_off < 0 || (size_t)R.idx_off + 2 * (size_t)R.n_nodes > idx_n) return bad(r, "node table");
-            const int nt = R.deg >= 3 ? R.deg - 1 : 1;
-            for (int t = 0; t < nt; t++)
-                if (R.tab_off[t] < 0 || R.tab_len[t] < 1 || R.tab_len[t] > kFastTableStride || (R.tab_off[t] & 3) || (size_t)R.tab_off[t] + (size_t)R.tab_len[t] > tab_n) return bad(r, "table " + std::to_string(t));
-        }
-    }
-    return LUTLDPC_OK;
-}
-
 // the item table of one launch: per-wave work of a role ~ edges per wave, a variable-node edge costing about 3x a check
 // edge (LUT look-ups); the slow roles keep clear of the end of the launch (item_table)
-static int plan_items(lutldpc_decoder *d, const FusedParams &FP, const std::vector<int> &blocks, const int32_t **items, int *nb) {
-    std::vector<double> cost(blocks.size()), front(blocks.size());
+static int plan_items(lutldpc_decoder *d, const std::vector<ClassParams> &roles, const int32_t **items, int *nb) {
+    std::vector<int> blocks(roles.size());
+    std::vector<double> cost(roles.size()), front(roles.size());
     double cmax = 0;
-    for (size_t r = 0; r < blocks.size(); r++) {
-        const RoleParams &R = FP.role[r];
+    for (size_t r = 0; r < roles.size(); r++) {
+        const ClassParams &R = roles[r];
+        blocks[r] = (int)class_blocks(R);
         cost[r] = (double)R.deg * R.nodes_per_wave * (R.kind ? 3.0 * R.deg / 4.0 : 1.0);
         cmax = std::max(cmax, cost[r]);
     }
-    for (size_t r = 0; r < blocks.size(); r++) front[r] = d->opt.tail_front * cost[r] / (cmax > 0 ? cmax : 1.0);
+    for (size_t r = 0; r < roles.size(); r++) front[r] = d->opt.tail_front * cost[r] / (cmax > 0 ? cmax : 1.0);
     return item_table(d, blocks, front, items, nb);
 }
 
 static int launch_fused_slot(lutldpc_decoder *d, const lutldpc_decoder::SkewPlan &plan, const lutldpc_decoder::SkewSlot &sl, bool vn_check) {
     if (sl.nb == 0) return LUTLDPC_OK;
     Timed t(d, LUTLDPC_K_FUSED_PASS);
-#define FUSED_ARGS d->stream, plan.d_roles.p + sl.role_off, sl.items, sl.nb, d->opt.fused_prio, vn_check, d->d_msgs.p, d->d_cha_t.p, d->d_hard.p, \
-                   reinterpret_cast<const uint32_t *>(d->d_state.p), reinterpret_cast<uint32_t *>(d->d_vfail.p), d->d_tables.p, d->d_fast_idx.p, d->d_msg0_t.p
+#define FUSED_ARGS d->stream, plan.d_roles.p + sl.role_off, sl.items, sl.nb, d->opt.fused_prio, vn_check, pass_bufs(d)
     if (d->fused_bucket_id == 0) PACK_DISPATCH(d, (lutldpc::launch_fused<PK, 0>(FUSED_ARGS)));
     else if (d->fused_bucket_id == 1) PACK_DISPATCH(d, (lutldpc::launch_fused<PK, 1>(FUSED_ARGS)));
     else if (d->fused_bucket_id == 2) PACK_DISPATCH(d, (lutldpc::launch_fused<PK, 2>(FUSED_ARGS)));
@@ -244,15 +172,14 @@ int launch_uncompaction(lutldpc_decoder *d, const HalfRange (&half)[2], int Bpad
 
 // Build (once per shape) the launch plan of the message-passing iterations of both halves: slot s pairs pass s of half A
 // with pass s-1 of half B, a pass being CN(ii) for even and VN(ii) for odd numbers.  Every role is checked against the
-// sizes of what it addresses before the plan is accepted (validate_fused), the roles then move to device memory once.
+// sizes of what it addresses before the plan is accepted (validate_class), the roles then move to device memory once.
 static int build_skew_plan(lutldpc_decoder *d, int G, lutldpc_decoder::SkewPlan &plan) {
     const int I = d->max_iters, n_ops = 2 * I - 1;
     const HalfRange half[2] = {{0, (G + 1) / 2}, {(G + 1) / 2, G - (G + 1) / 2}};
     const int psc = d->psc ? 1 : 0;
     int rc;
     for (int slot = 0; slot <= n_ops; slot++) {
-        FusedParams FP{};
-        std::vector<int> blocks;
+        std::vector<ClassParams> roles;
         lutldpc_decoder::SkewSlot sl;
         for (int hf = 0; hf < 2; hf++) {
             const int op = slot - hf;                 // B lags by one pass
@@ -260,20 +187,19 @@ static int build_skew_plan(lutldpc_decoder *d, int G, lutldpc_decoder::SkewPlan 
             const int ii = op / 2;
             if ((op & 1) == 0) {                      // CN(ii)
                 const int check = (psc && ii > 0) ? 1 : 0;
-                add_cn_roles(d, FP, blocks, half[hf], ii, check);
+                add_cn_roles(d, roles, half[hf], ii, check);
                 if (check) { sl.state_half = hf; sl.state_ii = ii; }
             } else {                                  // VN(ii)
-                add_vn_roles(d, FP, blocks, half[hf], ii, psc, (psc && !late_hard_active(d, true, nullptr)) ? 1 : 0);
+                add_vn_roles(d, roles, half[hf], ii, psc, (psc && !late_hard_active(d, true, nullptr)) ? 1 : 0);
             }
         }
-        // roles without work (an empty half when G == 1 never gets here; a degree class emptied by chain fusion does)
-        FusedParams FQ{};
-        std::vector<int> bq;
-        for (int r = 0; r < FP.n_roles; r++) if (blocks[(size_t)r] > 0) { FQ.role[FQ.n_roles++] = FP.role[r]; bq.push_back(blocks[(size_t)r]); }
-        if ((rc = validate_fused(d, FQ, bq))) return rc;
-        if ((rc = plan_items(d, FQ, bq, &sl.items, &sl.nb))) return rc;
-        sl.n_roles = FQ.n_roles; sl.role_off = plan.h_roles.size();
-        plan.h_roles.insert(plan.h_roles.end(), FQ.role, FQ.role + FQ.n_roles);
+        if ((int)roles.size() > kFusedMaxRoles) return fail(LUTLDPC_ERR_STATE, "fused launch check failed, role -1: role count");
+        for (size_t r = 0; r < roles.size(); r++)
+            if ((rc = validate_class(d, roles[r], "fused launch check failed, role " + std::to_string(r),
+                                     {roles[r].kind ? TT_VAR : TT_CHK, false, kFusedVnDeg[d->fused_bucket_id], kFusedCnDeg[d->fused_bucket_id], "the bucket"}))) return rc;
+        if ((rc = plan_items(d, roles, &sl.items, &sl.nb))) return rc;
+        sl.n_roles = (int)roles.size(); sl.role_off = plan.h_roles.size();
+        plan.h_roles.insert(plan.h_roles.end(), roles.begin(), roles.end());
         plan.slots.push_back(sl);
     }
     HIP_TRY(plan.d_roles.upload(plan.h_roles));

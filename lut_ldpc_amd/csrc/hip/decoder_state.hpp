@@ -5,7 +5,8 @@
 //   decoder.hip            C-ABI: create (knob table) / destroy / exit conditions / decode entries / profiling / describe / selftest
 //   decoder_setup.hip      tree compiler, dense index tables, chain fusion, JIT registry, static uploads
 //   decoder_batch.hip      batch buffers, parameter arena, placement search
-//   decoder_stream.hip     streaming decode: per-class launches, decision pass, graph replay, message trace   (kernels_generic.hpp)
+//   decoder_stream.hip     streaming decode: class parameters (the one builder and validator of ClassParams), per-class launches,
+//                          decision pass, graph replay, message trace   (kernels_generic.hpp)
 //   decoder_skew.hip       skewed two-half pipeline through pass_fused_kernel, compaction                     (kernels_compact.hpp)
 //   decoder_resident.hip   LDS-resident decoder (jit_resident.hpp)
 //   decoder_frontend.hip   channel sampler, encoder, error counters and their C-ABI entries    (kernels_frontend.hpp, kernels_encode.hpp)
@@ -266,7 +267,7 @@ struct lutldpc_decoder {
     // (the kernel reads them through a pointer), the interleaved item tables, what follows each launch.  Built once, at
     // the first decode of that shape; dropped with the batch buffers (the roles hold strides of the flag buffers).
     struct SkewSlot { int n_roles = 0; size_t role_off = 0; const int32_t *items = nullptr; int nb = 0; int state_half = -1, state_ii = 0; };
-    struct SkewPlan { std::vector<SkewSlot> slots; std::vector<RoleParams> h_roles; DevBuf<RoleParams> d_roles; };
+    struct SkewPlan { std::vector<SkewSlot> slots; std::vector<ClassParams> h_roles; DevBuf<ClassParams> d_roles; };
     std::map<std::array<int, 3>, std::unique_ptr<SkewPlan>> skew_plans;
     // interleaved item tables, keyed by the role block counts AND the (quantised) share of the timeline each role keeps clear
     std::map<std::pair<std::vector<int>, std::vector<int>>, DevBuf<int32_t>> item_tabs;
@@ -357,6 +358,24 @@ int launch_transpose_in(lutldpc_decoder *d, const uint8_t *src, uint8_t *dst_row
 int launch_transpose_out(lutldpc_decoder *d, const uint8_t *src_rows, uint8_t *dst, int B, int G, int rows = 0);
 int launch_quantize_llr(lutldpc_decoder *d, size_t n, int n_qb_Cha, int n_qb_Msg, int mode);
 bool chain_active(const lutldpc_decoder *d, int set);
+// One degree class of one pass for the frame groups `groups`: complete ClassParams, the only code that assigns their fields.
+// skew_ii: the iteration of a role of the skewed pipeline (its flag buffers, chain block, first pass), or kPerClassLaunch for
+// a launch of the streaming decode (flag buffer 0, no chain, inputs from the edge rows).
+struct HalfRange { int g0, G; };
+constexpr int kPerClassLaunch = -1;
+ClassParams cn_class_params(const lutldpc_decoder *d, size_t ci, HalfRange groups, int nz, int check, int skew_ii = kPerClassLaunch);
+ClassParams lut_cn_class_params(const lutldpc_decoder *d, int set, size_t ci, HalfRange groups, int nz, int check);      // LUT checks: a generated kernel
+ClassParams vn_class_params(const lutldpc_decoder *d, int kind, int set, size_t ci, HalfRange groups, int nz, int check, int write_hard, int skew_ii = kPerClassLaunch);
+inline bool fast_covers(const lutldpc_decoder *d, const FastClassPlan &f, int deg) { return d->opt.use_fast && f.ok && deg <= kFastMaxDeg; }   // the compile-time balanced-tree kernel takes the class
+// the kernel a ClassParams is meant for: its pass, compile-time (min-sum, balanced tables of <= 256 bytes) or generated (one
+// class blob), the degrees it has cases for and what the error message calls that limit
+struct KernelCases { int tree_kind; bool generated; int max_vn_deg, max_cn_deg; const char *limit; };
+// a ClassParams against the decoder's allocations and the cases of its kernel; `where` opens the error message
+int validate_class(const lutldpc_decoder *d, const ClassParams &P, const std::string &where, const KernelCases &k);
+inline PassBufs pass_bufs(const lutldpc_decoder *d) {
+    return {d->d_msgs.p, d->d_cha_t.p, d->d_hard.p, reinterpret_cast<const uint32_t *>(d->d_state.p), reinterpret_cast<uint32_t *>(d->d_vfail.p), d->d_tables.p,
+            d->d_fast_idx.p, d->d_msg0_t.p};
+}
 bool late_hard_active(const lutldpc_decoder *d, bool skewed, bool *chain_skip);
 int launch_late_hard(lutldpc_decoder *d, bool skewed, int g0, int G, const int32_t *ctl);
 int decode_tiles(lutldpc_decoder *d, int B);
@@ -364,7 +383,6 @@ int decode_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d_msg
 
 // ---- decoder_skew.hip (home of the kernels of kernels_compact.hpp; pass_fused_kernel through launch_fused)
 // Half A = groups [0, GA), half B = [GA, G)
-struct HalfRange { int g0, G; };
 hipError_t preload_compact_kernels();
 bool skew_eligible(const lutldpc_decoder *d);
 bool compaction_on(const lutldpc_decoder *d, int G);

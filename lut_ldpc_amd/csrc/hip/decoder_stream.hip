@@ -88,29 +88,132 @@ static PassParams filter_params(const PassParams &P, const std::vector<char> &ke
     return Q;
 }
 
+// ----------------------------------------------------------------------------- class parameters
+// The only code that fills a ClassParams.  skew_ii = kPerClassLaunch: a launch of the streaming decode (flag buffer 0, no chain,
+// inputs from the edge rows); otherwise: a role of the skewed pipeline in that iteration (decoder_skew.hip).
+static ClassParams class_params(const lutldpc_decoder *d, int kind, const NodeClass &c, int n_nodes, int idx_off, int npw, HalfRange g, int nz, int check) {
+    ClassParams P{};
+    P.kind = kind; P.deg = c.deg; P.g0 = g.g0; P.G = g.G;
+    P.n_nodes = n_nodes; P.nodes_per_wave = npw; P.waves_per_group = (n_nodes + npw - 1) / npw;
+    P.idx_off = idx_off; P.E = d->E; P.N = d->nvar; P.nz = nz; P.check = check; P.vfail_stride_w = d->Bcap / 4;
+    return P;
+}
+ClassParams cn_class_params(const lutldpc_decoder *d, size_t ci, HalfRange groups, int nz, int check, int skew_ii) {
+    const NodeClass &c = d->cclass[ci];
+    ClassParams P = class_params(d, 0, c, (int)c.nodes.size(), d->cn_idx_off[ci], skew_ii == kPerClassLaunch ? d->npw_cn(c.deg) : d->npw_cn_class(ci), groups, nz, check);
+    if (skew_ii == kPerClassLaunch) return P;
+    const int ii = skew_ii, buf_w = kVfailSlots * d->Bcap / 4;        // words per flag buffer
+    P.vfail_off_w = (ii & 1) * buf_w;                                 // parity flags: this iteration's exit test
+    if (ii == 0 && d->opt.first_from_nodes) { P.first = 1; P.nidx_off = d->cn_nidx_off[ci]; }
+    const bool on = ii != d->max_iters - 1 && chain_active(d, d->iter_set[(size_t)ii]);
+    // decided bits of the nodes updated here: stored by the check pass that reads their messages, unless they are recovered at
+    // the end with everything else (late_hard_active + chain_hard_kernel)
+    const bool hard = d->psc && ii >= 1 && chain_active(d, d->iter_set[(size_t)(ii - 1)]) && !late_hard_active(d, true, nullptr);
+    if ((on || hard) && d->chain_idx_off[ci] >= 0) {
+        P.chain.idx_off = d->chain_idx_off[ci];
+        P.chain.hard = hard ? 1 : 0;
+        if (on) {
+            const FastClassPlan &F2 = d->var_fast[(size_t)d->iter_set[(size_t)ii]][(size_t)d->chain_vclass];
+            P.chain.on = 1;
+            P.chain.tab_off = F2.tab_off[0]; P.chain.tab_len = F2.tab_len[0]; P.chain.tab_shift = F2.tab_shift[0];
+            P.chain.check = d->psc ? 1 : 0;
+            P.chain.vfail_off_w = ((ii + 1) & 1) * buf_w;             // unanimity of the nodes updated here: the next exit test
+            P.chain.sbit_out = __builtin_ctz((unsigned)(d->Nq_Msg[(size_t)(ii + 1)] / 2) | 0x100u);
+        }
+    }
+    return P;
+}
+ClassParams lut_cn_class_params(const lutldpc_decoder *d, int set, size_t ci, HalfRange groups, int nz, int check) {
+    ClassParams P = cn_class_params(d, ci, groups, nz, check);
+    const PassSeg &S = d->chk_plan[(size_t)set].P.seg[ci];           // the class blob the kernel was generated for: over full labels where there is one
+    const bool full = (size_t)set < d->chk_full_tab.size() && ci < d->chk_full_tab[(size_t)set].size() && d->chk_full_tab[(size_t)set][ci].second > 0;
+    P.tab_off[0] = full ? d->chk_full_tab[(size_t)set][ci].first : S.tab_off;
+    P.tab_len[0] = full ? d->chk_full_tab[(size_t)set][ci].second : S.tab_bytes;
+    return P;
+}
+ClassParams vn_class_params(const lutldpc_decoder *d, int kind, int set, size_t ci, HalfRange groups, int nz, int check, int write_hard, int skew_ii) {
+    const NodeClass &c = d->vclass[ci];
+    int n_nodes = (int)c.nodes.size(), idx_off = d->vn_idx_off[ci];
+    if (skew_ii != kPerClassLaunch && chain_active(d, set) && (int)ci == d->chain_vclass) { n_nodes = d->vn_red_n[ci]; idx_off = d->vn_red_off[ci]; }   // the others are updated by the check pass
+    ClassParams P = class_params(d, 1, c, n_nodes, idx_off, d->npw_vn(c.deg), groups, nz, check);
+    P.write_hard = write_hard;
+    if (skew_ii != kPerClassLaunch) P.vfail_off_w = ((skew_ii + 1) & 1) * (kVfailSlots * d->Bcap / 4);      // unanimity flags: the exit test after the NEXT check pass
+    const FastClassPlan &f = (kind == TT_DEC ? d->dec_fast : d->var_fast)[(size_t)set][ci];
+    if (fast_covers(d, f, c.deg)) {                                   // balanced tree: its tables in canonical order
+        P.shift_msg = f.shift_msg;
+        for (int t = 0; t < f.n_tables; t++) { P.tab_off[t] = f.tab_off[t]; P.tab_len[t] = f.tab_len[t]; P.tab_shift[t] = f.tab_shift[t]; }
+    } else {                                                          // generated kernel: the class blob
+        const PassSeg &S = (kind == TT_DEC ? d->dec_plan : d->var_plan)[(size_t)set].P.seg[ci];
+        P.tab_off[0] = S.tab_off; P.tab_len[0] = S.tab_bytes;
+    }
+    return P;
+}
+
+// One ClassParams against the sizes of everything it addresses and the cases of its kernel (LUTLDPC_VALIDATE=1: before every
+// per-class launch; always: every role of a skew plan)
+int validate_class(const lutldpc_decoder *d, const ClassParams &R, const std::string &where, const KernelCases &k) {
+    auto bad = [&](const std::string &what) { return fail(LUTLDPC_ERR_STATE, where + ": " + what); };
+    const int groups = d->Bcap / d->tile();
+    const size_t idx_n = d->fast_idx.size(), tab_n = d->d_tables.n, vfail_w = d->d_vfail.n / 4;
+    auto table_ok = [&](int off, int len, int min_len, int max_len) { return off >= 0 && len >= min_len && len <= max_len && !(off & 3) && (size_t)off + (size_t)len <= tab_n; };
+    if (R.G < 1 || R.g0 < 0 || R.g0 + R.G > groups) return bad("frame groups outside the batch buffers");
+    if (R.E != d->E || R.N != d->nvar) return bad("E / N");
+    if (R.n_nodes < 1 || R.nodes_per_wave < 1 || R.waves_per_group != (R.n_nodes + R.nodes_per_wave - 1) / R.nodes_per_wave) return bad("waves per group");
+    if (R.vfail_stride_w != d->Bcap / 4 || R.vfail_off_w < 0 || (size_t)R.vfail_off_w + (size_t)kVfailSlots * (size_t)R.vfail_stride_w > vfail_w) return bad("flag buffer");
+    if (R.kind != (k.tree_kind == TT_CHK ? 0 : 1)) return bad("kind");
+    if (R.kind == 0) {
+        if (R.deg < 2 || R.deg > k.max_cn_deg) return bad(std::string("check degree outside ") + k.limit);
+        if (R.idx_off < 0 || (size_t)R.idx_off + (size_t)R.n_nodes * (size_t)R.deg > idx_n) return bad("edge table");
+        if (!k.generated && (!is_pow2(R.nz) || R.nz > 64)) return bad("nz");
+        if (R.first && (R.nidx_off < 0 || (size_t)R.nidx_off + (size_t)R.n_nodes * (size_t)R.deg > idx_n || R.check || R.chain.hard)) return bad("node table of the first check pass");
+        if (R.chain.on || R.chain.hard) {
+            if (R.chain.idx_off < 0 || (size_t)R.chain.idx_off + 2 * (size_t)R.n_nodes > idx_n) return bad("chain link table");
+            if (R.chain.on && (R.chain.tab_off < 0 || R.chain.tab_len < 4 || R.chain.tab_len > 1024 || (size_t)R.chain.tab_off + (size_t)R.chain.tab_len > tab_n)) return bad("chain table");
+            if (R.chain.on && R.chain.check && (R.chain.vfail_off_w < 0 || (size_t)R.chain.vfail_off_w + (size_t)kVfailSlots * (size_t)R.vfail_stride_w > vfail_w)) return bad("chain flag buffer");
+        }
+    } else {
+        if (R.deg < 1 || R.deg > k.max_vn_deg) return bad(std::string("variable degree outside ") + k.limit);
+        if (R.idx_off < 0 || (size_t)R.idx_off + 2 * (size_t)R.n_nodes > idx_n) return bad("node table");
+    }
+    if (k.generated) {
+        if (!table_ok(R.tab_off[0], R.tab_len[0], 0, INT32_MAX)) return bad("class tables");
+    } else if (R.kind) {
+        const int leaves = k.tree_kind == TT_DEC ? R.deg : R.deg - 1, nt = leaves > 1 ? leaves : 1;       // LUT nodes of the balanced tree, root included
+        for (int t = 0; t < nt; t++)
+            if (!table_ok(R.tab_off[t], R.tab_len[t], 1, kFastTableStride)) return bad("table " + std::to_string(t));
+    }
+    return LUTLDPC_OK;
+}
+// LUTLDPC_VALIDATE=1: the parameters of a per-class launch against the allocations, before it is issued
+static int check_class_launch(const lutldpc_decoder *d, const ClassParams &P, int i, int tree_kind, bool generated) {
+    if (!d->opt.validate) return LUTLDPC_OK;
+    const KernelCases k = generated ? KernelCases{tree_kind, true, INT32_MAX, INT32_MAX, "the generated kernel"} : KernelCases{tree_kind, false, kFastMaxDeg, kFastMaxCnDeg, "the compile-time kernels"};
+    return validate_class(d, P, "class launch check failed, class " + std::to_string(i), k);
+}
+
 template <int KIND>
-static int launch_tree_pass(lutldpc_decoder *d, PassPlan &plan, std::vector<FastClassPlan> *fast, const std::vector<const JitKernel *> *jit, int G, int nz, int check, int write_hard, int kind_id,
-                     const std::vector<std::pair<int, int>> *jit_tabs = nullptr) {
+static int launch_tree_pass(lutldpc_decoder *d, PassPlan &plan, int set, const std::vector<const JitKernel *> *jit, int G, int nz, int check, int write_hard, int kind_id) {
     if (!plan.valid) return fail(LUTLDPC_ERR_STATE, "pass plan missing for this tree set");
     Timed t(d, kind_id);
     PassParams P = plan.P;
     P.G = G; P.nz = nz; P.check = check; P.write_hard = write_hard; P.vfail_stride_w = d->Bcap / 4;
     std::vector<char> keep((size_t)P.n_seg, 1);
     bool any = false;
+    const PassBufs bufs = pass_bufs(d);
+    auto class_of = [&](int i) { return KIND == TT_CHK ? lut_cn_class_params(d, set, (size_t)i, {0, G}, nz, check) : vn_class_params(d, KIND, set, (size_t)i, {0, G}, nz, check, write_hard); };
     // The compile-time and generated variable kernels read the sign of an outgoing label as bit sbit = log2(nz) (exit test and
     // decided bits); that holds only where nz is a power of two.  A variable pass that writes any other alphabet (Nq_Msg = 12:
     // nz = 6) runs in the interpreter below, which compares the label with nz.
     const bool sign_bit = KIND != TT_VAR || is_pow2(nz);
     // specialised kernels take the classes they know, one launch per degree class
-    if (d->opt.use_fast && fast && KIND != TT_CHK && sign_bit)
-        for (int i = 0; i < P.n_seg; i++) {
-            if (!(*fast)[(size_t)i].ok) continue;
+    if constexpr (KIND != TT_CHK)
+        for (int i = 0; i < P.n_seg && sign_bit; i++) {
+            if (!fast_covers(d, (KIND == TT_DEC ? d->dec_fast : d->var_fast)[(size_t)set][(size_t)i], P.seg[i].deg)) continue;
             bool ok = false;
-            FastParams FP = (*fast)[(size_t)i].P;
-            fill_vn_fast(FP, G, nz, check, write_hard, d->npw_vn(FP.deg), d->E, d->nvar, d->Bcap / 4);
+            const ClassParams FP = class_of(i);
+            if (int rc = check_class_launch(d, FP, i, KIND, false)) return rc;
             DEV_PARAM(dFP, d, FP);
-            PACK_DISPATCH(d, ok = launch_vn_fast<KIND, PK>(d->stream, FP, dFP, d->d_msgs.p, d->d_cha_t.p, d->d_hard.p,
-                                     reinterpret_cast<const uint32_t *>(d->d_state.p), reinterpret_cast<uint32_t *>(d->d_vfail.p), d->d_tables.p, d->d_fast_idx.p));
+            PACK_DISPATCH(d, ok = launch_vn_fast<KIND, PK>(d->stream, FP, dFP, bufs));
             if (ok) keep[(size_t)i] = 0;
         }
     // run-time generated kernels (jit.hpp) for the classes without a compile-time one
@@ -118,22 +221,11 @@ static int launch_tree_pass(lutldpc_decoder *d, PassPlan &plan, std::vector<Fast
         for (int i = 0; i < P.n_seg && (size_t)i < jit->size(); i++) {
             const JitKernel *k = (*jit)[(size_t)i];
             if (!keep[(size_t)i] || !k) continue;
-            FastParams F{};
-            F.n_nodes = P.seg[i].n_nodes; F.deg = P.seg[i].deg;
-            F.idx_off = KIND == TT_CHK ? d->cn_idx_off[(size_t)i] : d->vn_idx_off[(size_t)i];
-            F.nodes_per_wave = KIND == TT_CHK ? d->npw_cn(F.deg) : d->npw_vn(F.deg); F.waves_per_group = (F.n_nodes + F.nodes_per_wave - 1) / F.nodes_per_wave;
-            F.G = G; F.E = d->E; F.N = d->nvar; F.g0 = 0; F.nz = nz; F.check = check; F.write_hard = write_hard; F.vfail_stride_w = d->Bcap / 4;
-            F.tab_off[0] = P.seg[i].tab_off; F.tab_len[0] = P.seg[i].tab_bytes;
-            if (jit_tabs && (size_t)i < jit_tabs->size() && (*jit_tabs)[(size_t)i].second > 0) { F.tab_off[0] = (*jit_tabs)[(size_t)i].first; F.tab_len[0] = (*jit_tabs)[(size_t)i].second; }   // the kernel was generated for these tables
-            uint8_t *msgs = d->d_msgs.p, *hard = d->d_hard.p;
-            const uint8_t *cha = d->d_cha_t.p, *tables = d->d_tables.p;
-            const uint32_t *state_w = reinterpret_cast<const uint32_t *>(d->d_state.p);
-            uint32_t *vfail_w = reinterpret_cast<uint32_t *>(d->d_vfail.p);
-            const int32_t *fidx = d->d_fast_idx.p;
+            const ClassParams F = class_of(i);
+            if (int rc = check_class_launch(d, F, i, KIND, true)) return rc;
             DEV_PARAM(dF, d, F);
-            void *args[] = {&dF, &msgs, &cha, &hard, &state_w, &vfail_w, &tables, &fidx};
-            const unsigned blocks = (unsigned)((F.waves_per_group * G + 3) / 4);
-            HIP_TRY(hipModuleLaunchKernel(k->fn, blocks, 1, 1, 256, 1, 1, 0, d->stream, args, nullptr));
+            void *args[] = {&dF, (void *)&bufs.msgs, (void *)&bufs.cha, (void *)&bufs.hard, (void *)&bufs.state_w, (void *)&bufs.vfail_w, (void *)&bufs.tables, (void *)&bufs.fast_idx};
+            HIP_TRY(hipModuleLaunchKernel(k->fn, class_blocks(F), 1, 1, 256, 1, 1, 0, d->stream, args, nullptr));
             keep[(size_t)i] = 0;
         }
     for (char k : keep) any = any || k;
@@ -144,13 +236,11 @@ static int launch_tree_pass(lutldpc_decoder *d, PassPlan &plan, std::vector<Fast
         const int32_t *list = KIND == TT_CHK ? d->d_cn_list.p : d->d_vn_list.p;
         const int32_t *ptr = KIND == TT_CHK ? d->d_cn_ptr.p : d->d_vn_ptr.p;
         if (plan.lds_tab)
-            PACK_DISPATCH(d, launch_k(tree_pass_kernel<KIND, true, PK>, grid, block, (size_t)plan.lds_bytes, d->stream, dP, d->d_msgs.p, d->d_cha_t.p,
-                               d->d_hard.p, reinterpret_cast<const uint32_t *>(d->d_state.p), reinterpret_cast<uint32_t *>(d->d_vfail.p),
-                               d->d_ops.p, d->d_tables.p, list, ptr, d->d_cn_idx.p, plan.out_slots));
+            PACK_DISPATCH(d, launch_k(tree_pass_kernel<KIND, true, PK>, grid, block, (size_t)plan.lds_bytes, d->stream, dP, bufs.msgs, bufs.cha, bufs.hard, bufs.state_w,
+                               bufs.vfail_w, d->d_ops.p, bufs.tables, list, ptr, d->d_cn_idx.p, plan.out_slots));
         else
-            PACK_DISPATCH(d, launch_k(tree_pass_kernel<KIND, false, PK>, grid, block, (size_t)plan.lds_bytes, d->stream, dP, d->d_msgs.p, d->d_cha_t.p,
-                               d->d_hard.p, reinterpret_cast<const uint32_t *>(d->d_state.p), reinterpret_cast<uint32_t *>(d->d_vfail.p),
-                               d->d_ops.p, d->d_tables.p, list, ptr, d->d_cn_idx.p, plan.out_slots));
+            PACK_DISPATCH(d, launch_k(tree_pass_kernel<KIND, false, PK>, grid, block, (size_t)plan.lds_bytes, d->stream, dP, bufs.msgs, bufs.cha, bufs.hard, bufs.state_w,
+                               bufs.vfail_w, d->d_ops.p, bufs.tables, list, ptr, d->d_cn_idx.p, plan.out_slots));
     }
     LAUNCH_CHECK();
     return LUTLDPC_OK;
@@ -162,22 +252,22 @@ static int launch_cn_minsum(lutldpc_decoder *d, int G, int nz, int check) {
     P.G = G; P.nz = nz; P.check = check; P.vfail_stride_w = d->Bcap / 4;
     std::vector<char> keep((size_t)P.n_seg, 1);
     bool any = false;
+    const PassBufs bufs = pass_bufs(d);
     if (d->opt.use_fast)
         for (int i = 0; i < P.n_seg; i++) {
+            if (!cn_minsum_shape(nz, P.seg[i].deg)) continue;
             bool ok = false;
-            FastParams FP;
-            if (!fill_cn_fast(FP, P.seg[i].deg, P.seg[i].n_nodes, d->cn_idx_off[(size_t)i], G, d->E, nz, check, d->npw_cn(P.seg[i].deg), d->Bcap / 4)) continue;
+            const ClassParams FP = cn_class_params(d, (size_t)i, {0, G}, nz, check);
+            if (int rc = check_class_launch(d, FP, i, TT_CHK, false)) return rc;
             DEV_PARAM(dFP, d, FP);
-            PACK_DISPATCH(d, ok = launch_cn_fast<PK>(d->stream, FP, dFP, d->d_msgs.p,
-                               reinterpret_cast<const uint32_t *>(d->d_state.p), reinterpret_cast<uint32_t *>(d->d_vfail.p), d->d_fast_idx.p));
+            PACK_DISPATCH(d, ok = launch_cn_fast<PK>(d->stream, FP, dFP, bufs));
             if (ok) keep[(size_t)i] = 0;
         }
     for (char k : keep) any = any || k;
     if (any) {
         P = filter_params(P, keep);
         DEV_PARAM(dP, d, P);
-        PACK_DISPATCH(d, launch_k(cn_minsum_generic_kernel<PK>, dim3((unsigned)(P.blocks_per_group * G)), dim3(64), 0, d->stream, dP, d->d_msgs.p,
-                           reinterpret_cast<const uint32_t *>(d->d_state.p), reinterpret_cast<uint32_t *>(d->d_vfail.p),
+        PACK_DISPATCH(d, launch_k(cn_minsum_generic_kernel<PK>, dim3((unsigned)(P.blocks_per_group * G)), dim3(64), 0, d->stream, dP, bufs.msgs, bufs.state_w, bufs.vfail_w,
                            d->d_cn_list.p, d->d_cn_ptr.p, d->d_cn_idx.p));
     }
     LAUNCH_CHECK();
@@ -205,7 +295,7 @@ bool late_hard_active(const lutldpc_decoder *d, bool skewed, bool *chain_skip) {
 bool chain_active(const lutldpc_decoder *d, int set) {
     if (!d->opt.use_chain || d->chain_vclass < 0 || d->n_chain_nodes == 0) return false;
     const FastClassPlan &f = d->var_fast[(size_t)set][(size_t)d->chain_vclass];
-    return f.ok && f.P.n_tables == 1 && f.P.tab_len[0] <= 1024;
+    return f.ok && f.n_tables == 1 && f.tab_len[0] <= 1024;
 }
 
 // Decided bits of the frames that left through the exit test, read off their frozen messages (hard_from_frozen_kernel) and, for
@@ -305,14 +395,13 @@ static int decode_tiles_launch(lutldpc_decoder *d, int B) {
         const int nz_in = d->Nq_Msg[(size_t)ii] / 2;
         const int chk_check = (d->psc && ii > 0) ? 1 : 0;    // finishes the test started by VN pass ii-1
         if (d->min_lut) rc = launch_cn_minsum(d, G, nz_in, chk_check);
-        else rc = launch_tree_pass<TT_CHK>(d, d->chk_plan[(size_t)set], nullptr, d->chk_jit.empty() ? nullptr : &d->chk_jit[(size_t)set], G, nz_in, chk_check, 0, LUTLDPC_K_CN_PASS,
-                                           (size_t)set < d->chk_full_tab.size() ? &d->chk_full_tab[(size_t)set] : nullptr);
+        else rc = launch_tree_pass<TT_CHK>(d, d->chk_plan[(size_t)set], set, d->chk_jit.empty() ? nullptr : &d->chk_jit[(size_t)set], G, nz_in, chk_check, 0, LUTLDPC_K_CN_PASS);
         if (rc) return rc;
         if (chk_check && (rc = launch_state(d, B, Bpad, 2, ii))) return rc;   // :327-329 returns (ii-1)+1
         if (d->trace.level > 2 && (rc = trace_dump(d))) return rc;             // :311-317
         if (ii != I - 1) {
             const int nz_out = d->Nq_Msg[(size_t)(ii + 1)] / 2;
-            rc = launch_tree_pass<TT_VAR>(d, d->var_plan[(size_t)set], &d->var_fast[(size_t)set], d->var_jit.empty() ? nullptr : &d->var_jit[(size_t)set], G, nz_out, d->psc ? 1 : 0,
+            rc = launch_tree_pass<TT_VAR>(d, d->var_plan[(size_t)set], set, d->var_jit.empty() ? nullptr : &d->var_jit[(size_t)set], G, nz_out, d->psc ? 1 : 0,
                                           (d->psc && !late_hard_active(d, false, nullptr)) ? 1 : 0, LUTLDPC_K_VN_PASS);
             if (rc) return rc;
         }
@@ -334,7 +423,7 @@ static int decode_tiles_launch(lutldpc_decoder *d, int B) {
         }
     }
     // :340-349
-    if ((rc = launch_tree_pass<TT_DEC>(d, d->dec_plan[(size_t)last_set], &d->dec_fast[(size_t)last_set], d->dec_jit.empty() ? nullptr : &d->dec_jit[(size_t)last_set], G, 0, 0, 0, LUTLDPC_K_DECISION))) return rc;
+    if ((rc = launch_tree_pass<TT_DEC>(d, d->dec_plan[(size_t)last_set], last_set, d->dec_jit.empty() ? nullptr : &d->dec_jit[(size_t)last_set], G, 0, 0, 0, LUTLDPC_K_DECISION))) return rc;
     const int fsel = skewed ? (I & 1) : 0;            // the flag buffer no pass of the skewed pipeline has written since its last test
     if ((rc = launch_syndrome(d, G, fsel))) return rc;
     if ((rc = launch_state(d, B, Bpad, 3, I, 0, -1, fsel))) return rc;

@@ -158,9 +158,9 @@ inline void emit_pass_head(std::ostringstream &o, int pack, const char *deg_name
 {
     const int tab_pad = (tab_bytes + 15) / 16 * 16;
     o << kCommonHeaderText << "\nusing namespace lutldpc;\n"
-      << "extern \"C\" __global__ __launch_bounds__(256) void lutldpc_jit_pass(const FastParams *__restrict__ Pp, uint8_t *msgs, const uint8_t *cha, uint8_t *__restrict__ hard,\n"
+      << "extern \"C\" __global__ __launch_bounds__(256) void lutldpc_jit_pass(const ClassParams *__restrict__ Pp, uint8_t *msgs, const uint8_t *cha, uint8_t *__restrict__ hard,\n"
       << "    const uint32_t *__restrict__ state_w, uint32_t *__restrict__ vfail_w, const uint8_t *__restrict__ tables, const int32_t *__restrict__ fast_idx)\n{\n"
-      << "    const FastParams &P = *Pp;\n    constexpr int PACK = " << pack << ", " << deg_name << " = " << deg << ", F = 4 * PACK, BITS = " << 8 / pack << ";\n" << unused;
+      << "    const ClassParams &P = *Pp;\n    constexpr int PACK = " << pack << ", " << deg_name << " = " << deg << ", F = 4 * PACK, BITS = " << 8 / pack << ";\n" << unused;
     if (tab_bytes <= kJitMaxLdsTable) {
         o << "    __shared__ __attribute__((aligned(16))) uint8_t tab[" << tab_pad << "];\n"
           << "    {\n        const uint32_t *src = reinterpret_cast<const uint32_t *>(tables + P.tab_off[0]);\n"

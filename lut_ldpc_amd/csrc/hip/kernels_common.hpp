@@ -16,6 +16,8 @@
 // Every global access of a wave is a single fully coalesced 256-byte row and all node / edge
 // indices are wave-uniform (scalar registers, scalar loads).
 // Per-frame state lives in byte arrays indexed by frame; a lane's frames are PACK dwords of them.
+// Also here, because hiprtc compiles this header too: ClassParams, the description of one degree class of one pass that
+// every specialised kernel -- compile-time (kernels_fast.hpp) or generated (jit.hpp) -- reads from device memory.
 #pragma once
 #ifndef __HIPCC_RTC__      // hiprtc (jit.hpp compiles this header at run time) has the HIP runtime and the fixed-width types built in
 #include <hip/hip_runtime.h>
@@ -188,23 +190,6 @@ __device__ __forceinline__ void flag_frames(uint32_t *__restrict__ vfail_w, int 
 constexpr int kFastMaxTables = 32;     // LUT nodes of one balanced tree (degree <= 33)
 constexpr int kFastTableStride = 256;  // bytes per table slot in LDS
 
-struct FastParams {
-    int32_t n_nodes, node_off, nodes_per_wave, waves_per_group;
-    int32_t idx_off;       // offset of the class in the dense index blob (see decoder.hip: build_fast_index)
-    int32_t G, E, N;
-    int32_t g0;            // first frame group of the launch (the G groups g0 .. g0+G-1 are processed)
-    int32_t nz;            // sign threshold (see PassParams)
-    int32_t shift_msg;     // log2 of the message alphabet feeding the tables (label = a | b << shift)
-    int32_t check, write_hard;
-    int32_t deg;
-    int32_t n_tables;
-    int32_t tab_off[kFastMaxTables];    // byte offsets into the table blob, canonical node order
-    int32_t tab_len[kFastMaxTables];
-    int32_t tab_shift[kFastMaxTables];  // log2 alphabet of each table's first child
-    int32_t nib;                        // (unused: nibble-packed LDS tables were measured slower and removed)
-    int32_t vfail_stride_w;             // words between two copies of the early-termination flags (see flag_frames)
-    int32_t vfail_off_w;                // word offset of the flag buffer this pass reports to (skewed pipeline: two buffers)
-};
 // chain fusion of the check pass (cn_minsum_body<..., CHAIN>): which table, which links
 struct ChainParams {
     int32_t on;            // 1: update the linked degree-2 variable nodes inside this check pass
@@ -214,6 +199,27 @@ struct ChainParams {
     // (other flag buffer); their decided bits -- the signs of the messages they sent LAST iteration -- are stored by the
     // check pass that reads those messages (hard = 1), because the variable pass skipped them
     int32_t check, hard, vfail_off_w, sbit_out;
+};
+// One degree class of one pass: what a per-class launch (decoder_stream.hip) and a role of pass_fused_kernel (decoder_skew.hip)
+// are given.  Always in DEVICE memory, read through a pointer with scalar loads; filled only by cn_class_params /
+// vn_class_params and checked against the allocations by validate_class (decoder_state.hpp).
+struct ClassParams {
+    int32_t kind;          // 0: check class, 1: variable / decision class
+    int32_t deg;
+    int32_t g0, G;         // frame groups g0 .. g0+G-1
+    int32_t n_nodes, nodes_per_wave, waves_per_group;
+    int32_t idx_off;       // offset of the class in the dense index blob (decoder_setup.hip: build_fast_index)
+    int32_t E, N;
+    int32_t nz;            // sign threshold (see PassParams)
+    int32_t shift_msg;     // log2 of the message alphabet feeding the tables (label = a | b << shift)
+    int32_t check, write_hard;
+    int32_t vfail_stride_w;             // words between two copies of the early-termination flags (see flag_frames)
+    int32_t vfail_off_w;                // word offset of the flag buffer this pass reports to (skewed pipeline: two buffers)
+    int32_t first, nidx_off;            // check pass of iteration 0 in the skewed pipeline: inputs from the initial-message rows, through the node table at nidx_off
+    ChainParams chain;                  // check classes of the skewed pipeline
+    int32_t tab_off[kFastMaxTables];    // byte offsets into the table blob, canonical node order
+    int32_t tab_len[kFastMaxTables];
+    int32_t tab_shift[kFastMaxTables];  // log2 alphabet of each table's first child
 };
 
 // (x << s) | y in one instruction, s wave-uniform

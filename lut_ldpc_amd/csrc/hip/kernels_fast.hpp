@@ -8,6 +8,8 @@
 //   * pass_fused_kernel: the check pass of one half of the frame groups and the variable pass of the
 //     other half in one launch (the skewed two-half pipeline of decoder_skew.hip).
 // Other tree shapes get kernels generated at run time (jit.hpp); kernels_generic.hpp is the fallback.
+// All of them read ONE parameter structure, ClassParams (kernels_common.hpp): a per-class launch gets a pointer to one, the
+// fused kernel a pointer to the roles of its launch.  The host launchers below take it with PassBufs, the row buffers.
 //
 // Roofline: HBM-bound streaming of 256-byte rows.  Algorithmic bytes per launch with b bytes per label:
 // check pass 2*E*b*B, variable pass (2*E + N)*b*B (+N*b*B when the hard decisions are written for the
@@ -35,7 +37,7 @@ namespace lutldpc {
 // every check of degree >= 2 (both are replaced by real magnitudes after two inputs).
 // DEG is the exact check degree (straight-line code, all row loads of UNR checks issued up front);
 // `edges` is the dense [n_nodes][DEG] table of edge ids of this degree class, read with scalar loads.
-// `block` = index of the 4-wave block within this degree class; PT = FastParams or RoleParams.
+// `block` = index of the 4-wave block within this degree class.
 // CHAIN (UNR = 1): a degree-2 variable node shared by two consecutive checks of this wave is updated here -- its two
 // incoming messages are this check's output r[0] and the previous check's output r[1], held back in `pend` -- and
 // the NEW variable-to-check messages are stored instead of the check-to-variable ones: one write and one read less per
@@ -46,13 +48,14 @@ namespace lutldpc {
 constexpr int kCnAllButOneMaxDeg = 16;     // checks up to this degree: all-but-one minima from prefix / suffix minima (registers: DEG - 2 suffixes)
 // (ABO: the largest degree that takes the all-but-one form in this instantiation -- the fused kernels of the lean degree buckets keep
 // their few wide checks on the running-minima form, whose registers do not grow with the degree)
-template <int DEG, int UNR, int PACK, bool CHAIN, typename PT, bool FIRST = false, int ABO = kCnAllButOneMaxDeg>
+template <int DEG, int UNR, int PACK, bool CHAIN, bool FIRST = false, int ABO = kCnAllButOneMaxDeg>
 __device__ __forceinline__ void cn_minsum_body(
-    const PT &P, int block, uint8_t *msgs, const uint32_t *__restrict__ state_w, uint32_t *__restrict__ vfail_w,
-    const int32_t *__restrict__ fast_idx, const ChainParams CH = ChainParams{}, uint8_t *lds_tab = nullptr,
+    const ClassParams &P, int block, uint8_t *msgs, const uint32_t *__restrict__ state_w, uint32_t *__restrict__ vfail_w,
+    const int32_t *__restrict__ fast_idx, uint8_t *lds_tab = nullptr,
     const uint8_t *cha = nullptr, const uint8_t *__restrict__ tables = nullptr, uint8_t *hard = nullptr, const uint8_t *msg0 = nullptr)
 {
     static_assert(!CHAIN || (UNR == 1 && DEG >= 2), "chain fusion: one check per step");
+    const ChainParams CH = P.chain;      // (read only where CHAIN)
     if constexpr (CHAIN) {      // the degree-2 root table (block-uniform call)
         const int i = threadIdx.x;
         if (CH.on && i < CH.tab_len / 4) reinterpret_cast<uint32_t *>(lds_tab)[i] = reinterpret_cast<const uint32_t *>(tables + CH.tab_off)[i];
@@ -165,7 +168,7 @@ __device__ __forceinline__ void cn_minsum_body(
             }
             tn = (spp ^ odd) & SB;                                            // parity of the negative inputs (bit sbit)
             uint32_t oc[DEG];
-            if constexpr (DEG == 1) oc[0] = 0u;                               // (never launched: fill_cn_fast refuses degree 1)
+            if constexpr (DEG == 1) oc[0] = 0u;                               // (never launched: cn_minsum_shape refuses degree 1)
             else if constexpr (DEG == 2) { oc[0] = mcs[1]; oc[1] = mcs[0]; }
             else {
                 uint32_t suf[DEG];
@@ -326,10 +329,10 @@ __device__ __forceinline__ void cn_minsum_body(
 
 template <int DEG, int UNR, int PACK>
 __global__ __launch_bounds__(256) void cn_minsum_fast_kernel(
-    const FastParams *__restrict__ Pp, uint8_t *__restrict__ msgs, const uint32_t *__restrict__ state_w, uint32_t *__restrict__ vfail_w,
+    const ClassParams *__restrict__ Pp, uint8_t *__restrict__ msgs, const uint32_t *__restrict__ state_w, uint32_t *__restrict__ vfail_w,
     const int32_t *__restrict__ fast_idx)
 {
-    const FastParams &P = *Pp;           // (class parameters in device memory: read with scalar loads as they are needed)
+    const ClassParams &P = *Pp;          // (class parameters in device memory: read with scalar loads as they are needed)
     cn_minsum_body<DEG, UNR, PACK, false>(P, (int)blockIdx.x, msgs, state_w, vfail_w, fast_idx);
 }
 
@@ -434,9 +437,9 @@ __device__ __forceinline__ void bal_all_nodes(const uint32_t *in, uint32_t *v, c
 // DV == 1 (VAR only): ROOT(CHA), the build's degree-1 extension.
 // `block` = index of the 4-wave block within this degree class; lds_tab: >= (NI + 1) * 256 bytes,
 // staged here by the whole block (the call must be block-uniform).
-template <int DV, int KIND, bool CHECK, int PACK, typename PT>
+template <int DV, int KIND, bool CHECK, int PACK>
 __device__ __forceinline__ void vn_balanced_body(
-    const PT &P, int block, uint8_t *lds_tab, uint8_t *msgs, const uint8_t *cha, uint8_t *__restrict__ hard,
+    const ClassParams &P, int block, uint8_t *lds_tab, uint8_t *msgs, const uint8_t *cha, uint8_t *__restrict__ hard,
     const uint32_t *__restrict__ state_w, uint32_t *__restrict__ vfail_w, const uint8_t *__restrict__ tables,
     const int32_t *__restrict__ fast_idx)
 {
@@ -573,13 +576,13 @@ __device__ __forceinline__ void vn_balanced_body(
 
 template <int DV, int KIND, bool CHECK, int PACK>
 __global__ __launch_bounds__(256) void vn_balanced_fast_kernel(
-    const FastParams *__restrict__ Pp, uint8_t *msgs, const uint8_t *cha, uint8_t *__restrict__ hard,
+    const ClassParams *__restrict__ Pp, uint8_t *msgs, const uint8_t *cha, uint8_t *__restrict__ hard,
     const uint32_t *__restrict__ state_w, uint32_t *__restrict__ vfail_w, const uint8_t *__restrict__ tables,
     const int32_t *__restrict__ fast_idx)
 {
     constexpr int NT = (KIND == TT_DEC ? DV : DV - 1) > 1 ? (KIND == TT_DEC ? DV : DV - 1) : 1;   // LUT nodes incl. root
     __shared__ __attribute__((aligned(16))) uint8_t lds_tab[NT * kFastTableStride];
-    const FastParams &P = *Pp;
+    const ClassParams &P = *Pp;
     vn_balanced_body<DV, KIND, CHECK, PACK>(P, (int)blockIdx.x, lds_tab, msgs, cha, hard, state_w, vfail_w, tables, fast_idx);
 }
 
@@ -598,8 +601,7 @@ __global__ __launch_bounds__(256) void vn_balanced_fast_kernel(
 #ifndef LUTLDPC_B0_WAVES_MAX
 #define LUTLDPC_B0_WAVES_MAX 8
 #endif
-constexpr int kFusedMaxRoles = 10;
-constexpr int kFusedMaxTables = 20;
+constexpr int kFusedMaxRoles = 10;      // degree classes of a code that runs in the fused kernel (checks + variables)
 // Degree buckets of the fused kernel.  Its register count is the maximum over all the cases it contains
 // (every degree up to the bucket limits), so codes with small degrees get their own, leaner instantiation:
 //   bucket 0: variable degrees <= 8,  check degrees <= 8   (64 VGPRs, 8 waves per SIMD)
@@ -623,33 +625,14 @@ inline int fused_bucket(int max_vn_deg, int max_cn_deg) {
 inline int fused_bucket_rank(int bucket) { for (int i = 0; i < kFusedBuckets; i++) if (kFusedBucketOrder[i] == bucket) return i; return -1; }
 inline constexpr int fused_max_cn_deg() { int m = 0; for (int b = 0; b < kFusedBuckets; b++) m = kFusedCnDeg[b] > m ? kFusedCnDeg[b] : m; return m; }
 
-struct RoleParams {
-    int32_t kind;          // 0: min-sum check class, 1: variable class
-    int32_t deg;
-    int32_t g0, G;         // frame groups g0 .. g0+G-1
-    int32_t n_nodes, nodes_per_wave, waves_per_group, idx_off;
-    int32_t E, N, nz, shift_msg, check, write_hard;
-    int32_t vfail_stride_w, vfail_off_w;
-    int32_t first, nidx_off;   // check roles of iteration 0: inputs from the initial-message rows, through the node table at nidx_off
-    ChainParams chain;     // check roles only
-    int32_t tab_off[kFusedMaxTables], tab_len[kFusedMaxTables], tab_shift[kFusedMaxTables];
-};
-// host-side staging of the roles of one launch (decoder_skew.hip builds these once per (batch shape, exit conditions) and keeps
-// them in DEVICE memory: the kernel gets a pointer, not the 3.4 KB by value)
-struct FusedParams {
-    int32_t n_roles;
-    int32_t prio;          // 1: raise the issue priority of the look-up-heavy waves (s_setprio)
-    RoleParams role[kFusedMaxRoles];
-};
-
 template <int PACK, bool CHAIN, bool FIRST, int ABO, int... Ds>
-__device__ __forceinline__ void fused_cn_switch(const RoleParams &P, int block, std::integer_sequence<int, Ds...>, uint8_t *msgs, const uint32_t *state_w,
+__device__ __forceinline__ void fused_cn_switch(const ClassParams &P, int block, std::integer_sequence<int, Ds...>, uint8_t *msgs, const uint32_t *state_w,
                                                 uint32_t *vfail_w, const int32_t *fast_idx, uint8_t *lds_tab, const uint8_t *cha, const uint8_t *tables, uint8_t *hard,
                                                 const uint8_t *msg0) {
-    ((P.deg == Ds + 2 ? (cn_minsum_body<Ds + 2, 1, PACK, CHAIN, RoleParams, FIRST, ABO>(P, block, msgs, state_w, vfail_w, fast_idx, P.chain, lds_tab, cha, tables, hard, msg0), 0) : 0), ...);
+    ((P.deg == Ds + 2 ? (cn_minsum_body<Ds + 2, 1, PACK, CHAIN, FIRST, ABO>(P, block, msgs, state_w, vfail_w, fast_idx, lds_tab, cha, tables, hard, msg0), 0) : 0), ...);
 }
 template <int PACK, bool CHECK, int... Ds>
-__device__ __forceinline__ void fused_vn_switch(const RoleParams &P, int block, std::integer_sequence<int, Ds...>, uint8_t *lds_tab, uint8_t *msgs,
+__device__ __forceinline__ void fused_vn_switch(const ClassParams &P, int block, std::integer_sequence<int, Ds...>, uint8_t *lds_tab, uint8_t *msgs,
                                                 const uint8_t *cha, uint8_t *hard, const uint32_t *state_w, uint32_t *vfail_w, const uint8_t *tables,
                                                 const int32_t *fast_idx) {
     ((P.deg == Ds + 1 ? (vn_balanced_body<Ds + 1, TT_VAR, CHECK, PACK>(P, block, lds_tab, msgs, cha, hard, state_w, vfail_w, tables, fast_idx), 0) : 0), ...);
@@ -660,7 +643,7 @@ __device__ __forceinline__ void fused_vn_switch(const RoleParams &P, int block, 
 // loads as they are needed).  The kernel-argument segment stays a handful of pointers.
 template <int PACK, bool CHECK, int BUCKET>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((BUCKET == 0 || BUCKET == 3) ? LUTLDPC_B0_WAVES_MIN : BUCKET == 1 ? 4 : 3, (BUCKET == 0 || BUCKET == 3) ? LUTLDPC_B0_WAVES_MAX : 8))) void pass_fused_kernel(
-    const RoleParams *__restrict__ roles, const int2 *__restrict__ items, int prio, uint8_t *msgs, const uint8_t *cha, uint8_t *__restrict__ hard,
+    const ClassParams *__restrict__ roles, const int2 *__restrict__ items, int prio, uint8_t *msgs, const uint8_t *cha, uint8_t *__restrict__ hard,
     const uint32_t *__restrict__ state_w, uint32_t *__restrict__ vfail_w, const uint8_t *__restrict__ tables, const int32_t *__restrict__ fast_idx,
     const uint8_t *__restrict__ msg0)
 {
@@ -668,7 +651,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((BUCKET == 
     __shared__ __attribute__((aligned(16))) uint8_t lds_tab[MAXVN * kFastTableStride];
     const int2 it = items[blockIdx.x];
     const int r = __builtin_amdgcn_readfirstlane(it.x), rb = __builtin_amdgcn_readfirstlane(it.y);
-    const RoleParams &P = roles[r];
+    const ClassParams &P = roles[r];
     if (prio && P.kind) {                          // LUT-heavy waves first: they are the long ones
         if (P.deg >= 4) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(1);
     }
@@ -733,14 +716,16 @@ inline bool match_balanced(const Tree &t, int kind, int d, std::vector<const Tre
 
 inline bool is_pow2(int x) { return x > 0 && (x & (x - 1)) == 0; }
 
-// Per-class plan of a fast variable/decision pass (filled at create time)
+// Per-class plan of a fast variable/decision pass (filled at create time): the tree has the balanced shape, and where its
+// tables sit (canonical node order).  vn_class_params copies them into the ClassParams of a launch.
 struct FastClassPlan {
     bool ok = false;
-    FastParams P{};
+    int n_tables = 0, shift_msg = 0;
+    int32_t tab_off[kFastMaxTables] = {}, tab_len[kFastMaxTables] = {}, tab_shift[kFastMaxTables] = {};
 };
 
 // tab_of: LUT node -> (offset in the global blob, length)
-inline FastClassPlan plan_fast_vn(const Tree &t, int kind, int d, const std::map<const TreeNode *, std::pair<uint32_t, uint32_t>> &tab_of, int node_off, int n_nodes) {
+inline FastClassPlan plan_fast_vn(const Tree &t, int kind, int d, const std::map<const TreeNode *, std::pair<uint32_t, uint32_t>> &tab_of) {
     FastClassPlan fp;
     std::vector<const TreeNode *> canon;
     if (d < 1 || d > 20 || !match_balanced(t, kind, d, canon) || (int)canon.size() > kFastMaxTables) return fp;
@@ -756,83 +741,62 @@ inline FastClassPlan plan_fast_vn(const Tree &t, int kind, int d, const std::map
             if (nd->child[0]->K != nd->child[1]->K) return fp;
             if (shift_msg < 0) shift_msg = sh0; else if (shift_msg != sh0) return fp;
         }
-        fp.P.tab_off[j] = (int32_t)it->second.first;
-        fp.P.tab_len[j] = (int32_t)it->second.second;
-        fp.P.tab_shift[j] = sh0;
+        fp.tab_off[j] = (int32_t)it->second.first;
+        fp.tab_len[j] = (int32_t)it->second.second;
+        fp.tab_shift[j] = sh0;
     }
-    fp.P.shift_msg = shift_msg < 0 ? 0 : shift_msg;
-    fp.P.n_tables = (int)canon.size();
-    fp.P.nib = 0;      // nibble-packed LDS tables (lut4<true>): conflict-free but measured slower on MI355X, not instantiated
-    fp.P.deg = d; fp.P.node_off = node_off; fp.P.n_nodes = n_nodes;
+    fp.shift_msg = shift_msg < 0 ? 0 : shift_msg;
+    fp.n_tables = (int)canon.size();
     fp.ok = true;
     return fp;
 }
 
 // ------------------------------------------------------------------------------------------
 // Host-side launchers.  They are ordinary (non-inline) function templates, explicitly instantiated in
-// their own translation units (fast_vn_var.hip, fast_vn_dec.hip, fast_cn.hip, fused.hip) so that the
+// their own translation units (fast_vn_var_p*.hip, fast_vn_dec.hip, fast_cn.hip, fused_b*.hip) so that the
 // ~250 kernel instantiations compile in parallel; the decoder units see `extern template` declarations (decoder_state.hpp).
+// Each takes the class parameters P (complete: cn_class_params / vn_class_params), dP = their copy in device memory, and the
+// row buffers; it returns false when the degree has no instantiation.
 constexpr int kFastMaxDeg = 20;      // variable / decision nodes
 constexpr int kFastMaxCnDeg = 32;    // check nodes
 
-template <int KIND, bool CHECK, int PACK, int DV>
-void launch_vn_fast_one(hipStream_t s, const FastParams &P, const FastParams *dP, uint8_t *msgs, const uint8_t *cha, uint8_t *hard, const uint32_t *state_w,
-                        uint32_t *vfail_w, const uint8_t *tables, const int32_t *fast_idx) {
-    const int waves = P.waves_per_group * P.G;
-    launch_k(vn_balanced_fast_kernel<DV, KIND, CHECK, PACK>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, dP, msgs, cha, hard, state_w, vfail_w,
-             tables, fast_idx);
-}
+// the min-sum check kernels take: a sign BIT (power-of-two nz) in a magnitude field of at most 6 bits, degrees 2 .. kFastMaxCnDeg
+inline bool cn_minsum_shape(int nz, int deg) { return is_pow2(nz) && nz <= 64 && deg >= 2 && deg <= kFastMaxCnDeg; }
+
+// what every pass launcher is handed besides its class parameters (host side only: unpacked into the kernels' argument lists)
+struct PassBufs {
+    uint8_t *msgs; const uint8_t *cha; uint8_t *hard;
+    const uint32_t *state_w; uint32_t *vfail_w;
+    const uint8_t *tables; const int32_t *fast_idx; const uint8_t *msg0;
+};
+inline unsigned class_blocks(const ClassParams &P) { return (unsigned)((P.waves_per_group * P.G + 3) / 4); }      // 4-wave blocks of one class
 
 template <int KIND, bool CHECK, int PACK, int... DVs>
-bool dispatch_vn_fast(int deg, std::integer_sequence<int, DVs...>, hipStream_t s, const FastParams &P, const FastParams *dP, uint8_t *msgs, const uint8_t *cha,
-                      uint8_t *hard, const uint32_t *state_w, uint32_t *vfail_w, const uint8_t *tables, const int32_t *fast_idx) {
+bool dispatch_vn_fast(std::integer_sequence<int, DVs...>, hipStream_t s, const ClassParams &P, const ClassParams *dP, const PassBufs &B) {
     bool done = false;
-    ((deg == DVs + 1 ? (launch_vn_fast_one<KIND, CHECK, PACK, DVs + 1>(s, P, dP, msgs, cha, hard, state_w, vfail_w, tables, fast_idx), done = true) : false), ...);
+    ((P.deg == DVs + 1 ? (launch_k(vn_balanced_fast_kernel<DVs + 1, KIND, CHECK, PACK>, dim3(class_blocks(P)), dim3(256), 0, s, dP, B.msgs, B.cha, B.hard, B.state_w,
+                                   B.vfail_w, B.tables, B.fast_idx), done = true) : false), ...);
     return done;
-}
-
-// launch one class; returns false when the degree has no instantiation.  P is complete (fill_vn_fast), dP its copy in device memory.
-inline void fill_vn_fast(FastParams &P, int G, int nz, int check, int write_hard, int nodes_per_wave, int E, int N, int vfail_stride_w) {
-    P.vfail_stride_w = vfail_stride_w;
-    P.G = G; P.E = E; P.N = N; P.nz = nz; P.check = check; P.write_hard = write_hard;
-    P.nodes_per_wave = nodes_per_wave;
-    P.waves_per_group = (P.n_nodes + nodes_per_wave - 1) / nodes_per_wave;
 }
 template <int KIND, int PACK>
-bool launch_vn_fast(hipStream_t s, const FastParams &P, const FastParams *dP, uint8_t *msgs, const uint8_t *cha,
-                    uint8_t *hard, const uint32_t *state_w, uint32_t *vfail_w, const uint8_t *tables, const int32_t *fast_idx) {
+bool launch_vn_fast(hipStream_t s, const ClassParams &P, const ClassParams *dP, const PassBufs &B) {
     constexpr auto seq = std::make_integer_sequence<int, kFastMaxDeg>{};
-    if (KIND == TT_VAR && P.check) return dispatch_vn_fast<KIND, true, PACK>(P.deg, seq, s, P, dP, msgs, cha, hard, state_w, vfail_w, tables, fast_idx);
-    return dispatch_vn_fast<KIND, false, PACK>(P.deg, seq, s, P, dP, msgs, cha, hard, state_w, vfail_w, tables, fast_idx);
+    if (KIND == TT_VAR && P.check) return dispatch_vn_fast<KIND, true, PACK>(seq, s, P, dP, B);
+    return dispatch_vn_fast<KIND, false, PACK>(seq, s, P, dP, B);
 }
 
-template <int PACK, int DEG>
-void launch_cn_fast_one(hipStream_t s, const FastParams &P, const FastParams *dP, uint8_t *msgs, const uint32_t *state_w, uint32_t *vfail_w, const int32_t *fast_idx) {
-    // checks evaluated per pipeline step: more = more loads outstanding per wave, fewer = fewer VGPRs = more waves
-    constexpr int UNR = DEG <= 4 ? 4 : DEG <= 10 ? 2 : 1;
-    const int waves = P.waves_per_group * P.G;
-    launch_k(cn_minsum_fast_kernel<DEG, UNR, PACK>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, dP, msgs, state_w, vfail_w, fast_idx);
-}
+// checks evaluated per pipeline step: more = more loads outstanding per wave, fewer = fewer VGPRs = more waves
+constexpr int cn_unroll(int deg) { return deg <= 4 ? 4 : deg <= 10 ? 2 : 1; }
 template <int PACK, int... Ds>
-bool dispatch_cn_fast(int deg, std::integer_sequence<int, Ds...>, hipStream_t s, const FastParams &P, const FastParams *dP, uint8_t *msgs, const uint32_t *state_w,
-                      uint32_t *vfail_w, const int32_t *fast_idx) {
+bool dispatch_cn_fast(std::integer_sequence<int, Ds...>, hipStream_t s, const ClassParams &P, const ClassParams *dP, const PassBufs &B) {
     bool done = false;
-    ((deg == Ds + 1 ? (launch_cn_fast_one<PACK, Ds + 1>(s, P, dP, msgs, state_w, vfail_w, fast_idx), done = true) : false), ...);
+    ((P.deg == Ds + 1 ? (launch_k(cn_minsum_fast_kernel<Ds + 1, cn_unroll(Ds + 1), PACK>, dim3(class_blocks(P)), dim3(256), 0, s, dP, B.msgs, B.state_w, B.vfail_w, B.fast_idx), done = true) : false), ...);
     return done;
 }
-
-// min-sum: one launch per degree class (P from fill_cn_fast, dP its copy in device memory)
-inline bool fill_cn_fast(FastParams &P, int deg, int n_nodes, int idx_off, int G, int E, int nz, int check, int nodes_per_wave, int vfail_stride_w) {
-    if (!is_pow2(nz) || nz > 64 || deg < 2 || deg > kFastMaxCnDeg) return false;
-    P = FastParams{};
-    P.n_nodes = n_nodes; P.idx_off = idx_off; P.G = G; P.E = E; P.nz = nz; P.check = check; P.deg = deg; P.vfail_stride_w = vfail_stride_w;
-    P.nodes_per_wave = nodes_per_wave;
-    P.waves_per_group = (n_nodes + nodes_per_wave - 1) / nodes_per_wave;
-    return true;
-}
+// min-sum: one launch per degree class
 template <int PACK>
-bool launch_cn_fast(hipStream_t s, const FastParams &P, const FastParams *dP, uint8_t *msgs, const uint32_t *state_w, uint32_t *vfail_w, const int32_t *fast_idx) {
-    return dispatch_cn_fast<PACK>(P.deg, std::make_integer_sequence<int, kFastMaxCnDeg>{}, s, P, dP, msgs, state_w, vfail_w, fast_idx);
+bool launch_cn_fast(hipStream_t s, const ClassParams &P, const ClassParams *dP, const PassBufs &B) {
+    return dispatch_cn_fast<PACK>(std::make_integer_sequence<int, kFastMaxCnDeg>{}, s, P, dP, B);
 }
 
 // code-object preload of the per-class translation units (see preload_fused)
@@ -848,15 +812,15 @@ hipError_t preload_cn_fast() {
 }
 
 // skewed pipeline: one launch of pass_fused_kernel over n_blocks items
+template <int PACK, bool CHECK, int BUCKET>
+void launch_fused_one(hipStream_t s, const ClassParams *d_roles, const int32_t *items, int n_blocks, int prio, const PassBufs &B) {
+    launch_k(pass_fused_kernel<PACK, CHECK, BUCKET>, dim3((unsigned)n_blocks), dim3(256), 0, s, d_roles, reinterpret_cast<const int2 *>(items), prio, B.msgs, B.cha, B.hard,
+             B.state_w, B.vfail_w, B.tables, B.fast_idx, B.msg0);
+}
 template <int PACK, int BUCKET>
-void launch_fused(hipStream_t s, const RoleParams *d_roles, const int32_t *items, int n_blocks, int prio, bool vn_check, uint8_t *msgs, const uint8_t *cha, uint8_t *hard,
-                  const uint32_t *state_w, uint32_t *vfail_w, const uint8_t *tables, const int32_t *fast_idx, const uint8_t *msg0) {
-    if (vn_check)
-        launch_k(pass_fused_kernel<PACK, true, BUCKET>, dim3((unsigned)n_blocks), dim3(256), 0, s, d_roles, reinterpret_cast<const int2 *>(items), prio, msgs, cha, hard,
-                 state_w, vfail_w, tables, fast_idx, msg0);
-    else
-        launch_k(pass_fused_kernel<PACK, false, BUCKET>, dim3((unsigned)n_blocks), dim3(256), 0, s, d_roles, reinterpret_cast<const int2 *>(items), prio, msgs, cha, hard,
-                 state_w, vfail_w, tables, fast_idx, msg0);
+void launch_fused(hipStream_t s, const ClassParams *d_roles, const int32_t *items, int n_blocks, int prio, bool vn_check, const PassBufs &B) {
+    if (vn_check) launch_fused_one<PACK, true, BUCKET>(s, d_roles, items, n_blocks, prio, B);
+    else launch_fused_one<PACK, false, BUCKET>(s, d_roles, items, n_blocks, prio, B);
 }
 // force the code object of this translation unit onto the current device now (HIP loads code objects lazily, at the first
 // launch of one of their kernels): decoder_setup.hip calls these at decoder creation, see preload_code_objects
@@ -866,14 +830,12 @@ hipError_t preload_fused() {
     return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&pass_fused_kernel<PACK, false, BUCKET>));
 }
 
-#define LUTLDPC_FUSED_SIG (hipStream_t, const RoleParams *, const int32_t *, int, int, bool, uint8_t *, const uint8_t *, uint8_t *, const uint32_t *, uint32_t *, const uint8_t *, const int32_t *, const uint8_t *)
+#define LUTLDPC_CLASS_SIG (hipStream_t, const ClassParams &, const ClassParams *, const PassBufs &)
+#define LUTLDPC_FUSED_SIG (hipStream_t, const ClassParams *, const int32_t *, int, int, bool, const PassBufs &)
 #define LUTLDPC_FAST_LAUNCHERS(X)                                                                                                           \
-    X template bool launch_vn_fast<TT_VAR, 1>(hipStream_t, const FastParams &, const FastParams *, uint8_t *, const uint8_t *, uint8_t *, const uint32_t *, uint32_t *, const uint8_t *, const int32_t *); \
-    X template bool launch_vn_fast<TT_VAR, 2>(hipStream_t, const FastParams &, const FastParams *, uint8_t *, const uint8_t *, uint8_t *, const uint32_t *, uint32_t *, const uint8_t *, const int32_t *); \
-    X template bool launch_vn_fast<TT_DEC, 1>(hipStream_t, const FastParams &, const FastParams *, uint8_t *, const uint8_t *, uint8_t *, const uint32_t *, uint32_t *, const uint8_t *, const int32_t *); \
-    X template bool launch_vn_fast<TT_DEC, 2>(hipStream_t, const FastParams &, const FastParams *, uint8_t *, const uint8_t *, uint8_t *, const uint32_t *, uint32_t *, const uint8_t *, const int32_t *); \
-    X template bool launch_cn_fast<1>(hipStream_t, const FastParams &, const FastParams *, uint8_t *, const uint32_t *, uint32_t *, const int32_t *);    \
-    X template bool launch_cn_fast<2>(hipStream_t, const FastParams &, const FastParams *, uint8_t *, const uint32_t *, uint32_t *, const int32_t *);    \
+    X template bool launch_vn_fast<TT_VAR, 1> LUTLDPC_CLASS_SIG; X template bool launch_vn_fast<TT_VAR, 2> LUTLDPC_CLASS_SIG; \
+    X template bool launch_vn_fast<TT_DEC, 1> LUTLDPC_CLASS_SIG; X template bool launch_vn_fast<TT_DEC, 2> LUTLDPC_CLASS_SIG; \
+    X template bool launch_cn_fast<1> LUTLDPC_CLASS_SIG; X template bool launch_cn_fast<2> LUTLDPC_CLASS_SIG; \
     X template void launch_fused<1, 0> LUTLDPC_FUSED_SIG; X template void launch_fused<2, 0> LUTLDPC_FUSED_SIG; \
     X template void launch_fused<1, 1> LUTLDPC_FUSED_SIG; X template void launch_fused<2, 1> LUTLDPC_FUSED_SIG; \
     X template void launch_fused<1, 2> LUTLDPC_FUSED_SIG; X template void launch_fused<2, 2> LUTLDPC_FUSED_SIG; \

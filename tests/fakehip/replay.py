@@ -87,6 +87,9 @@ def scenarios(which):
         run("n500_q4_i8", 300, 1.8, {"LUTLDPC_PACK": "1"}, [(True, True), (False, False)])
         run("n500_q4_i8", 1100, 1.8, {}, all3, repeats=3, with_oracle=False)
         run("n500_q4_i8", 1100, 1.8, {"LUTLDPC_VALIDATE": "1"}, all3, with_oracle=False)
+        # the validator in front of the per-class and the generated-kernel launches (no fused pipeline)
+        for name, B, snr in [("n500_q4", 300, 1.8), ("reg36_n1000_high", 33, 2.0)]:
+            run(name, B, snr, {"LUTLDPC_VALIDATE": "1", "LUTLDPC_SKEW": "0"}, [(True, True), (False, False)])
         run("reg36_n1000_mixed", 1025, 2.2, {"LUTLDPC_COMPACT": "1", "LUTLDPC_COMPACT_FIRST": "2", "LUTLDPC_COMPACT_EVERY": "1", "LUTLDPC_COMPACT_MARGIN": "0"}, all3, repeats=3, with_oracle=False)
         run("c5_chklut", 20, 4.2, {}, [(True, True)])
         run("dvbs2_q4_i6", 1030, 1.0, {}, [(True, True), (False, False)], repeats=3, with_oracle=False)

@@ -54,9 +54,10 @@ def test_kernel_paths_agree_at_full_iteration_count(name, snr, monkeypatch):
 
 
 @pytest.mark.parametrize("name,B,snr", [("n500_q4", 300, 1.8), ("reg36_n1000_mixed", 64, 2.2), ("c5_chklut", 20, 4.2), ("reg36_n1000_high", 33, 2.0)])
-@pytest.mark.parametrize("env", [{"LUTLDPC_PACK": "1"}, {"LUTLDPC_USE_FAST": "0"}, {"LUTLDPC_PACK": "1", "LUTLDPC_USE_FAST": "0"}])
+@pytest.mark.parametrize("env", [{"LUTLDPC_PACK": "1"}, {"LUTLDPC_USE_FAST": "0"}, {"LUTLDPC_PACK": "1", "LUTLDPC_USE_FAST": "0"}, {"LUTLDPC_VALIDATE": "1"}])
 def test_kernel_variants(name, B, snr, env, monkeypatch):
-    """Byte rows vs nibble rows, specialised vs generic kernels: every combination is bit-exact."""
+    """Byte rows vs nibble rows, specialised vs generic kernels, the validating debug mode (every class's parameters checked
+    against the allocation sizes before its launch): every combination is bit-exact."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     cd = oracle_codec(name)
@@ -71,10 +72,12 @@ def test_kernel_variants(name, B, snr, env, monkeypatch):
 
 
 @pytest.mark.parametrize("name,B,snr", [("n500_q4", 1100, 1.6), ("reg36_n1000_q4", 1537, 2.0), ("reg36_n1000_mixed", 1025, 2.2)])
-@pytest.mark.parametrize("env", [{"LUTLDPC_PACK": "1"}, {"LUTLDPC_SKEW": "0"}, {"LUTLDPC_VALIDATE": "1"}, {"LUTLDPC_LATE_HARD": "0"}, {"LUTLDPC_FIRST_FROM_NODES": "0"}])
+@pytest.mark.parametrize("env", [{"LUTLDPC_PACK": "1"}, {"LUTLDPC_SKEW": "0"}, {"LUTLDPC_VALIDATE": "1"}, {"LUTLDPC_LATE_HARD": "0"}, {"LUTLDPC_FIRST_FROM_NODES": "0"},
+                                 {"LUTLDPC_VALIDATE": "1", "LUTLDPC_SKEW": "0"}])
 def test_skewed_pipeline_variants(name, B, snr, env, monkeypatch):
     """Byte rows, per-class launches instead of the fused pipeline, the validating debug mode (every role checked against
-    the allocation sizes, one stream synchronisation per fused launch), and decided bits stored by every variable pass
+    the allocation sizes, one stream synchronisation per fused launch; with LUTLDPC_SKEW=0 the same check in front of every
+    per-class launch), and decided bits stored by every variable pass
     instead of recovered at the end (LUTLDPC_LATE_HARD=0), the initial messages copied to the edge rows by their own kernel
     instead of read by the first check pass (LUTLDPC_FIRST_FROM_NODES=0)."""
     for k, v in env.items():
