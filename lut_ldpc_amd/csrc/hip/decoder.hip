@@ -34,10 +34,13 @@ void make_describe(lutldpc_decoder *d) {
 #include "kernel_src_hash.inc"
       << "\",\"tile_frames\":" << d->tile() << ",\"message_bytes\":" << (d->pack == 2 ? "0.5" : "1") << ",\"pack\":" << d->pack << ",\"vector_bytes_per_lane\":4"
       << ",\"nodes_per_block\":" << d->opt.nodes_per_block << ",\"vn_edges_per_wave\":" << d->opt.vn_edges_per_wave << ",\"cn_edges_per_wave\":" << d->cn_epw() << ",\"use_fast\":" << d->opt.use_fast
+      // knobs as given (0: unset, derived per degree class -- the classes below report what is in force)
+      << ",\"nodes_per_wave\":" << d->opt.nodes_per_wave << ",\"nodes_per_wave_cn\":" << d->opt.nodes_per_wave_cn << ",\"tail_front\":" << d->opt.tail_front
+      << ",\"fused_prio\":" << d->opt.fused_prio << ",\"chk_full_labels\":" << d->opt.chk_full_labels
       << ",\"vn_classes\":[";
     for (size_t i = 0; i < d->vclass.size(); i++) {
         const bool f = !d->var_fast.empty() && i < d->var_fast[0].size() && fast_covers(d, d->var_fast[0][i], d->vclass[i].deg);
-        o << (i ? "," : "") << "{\"deg\":" << d->vclass[i].deg << ",\"nodes\":" << d->vclass[i].nodes.size() << ",\"kernel\":\""
+        o << (i ? "," : "") << "{\"deg\":" << d->vclass[i].deg << ",\"nodes\":" << d->vclass[i].nodes.size() << ",\"nodes_per_wave\":" << d->npw_vn(d->vclass[i].deg) << ",\"kernel\":\""
           << (f ? "vn_balanced_fast_kernel" : (!d->var_jit.empty() && i < d->var_jit[0].size() && d->var_jit[0][i]) ? "lutldpc_jit_pass" : "tree_pass_kernel<VAR>") << "\"}";
     }
     o << "],\"cn_classes\":[";
@@ -48,7 +51,12 @@ void make_describe(lutldpc_decoder *d) {
             n_fast += d->opt.use_fast && d->min_lut && cn_minsum_shape(nq / 2, d->cclass[i].deg);
         const char *minsum = n_fast == (int)d->Nq_Msg.size() ? "cn_minsum_fast_kernel"
                            : n_fast == 0 ? "cn_minsum_generic_kernel" : "cn_minsum_fast_kernel+cn_minsum_generic_kernel";
-        o << (i ? "," : "") << "{\"deg\":" << d->cclass[i].deg << ",\"nodes\":" << d->cclass[i].nodes.size() << ",\"kernel\":\""
+        // degree-2 nodes updated inside the check pass of this class: the forward links of its chain table (build_fast_index)
+        int chained = 0;
+        if (d->opt.use_chain && i < d->chain_idx_off.size() && d->chain_idx_off[i] >= 0)
+            for (size_t j = 0; j < d->cclass[i].nodes.size(); j++) chained += d->fast_idx[(size_t)d->chain_idx_off[i] + 2 * j + 1] != 0;
+        o << (i ? "," : "") << "{\"deg\":" << d->cclass[i].deg << ",\"nodes\":" << d->cclass[i].nodes.size() << ",\"nodes_per_wave\":" << d->npw_cn_class(i)
+          << ",\"chain_nodes\":" << chained << ",\"kernel\":\""
           << (d->min_lut ? minsum
                          : (!d->chk_jit.empty() && i < d->chk_jit[0].size() && d->chk_jit[0][i]) ? "lutldpc_jit_pass" : "tree_pass_kernel<CHK>") << "\"}";
     }

@@ -6,7 +6,7 @@ import os, pathlib, sys, tempfile
 import numpy as np
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))   # (this file lives in tests/: only tests may use the oracle)
-from helpers import awgn_labels, compare, product_decoder, write_random_alist     # noqa: E402
+from helpers import awgn_labels, compare, product_decoder, write_degree_alist, write_random_alist     # noqa: E402
 from oracle import oracle as orc                                                   # noqa: E402
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 20
@@ -16,6 +16,27 @@ BP = "--bp" in sys.argv                # the [BP] comparison decoder instead of 
 GEOM = "--resident-geom" in sys.argv   # LDS-resident decoder (the default for these code sizes) with a random workgroup geometry per case
 if COMPACT:
     os.environ["LUTLDPC_RESIDENT"] = "0"   # (compaction belongs to the streaming kernels)
+
+
+def degree_draw(r, N, M):
+    """A degree distribution for write_degree_alist: degree-3 variables, one to three guest classes of degrees 4..20, up to two guest
+    check classes of degrees 2..32, the remaining edges dealt evenly to the other checks.  None where that leaves the kernels' range."""
+    vdeg = {3: N}
+    for d in r.choice(np.arange(4, 21), size=int(r.integers(1, 4)), replace=False):
+        vdeg[int(d)] = int(r.integers(10, 40))
+    cdeg = {}
+    for d in r.choice(np.arange(2, 33), size=int(r.integers(0, 3)), replace=False):
+        cdeg[int(d)] = int(r.integers(5, 30))
+    rest, Mr = sum(d * n for d, n in vdeg.items()) - sum(d * n for d, n in cdeg.items()), max(M - sum(cdeg.values()), 1)
+    d0, a = rest // Mr, rest % Mr
+    if d0 < 2 or d0 + 1 > 32:
+        return None
+    for d, n in ((d0, Mr - a), (d0 + 1, a)):
+        if n:
+            cdeg[d] = cdeg.get(d, 0) + n
+    return vdeg, cdeg
+
+
 bad = 0
 for c in range(cases):
     N = int(rng.integers(200, 1600))
@@ -41,8 +62,14 @@ for c in range(cases):
     if c < int(os.environ.get("FUZZ_FROM", "0")):
         continue
     d = pathlib.Path(tempfile.mkdtemp())
+    r4 = np.random.default_rng(9000 + c)                       # one case in three: prescribed degrees on both sides, up to 20 and 32
+    deg = degree_draw(r4, N, M) if r4.integers(0, 3) == 0 and not BP else None
     try:
-        dv, dc = write_random_alist(d / "r.alist", N, M, dvc, p.tolist(), seed=1000 + c)
+        if deg:
+            dv, dc = write_degree_alist(d / "r.alist", *deg, seed=1000 + c)
+            N, M, dvc = len(dv), len(dc), sorted(deg[0])
+        else:
+            dv, dc = write_random_alist(d / "r.alist", N, M, dvc, p.tolist(), seed=1000 + c)
     except AssertionError:
         print(f"case {c}: graph generation gave up, skipped"); continue
     if dc.max() > 32 or dv.max() > 20:

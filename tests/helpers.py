@@ -136,42 +136,63 @@ def resident_variant(src):
             "waves_eu": int(waves.group(1)) if waves else 0, "U": U}
 
 
-def write_ira_alist(path, K, M, dv_info, seed=0):
-    """A dual-diagonal (IRA / DVB-S2 style) code for the tests: K information nodes of degree dv_info spread evenly over M checks
-    plus M parity nodes of degree 2 in a (tail-biting) zigzag, parity node j joining checks j and j+1.  Check degree
-    K*dv_info/M + 2.  Returns (N, M)."""
-    rng = np.random.default_rng(seed)
-    assert (K * dv_info) % M == 0
-    per = K * dv_info // M
-    sockets = np.repeat(np.arange(M), per)
-    rng.shuffle(sockets)
-    cols = sockets.reshape(K, dv_info).copy()
-    for _ in range(100):                                   # repair columns that got the same check twice by swapping sockets
-        bad = [v for v in range(K) if len(set(cols[v])) < dv_info]
+def _repair_double_edges(cols, rng, rounds=200):
+    """cols[v]: the checks of node v's sockets.  Nodes that got the same check twice swap a socket with a random other node."""
+    n = len(cols)
+    for _ in range(rounds):
+        bad = [v for v in range(n) if len(set(cols[v])) < len(cols[v])]
         if not bad:
             break
         for v in bad:
-            for k in range(1, dv_info):
+            for k in range(1, len(cols[v])):
                 if cols[v][k] in cols[v][:k]:
-                    w = int(rng.integers(K))
-                    j = int(rng.integers(dv_info))
+                    w = int(rng.integers(n))
+                    j = int(rng.integers(len(cols[w])))
                     if cols[w][j] not in cols[v] and cols[v][k] not in cols[w]:
                         cols[v][k], cols[w][j] = cols[w][j], cols[v][k]
-    assert all(len(set(c)) == dv_info for c in cols)
-    col_rows = [sorted(int(r) for r in c) for c in cols] + [sorted({j, (j + 1) % M}) for j in range(M)]
-    N = K + M
+    assert all(len(set(c)) == len(c) for c in cols)
+
+
+def _write_alist(path, col_rows, M):
+    """col_rows[v]: the sorted checks of node v.  Returns the check degrees."""
     row_cols = [[] for _ in range(M)]
     for v, rows in enumerate(col_rows):
         for r in rows:
             row_cols[r].append(v)
     with open(path, "w") as f:
-        f.write(f"{N} {M}\n{max(len(c) for c in col_rows)} {max(len(r) for r in row_cols)}\n")
+        f.write(f"{len(col_rows)} {M}\n{max(len(c) for c in col_rows)} {max(len(r) for r in row_cols)}\n")
         f.write(" ".join(str(len(c)) for c in col_rows) + "\n" + " ".join(str(len(r)) for r in row_cols) + "\n")
         for c in col_rows:
             f.write(" ".join(str(r + 1) for r in c) + "\n")
         for r in row_cols:
             f.write(" ".join(str(v + 1) for v in sorted(r)) + "\n")
-    return N, M
+    return np.array([len(r) for r in row_cols])
+
+
+def write_zigzag_runs_alist(path, runs, dv_info, seed=0):
+    """A dual-diagonal (IRA / DVB-S2 style) code for the tests: information nodes of degree dv_info dealt to the information sockets
+    of the checks, plus one parity node of degree 2 per check in a (tail-biting) zigzag, parity node j joining checks j and j+1.
+    runs = [(checks, information sockets per check), ...]: the zigzag passes through contiguous runs of checks of degree
+    sockets + 2, so every degree class holds neighbours of the zigzag.  Returns (N, M)."""
+    rng = np.random.default_rng(seed)
+    per = np.concatenate([np.full(n, s, int) for n, s in runs])
+    M = len(per)
+    assert per.sum() % dv_info == 0
+    K = int(per.sum()) // dv_info
+    sockets = np.repeat(np.arange(M), per)
+    rng.shuffle(sockets)
+    cols = [list(c) for c in sockets.reshape(K, dv_info)]
+    _repair_double_edges(cols, rng)
+    col_rows = [sorted(int(r) for r in c) for c in cols] + [sorted({j, (j + 1) % M}) for j in range(M)]
+    _write_alist(path, col_rows, M)
+    return K + M, M
+
+
+def write_ira_alist(path, K, M, dv_info, seed=0):
+    """The zigzag code with one run: K information nodes of degree dv_info spread evenly over M checks, check degree
+    K*dv_info/M + 2.  Returns (N, M)."""
+    assert (K * dv_info) % M == 0
+    return write_zigzag_runs_alist(path, [(M, K * dv_info // M)], dv_info, seed)
 
 
 def write_random_alist(path, N, M, dv_choices, dv_probs, seed=0):
@@ -185,28 +206,25 @@ def write_random_alist(path, N, M, dv_choices, dv_probs, seed=0):
     rng.shuffle(sockets)
     ptr = np.concatenate([[0], np.cumsum(dv)])
     cols = [list(sockets[ptr[v]:ptr[v + 1]]) for v in range(N)]
-    for _ in range(200):
-        bad = [v for v in range(N) if len(set(cols[v])) < len(cols[v])]
-        if not bad:
-            break
-        for v in bad:
-            for k in range(1, len(cols[v])):
-                if cols[v][k] in cols[v][:k]:
-                    w = int(rng.integers(N)); j = int(rng.integers(len(cols[w])))
-                    if cols[w][j] not in cols[v] and cols[v][k] not in cols[w]:
-                        cols[v][k], cols[w][j] = cols[w][j], cols[v][k]
-    assert all(len(set(c)) == len(c) for c in cols)
-    col_rows = [sorted(int(r) for r in c) for c in cols]
-    row_cols = [[] for _ in range(M)]
-    for v, rows in enumerate(col_rows):
-        for r in rows:
-            row_cols[r].append(v)
-    assert min(len(r) for r in row_cols) >= 2
-    with open(path, "w") as f:
-        f.write(f"{N} {M}\n{max(len(c) for c in col_rows)} {max(len(r) for r in row_cols)}\n")
-        f.write(" ".join(str(len(c)) for c in col_rows) + "\n" + " ".join(str(len(r)) for r in row_cols) + "\n")
-        for c in col_rows:
-            f.write(" ".join(str(r + 1) for r in c) + "\n")
-        for r in row_cols:
-            f.write(" ".join(str(v + 1) for v in sorted(r)) + "\n")
-    return dv, np.array([len(r) for r in row_cols])
+    _repair_double_edges(cols, rng)
+    dc = _write_alist(path, [sorted(int(r) for r in c) for c in cols], M)
+    assert dc.min() >= 2
+    return dv, dc
+
+
+def write_degree_alist(path, vdeg, cdeg, seed=0):
+    """A configuration-model code with a prescribed degree distribution on both sides: vdeg / cdeg map a degree to the number of
+    variable / check nodes that have it (equal edge totals).  Nodes are numbered by ascending degree; double edges repaired by
+    swapping sockets.  Returns (dv, dc) as arrays."""
+    rng = np.random.default_rng(seed)
+    dv = np.concatenate([np.full(n, d, int) for d, n in sorted(vdeg.items())])
+    dc = np.concatenate([np.full(n, d, int) for d, n in sorted(cdeg.items())])
+    assert dv.sum() == dc.sum(), (int(dv.sum()), int(dc.sum()))
+    sockets = np.repeat(np.arange(len(dc)), dc)
+    rng.shuffle(sockets)
+    ptr = np.concatenate([[0], np.cumsum(dv)])
+    cols = [list(sockets[ptr[v]:ptr[v + 1]]) for v in range(len(dv))]
+    _repair_double_edges(cols, rng)
+    got = _write_alist(path, [sorted(int(r) for r in c) for c in cols], len(dc))
+    assert (got == dc).all()
+    return dv, dc

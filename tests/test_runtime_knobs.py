@@ -27,6 +27,10 @@ def test_defaults(clean_env):
     assert d["compaction"] == 2                                   # automatic
     assert d["vn_edges_per_wave"] == 16 and d["cn_edges_per_wave"] == 42 and d["nodes_per_block"] == 16
     assert d["resident"] == 0                                     # never on a host-only handle
+    assert d["nodes_per_wave"] == 0 and d["nodes_per_wave_cn"] == 0      # unset: derived per class from the edges per wave
+    assert d["tail_front"] == 0.25 and d["fused_prio"] == 0 and d["chk_full_labels"] == 1
+    assert [(c["deg"], c["nodes_per_wave"]) for c in d["vn_classes"]] == [(2, 8), (3, 5), (9, 1), (17, 1)]
+    assert [(c["deg"], c["nodes_per_wave"], c["chain_nodes"]) for c in d["cn_classes"]] == [(8, 5, 0), (9, 4, 0), (10, 4, 0)]
 
 
 @pytest.mark.parametrize("var,value,field,want", [
@@ -44,13 +48,43 @@ def test_defaults(clean_env):
     ("LUTLDPC_CN_EDGES_PER_WAVE", "24", "cn_edges_per_wave", 24),
     ("LUTLDPC_NODES_PER_BLOCK", "8", "nodes_per_block", 8),
     ("LUTLDPC_NODES_PER_BLOCK", "5000", "nodes_per_block", 16),
+    ("LUTLDPC_NODES_PER_WAVE", "3", "nodes_per_wave", 3),
+    ("LUTLDPC_NODES_PER_WAVE", "3", "nodes_per_wave_cn", 3),         # the check side follows unless it has a value of its own
+    ("LUTLDPC_NODES_PER_WAVE", "4097", "nodes_per_wave", 0),
+    ("LUTLDPC_NODES_PER_WAVE_CN", "2", "nodes_per_wave_cn", 2),
+    ("LUTLDPC_NODES_PER_WAVE_CN", "2", "nodes_per_wave", 0),
+    ("LUTLDPC_TAIL_FRONT", "0", "tail_front", 0),
+    ("LUTLDPC_TAIL_FRONT", "0.89", "tail_front", 0.89),
+    ("LUTLDPC_TAIL_FRONT", "0.9", "tail_front", 0.25),               # the upper limit is exclusive
+    ("LUTLDPC_PRIO", "1", "fused_prio", 1),
+    ("LUTLDPC_CHK_FULL", "0", "chk_full_labels", 0),
 ])
 def test_knob_is_reflected_in_describe(clean_env, var, value, field, want):
     clean_env.setenv(var, value)
     assert _describe()[field] == want
 
 
+def test_nodes_per_wave_in_force(clean_env):
+    """The classes report what the knobs make of them: a fixed count on both sides, on the check side alone, from the edges per wave."""
+    clean_env.setenv("LUTLDPC_NODES_PER_WAVE", "3")
+    d = _describe()
+    assert {c["nodes_per_wave"] for c in d["vn_classes"] + d["cn_classes"]} == {3}
+    clean_env.setenv("LUTLDPC_NODES_PER_WAVE_CN", "2")
+    d = _describe()
+    assert {c["nodes_per_wave"] for c in d["vn_classes"]} == {3} and {c["nodes_per_wave"] for c in d["cn_classes"]} == {2}
+    clean_env.delenv("LUTLDPC_NODES_PER_WAVE")
+    clean_env.delenv("LUTLDPC_NODES_PER_WAVE_CN")
+    clean_env.setenv("LUTLDPC_CN_EDGES_PER_WAVE", "24")
+    assert [c["nodes_per_wave"] for c in _describe()["cn_classes"]] == [3, 2, 2]
+
+
 def test_chain_fusion_switch(clean_env):
-    assert _describe("dvbs2_q4_i6")["chain_nodes"] > 0
+    """DVB-S2: the one chain-rich class (degree 7, the zigzag) runs twelve checks per wave and holds every chained node."""
+    d = _describe("dvbs2_q4_i6")
+    assert d["chain_nodes"] > 0 and sum(c["chain_nodes"] for c in d["cn_classes"]) == d["chain_nodes"]
+    rich = max(d["cn_classes"], key=lambda c: c["chain_nodes"])
+    assert rich["nodes_per_wave"] == 12 and rich["chain_nodes"] >= 0.9 * rich["nodes"], rich
     clean_env.setenv("LUTLDPC_CHAIN", "0")
-    assert _describe("dvbs2_q4_i6")["chain_nodes"] == 0
+    d = _describe("dvbs2_q4_i6")
+    assert d["chain_nodes"] == 0 and not any(c["chain_nodes"] for c in d["cn_classes"])
+    assert all(c["nodes_per_wave"] == 42 // c["deg"] for c in d["cn_classes"])
