@@ -28,6 +28,16 @@ void prof_fold(lutldpc_decoder *d) {
     d->ev_live.clear();
 }
 
+// CRC-32 (IEEE, reflected), chainable: crc32(crc32(0, a), b) = crc32 of a followed by b
+static uint32_t crc32(uint32_t crc, const void *p, size_t n) {
+    crc = ~crc;
+    for (size_t i = 0; i < n; i++) {
+        crc ^= static_cast<const uint8_t *>(p)[i];
+        for (int k = 0; k < 8; k++) crc = (crc >> 1) ^ (0xEDB88320u & (0u - (crc & 1u)));
+    }
+    return ~crc;
+}
+
 void make_describe(lutldpc_decoder *d) {
     std::ostringstream o;
     o << "{\"build\":\"" << __DATE__ << " " << __TIME__ << "\",\"kernel_sources\":\"" <<
@@ -39,9 +49,10 @@ void make_describe(lutldpc_decoder *d) {
       << ",\"fused_prio\":" << d->opt.fused_prio << ",\"chk_full_labels\":" << d->opt.chk_full_labels
       << ",\"vn_classes\":[";
     for (size_t i = 0; i < d->vclass.size(); i++) {
-        const bool f = !d->var_fast.empty() && i < d->var_fast[0].size() && fast_covers(d, d->var_fast[0][i], d->vclass[i].deg);
+        const TreeClassPlan *t = d->tree_class(TT_VAR, 0, (int)i);      // (null: set 0 decides, a code of one iteration)
+        const bool f = t && fast_covers(d, t->fast, d->vclass[i].deg);
         o << (i ? "," : "") << "{\"deg\":" << d->vclass[i].deg << ",\"nodes\":" << d->vclass[i].nodes.size() << ",\"nodes_per_wave\":" << d->npw_vn(d->vclass[i].deg) << ",\"kernel\":\""
-          << (f ? "vn_balanced_fast_kernel" : (!d->var_jit.empty() && i < d->var_jit[0].size() && d->var_jit[0][i]) ? "lutldpc_jit_pass" : "tree_pass_kernel<VAR>") << "\"}";
+          << (f ? "vn_balanced_fast_kernel" : t && t->jit ? "lutldpc_jit_pass" : "tree_pass_kernel<VAR>") << "\"}";
     }
     o << "],\"cn_classes\":[";
     for (size_t i = 0; i < d->cclass.size(); i++) {
@@ -53,15 +64,24 @@ void make_describe(lutldpc_decoder *d) {
                            : n_fast == 0 ? "cn_minsum_generic_kernel" : "cn_minsum_fast_kernel+cn_minsum_generic_kernel";
         // degree-2 nodes updated inside the check pass of this class: the forward links of its chain table (build_fast_index)
         int chained = 0;
-        if (d->opt.use_chain && i < d->chain_idx_off.size() && d->chain_idx_off[i] >= 0)
-            for (size_t j = 0; j < d->cclass[i].nodes.size(); j++) chained += d->fast_idx[(size_t)d->chain_idx_off[i] + 2 * j + 1] != 0;
+        if (d->opt.use_chain && d->cclass[i].chain_off >= 0)
+            for (size_t j = 0; j < d->cclass[i].nodes.size(); j++) chained += d->fast_idx[(size_t)d->cclass[i].chain_off + 2 * j + 1] != 0;
+        const TreeClassPlan *t = d->tree_class(TT_CHK, 0, (int)i);
         o << (i ? "," : "") << "{\"deg\":" << d->cclass[i].deg << ",\"nodes\":" << d->cclass[i].nodes.size() << ",\"nodes_per_wave\":" << d->npw_cn_class(i)
           << ",\"chain_nodes\":" << chained << ",\"kernel\":\""
           << (d->min_lut ? minsum
-                         : (!d->chk_jit.empty() && i < d->chk_jit[0].size() && d->chk_jit[0][i]) ? "lutldpc_jit_pass" : "tree_pass_kernel<CHK>") << "\"}";
+                         : t && t->jit ? "lutldpc_jit_pass" : "tree_pass_kernel<CHK>") << "\"}";
     }
     o << "],\"resident\":" << (resident_active(d) ? 1 : 0) << ",\"skewed_pipeline\":" << ((d->opt.skew && d->skew_ok) ? 1 : 0) << ",\"fused_bucket\":" << d->fused_bucket_id << ",\"compaction\":" << (d->opt.use_compact < 0 ? 2 : d->opt.use_compact) << ",\"compaction_min_groups\":" << compaction_min_groups(d) << ",\"chain_nodes\":" << (d->opt.use_chain ? d->n_chain_nodes : 0) << ",\"placement\":" << d->place_info;
     if (d->gen_set) o << ",\"generator\":{\"K\":" << d->gen_K << ",\"R\":" << d->gen_R << "}";
+    {   // the static blobs, comparable between builds without a device.  (An Op has two bytes of padding before `mult`.)
+        uint32_t ops = 0;
+        for (const Op &op : d->all_ops) ops = crc32(crc32(ops, &op, offsetof(Op, child) + sizeof(op.child)), &op.mult, sizeof(Op) - offsetof(Op, mult));
+        char b[160];
+        snprintf(b, sizeof(b), ",\"static\":{\"ops\":%zu,\"ops_crc\":\"%08x\",\"tables_bytes\":%zu,\"tables_crc\":\"%08x\",\"index_words\":%zu,\"index_crc\":\"%08x\"}", d->all_ops.size(), ops,
+                 d->all_tables.size(), crc32(0, d->all_tables.data(), d->all_tables.size()), d->fast_idx.size(), crc32(0, d->fast_idx.data(), 4 * d->fast_idx.size()));
+        o << b;
+    }
     o << "}";
     d->describe = o.str();
 }
@@ -194,15 +214,15 @@ int lutldpc_decoder_create(int nvar, int nchk, const int32_t *dv, const int32_t 
     for (int v = 0; v < nvar; v++) d->vn_ptr[(size_t)v + 1] = d->vn_ptr[(size_t)v] + dv[v];
     for (int c = 0; c < nchk; c++) d->cn_ptr[(size_t)c + 1] = d->cn_ptr[(size_t)c] + dc[c];
     {   // every edge must appear exactly once; derive chk_equ_idx (VN of each check edge)
-        std::vector<int> edge_vn((size_t)d->E);
-        for (int v = 0; v < nvar; v++) for (int e = d->vn_ptr[(size_t)v]; e < d->vn_ptr[(size_t)v + 1]; e++) edge_vn[(size_t)e] = v;
+        d->edge_vn.resize((size_t)d->E);
+        for (int v = 0; v < nvar; v++) for (int e = d->vn_ptr[(size_t)v]; e < d->vn_ptr[(size_t)v + 1]; e++) d->edge_vn[(size_t)e] = v;
         std::vector<uint8_t> seen((size_t)d->E, 0);
         d->cn_vn.resize((size_t)d->E);
         for (int k = 0; k < d->E; k++) {
             int e = cn_msg_idx[k];
             if (e < 0 || e >= d->E || seen[(size_t)e]) return fail(LUTLDPC_ERR_ARG, "cn_msg_idx is not a permutation of the edges");
             seen[(size_t)e] = 1;
-            d->cn_vn[(size_t)k] = edge_vn[(size_t)e];
+            d->cn_vn[(size_t)k] = d->edge_vn[(size_t)e];
         }
     }
     if ((uint64_t)d->E * kRowBytes >= (1ull << 32) || (uint64_t)nvar * kRowBytes >= (1ull << 32))
@@ -250,7 +270,7 @@ int lutldpc_decoder_destroy(lutldpc_decoder *d) {
 int lutldpc_decoder_set_exit_conditions(lutldpc_decoder *d, int max_iters, int psc, int pisc) {
     if (!d) return fail(LUTLDPC_ERR_ARG, "NULL decoder");
     if (max_iters < 1 || max_iters > d->max_iters_created) return fail(LUTLDPC_ERR_ARG, "max_iters outside [1, value at creation]");
-    if (!d->dec_plan[(size_t)d->iter_set[(size_t)(max_iters - 1)]].valid)
+    if (!d->tree_set(TT_DEC, d->iter_set[(size_t)(max_iters - 1)])->valid)
         return fail(LUTLDPC_ERR_ARG, "the tree set of iteration max_iters-1 is not a decision tree set");
     d->max_iters = max_iters; d->psc = psc ? 1 : 0; d->pisc = pisc ? 1 : 0;
     return LUTLDPC_OK;
@@ -358,15 +378,10 @@ const char *lutldpc_decoder_describe(lutldpc_decoder *d) { return d ? d->describ
 // kind + 16: the program of the same tree after table composition (compose_tree)
 // kind + 32 (checks): the program over full labels the generated check kernels run (chk_full_label_program)
 static const Program *find_prog(lutldpc_decoder *d, int kind, int set, int cls) {
-    if (kind == TT_CHK + 32) {
-        if (set < 0 || set >= (int)d->chk_prog_full.size() || cls < 0 || cls >= (int)d->chk_prog_full[(size_t)set].size() || d->chk_full_tab[(size_t)set][(size_t)cls].second == 0) return nullptr;
-        return &d->chk_prog_full[(size_t)set][(size_t)cls];
-    }
-    const bool comp = (kind & 16) != 0;
-    kind &= 15;
-    auto &v = comp ? (kind == TT_VAR ? d->var_prog_c : kind == TT_CHK ? d->chk_prog_c : d->dec_prog_c) : (kind == TT_VAR ? d->var_prog : kind == TT_CHK ? d->chk_prog : d->dec_prog);
-    if (set < 0 || set >= (int)v.size() || cls < 0 || cls >= (int)v[(size_t)set].size()) return nullptr;
-    return &v[(size_t)set][(size_t)cls];
+    const bool full = kind == TT_CHK + 32, comp = !full && (kind & 16) != 0;
+    const TreeClassPlan *c = d->tree_class(full ? TT_CHK : kind & 15, set, cls);
+    if (!c || (full && c->full.tab.bytes == 0)) return nullptr;
+    return full ? &c->full.prog : comp ? &c->composed.prog : &c->base.prog;
 }
 int lutldpc_selftest_program_eval(lutldpc_decoder *d, int kind, int set, int cls, const int32_t *in, int n_in, int32_t *out, int n_out) {
     if (!d || !in || !out) return fail(LUTLDPC_ERR_ARG, "NULL argument");

@@ -22,25 +22,15 @@ ResidentSpec resident_spec(const lutldpc_decoder *d, int S, int NT) {
         R.cn_persistent = d->opt.resident_cn_persistent >= 0 ? d->opt.resident_cn_persistent
                           : (d->min_lut && max_cn <= 16 && ((max_vn <= 4 && cn_regs <= 40) || (max_vn > 12 && cn_regs <= 96)) ? 1 : 0);      // (measured: (3,6) N=10000 1.82 -> 1.92 M codewords/s fixed work, 3.65 -> 3.93 M as shipped)
     }
-    for (size_t i = 0; i < d->vclass.size(); i++) R.vcls.push_back({d->vclass[i].deg, (int)d->vclass[i].nodes.size(), d->vn_tidx_off[i], 0});
-    for (size_t i = 0; i < d->cclass.size(); i++) R.ccls.push_back({d->cclass[i].deg, (int)d->cclass[i].nodes.size(), d->cn_tidx_off[i], d->cn_tnidx_off[i]});
-    const size_t ns = d->var_plan.size();
-    R.var_prog.assign(ns, {}); R.dec_prog.assign(ns, {}); R.chk_prog.assign(ns, {});
-    R.var_tab.assign(ns, {}); R.dec_tab.assign(ns, {}); R.chk_tab.assign(ns, {});
+    for (auto &c : d->vclass) R.vcls.push_back({c.deg, (int)c.nodes.size(), c.tidx_off, 0});
+    for (auto &c : d->cclass) R.ccls.push_back({c.deg, (int)c.nodes.size(), c.tidx_off, c.tnidx_off});
+    // the composed forms; checks over full labels where that form exists (one instruction per look-up)
+    const size_t ns = d->tree_plans[TT_VAR].size();
+    R.var.assign(ns, {}); R.dec.assign(ns, {}); R.chk.assign(ns, {});
     for (size_t s = 0; s < ns; s++) {
-        auto fill = [&](const PassPlan &plan, const std::vector<Program> &progs, const std::vector<std::pair<int, int>> &tabs, std::vector<const Program *> &pp,
-                        std::vector<std::pair<int, int>> &tt) {
-            if (!plan.valid) return;
-            for (size_t c = 0; c < progs.size(); c++) { pp.push_back(&progs[c]); tt.push_back(tabs[c]); }
-        };
-        fill(d->var_plan[s], d->var_prog_c[s], d->var_tab_c[s], R.var_prog[s], R.var_tab[s]);
-        fill(d->dec_plan[s], d->dec_prog_c[s], d->dec_tab_c[s], R.dec_prog[s], R.dec_tab[s]);
-        if (!d->min_lut && d->chk_plan[s].valid)
-            for (size_t c = 0; c < d->chk_prog_c[s].size(); c++) {      // over full labels where that form exists (one instruction per look-up)
-                const bool full = c < d->chk_tab_cf[s].size() && d->chk_tab_cf[s][c].second > 0;
-                R.chk_prog[s].push_back(full ? &d->chk_prog_cf[s][c] : &d->chk_prog_c[s][c]);
-                R.chk_tab[s].push_back(full ? d->chk_tab_cf[s][c] : d->chk_tab_c[s][c]);
-            }
+        for (auto &c : d->tree_set(TT_VAR, (int)s)->cls) R.var[s].push_back(&c.composed);
+        for (auto &c : d->tree_set(TT_DEC, (int)s)->cls) R.dec[s].push_back(&c.composed);
+        for (size_t c = 0; c < d->tree_set(TT_CHK, (int)s)->cls.size(); c++) R.chk[s].push_back(d->chk_form((int)s, (int)c, true));
     }
     return R;
 }

@@ -13,10 +13,9 @@ void build_classes(const std::vector<int> &deg, std::vector<NodeClass> &cls, std
     for (auto &c : cls) list.insert(list.end(), c.nodes.begin(), c.nodes.end());
 }
 
-// Build the launch plan of one pass from per-class programs (generic) -- progs may be empty
-// for the min-sum pass.
-static int build_plan(lutldpc_decoder *d, const std::vector<NodeClass> &cls, const std::vector<Program> *progs,
-               const std::vector<size_t> *op_off, const std::vector<size_t> *tab_off, PassPlan &plan) {
+// Build the launch plan of one pass from the per-class programs of a tree set (their base forms: what the interpreter
+// kernels walk) -- `set` may be null for the min-sum pass.
+static int build_plan(lutldpc_decoder *d, const std::vector<NodeClass> &cls, const TreeSetPlan *set, PassPlan &plan) {
     if ((int)cls.size() > kMaxSeg) return fail(LUTLDPC_ERR_UNSUPPORTED, "more than 32 distinct node degrees in one pass");
     PassParams &P = plan.P;
     std::memset(&P, 0, sizeof(P));
@@ -30,13 +29,14 @@ static int build_plan(lutldpc_decoder *d, const std::vector<NodeClass> &cls, con
         S.n_nodes = (int)cls[i].nodes.size();
         S.node_off = node_off;
         S.deg = cls[i].deg;
-        if (progs) {
-            const Program &pr = (*progs)[i];
-            S.op_off = (int)(*op_off)[i]; S.n_ops = (int)pr.ops.size();
-            S.tab_off = (int)(*tab_off)[i]; S.tab_bytes = (int)pr.tables.size();
+        if (set) {
+            const TreeClassPlan &c = set->cls[i];
+            const Program &pr = c.base.prog;
+            S.op_off = c.op_off; S.n_ops = (int)pr.ops.size();
+            S.tab_off = c.base.tab.off; S.tab_bytes = c.base.tab.bytes;
             S.n_in = pr.n_in; S.n_out = pr.n_out; S.n_slots = pr.n_slots;
             max_slots = std::max(max_slots, pr.n_slots);
-            max_tab = std::max(max_tab, (int)pr.tables.size());
+            max_tab = std::max(max_tab, c.base.tab.bytes);
             max_out = std::max(max_out, pr.n_out);
         }
         blk += (S.n_nodes + P.nodes_per_block - 1) / P.nodes_per_block;
@@ -54,10 +54,11 @@ static int build_plan(lutldpc_decoder *d, const std::vector<NodeClass> &cls, con
 }
 
 static void build_fast_index(lutldpc_decoder *d) {
-    d->fast_idx.clear(); d->vn_idx_off.clear(); d->cn_idx_off.clear();
-    d->chain_idx_off.assign(d->cclass.size(), -1); d->vn_red_off.assign(d->vclass.size(), -1); d->vn_red_n.assign(d->vclass.size(), 0);
+    d->fast_idx.clear();
+    for (auto &c : d->cclass) { c.chain_off = -1; c.npw = 0; }
     for (auto &c : d->vclass) {
-        d->vn_idx_off.push_back((int)d->fast_idx.size());
+        c.red_off = -1; c.red_n = 0;
+        c.idx_off = (int)d->fast_idx.size();
         for (int v : c.nodes) { d->fast_idx.push_back(v); d->fast_idx.push_back(d->vn_ptr[(size_t)v]); }
     }
     // ---- chain links (kernels_fast.hpp: cn_minsum_body<..., CHAIN>).  A degree-2 variable node whose two checks
@@ -75,7 +76,6 @@ static void build_fast_index(lutldpc_decoder *d) {
     // code) gets at least four checks per wave, so that three of four links fall inside a wave -- and twelve where the class is
     // large enough to keep 2048 runs per frame group (DVB-S2: 11 of 12 links inside a wave, +0.9 % over six checks per wave;
     // 18 per wave is slower again, tools/env_sweep.sh)
-    d->cn_npw_class.assign(d->cclass.size(), 0);
     if (d->opt.use_chain && d->min_lut) {
         std::vector<int> cand(d->cclass.size(), 0);
         for (int v = 0; v < d->nvar; v++) {
@@ -87,8 +87,8 @@ static void build_fast_index(lutldpc_decoder *d) {
         for (size_t ci = 0; ci < d->cclass.size(); ci++)
             if (2 * cand[ci] >= (int)d->cclass[ci].nodes.size() && d->opt.nodes_per_wave_cn <= 0) {
                 const int n = (int)d->cclass[ci].nodes.size();
-                d->cn_npw_class[ci] = std::max(4, d->npw_cn(d->cclass[ci].deg));
-                if (d->opt.cn_edges_per_wave <= 0) d->cn_npw_class[ci] = std::max(d->cn_npw_class[ci], std::min(12, n / 2048));
+                d->cclass[ci].npw = std::max(4, d->npw_cn(d->cclass[ci].deg));
+                if (d->opt.cn_edges_per_wave <= 0) d->cclass[ci].npw = std::max(d->cclass[ci].npw, std::min(12, n / 2048));
             }
     }
     if (d->opt.use_chain && d->min_lut)
@@ -105,7 +105,7 @@ static void build_fast_index(lutldpc_decoder *d) {
         }
     for (size_t ci = 0; ci < d->cclass.size(); ci++) {
         auto &c = d->cclass[ci];
-        d->cn_idx_off.push_back((int)d->fast_idx.size());
+        c.idx_off = (int)d->fast_idx.size();
         bool any = false;
         for (int cn : c.nodes) {
             std::vector<int> es;
@@ -125,51 +125,38 @@ static void build_fast_index(lutldpc_decoder *d) {
             any = any || back[(size_t)cn] || fwd[(size_t)cn];
         }
         if (any) {
-            d->chain_idx_off[ci] = (int)d->fast_idx.size();
+            c.chain_off = (int)d->fast_idx.size();
             for (int cn : c.nodes) { d->fast_idx.push_back(back[(size_t)cn]); d->fast_idx.push_back(fwd[(size_t)cn]); }
         }
     }
     // the node behind every entry of the check classes' edge tables, same order
-    {
-        std::vector<int> edge_node((size_t)d->E, 0);
-        for (int v = 0; v < d->nvar; v++)
-            for (int e = d->vn_ptr[(size_t)v]; e < d->vn_ptr[(size_t)v + 1]; e++) edge_node[(size_t)e] = v;
-        d->cn_nidx_off.assign(d->cclass.size(), 0);
-        for (size_t ci = 0; ci < d->cclass.size(); ci++) {
-            const size_t off = (size_t)d->cn_idx_off[ci], cnt = d->cclass[ci].nodes.size() * (size_t)d->cclass[ci].deg;
-            d->cn_nidx_off[ci] = (int)d->fast_idx.size();
-            for (size_t j = 0; j < cnt; j++) d->fast_idx.push_back(edge_node[(size_t)d->fast_idx[off + j]]);
-        }
+    for (auto &c : d->cclass) {
+        const size_t off = (size_t)c.idx_off, cnt = c.nodes.size() * (size_t)c.deg;
+        c.nidx_off = (int)d->fast_idx.size();
+        for (size_t j = 0; j < cnt; j++) d->fast_idx.push_back(d->edge_vn[(size_t)d->fast_idx[off + j]]);
     }
     // LDS-resident decoder (jit_resident.hpp): there a LANE owns a node, so the tables are transposed -- [k][node of the class] --
     // and 64 lanes reading entry k of 64 consecutive nodes touch 256 contiguous bytes.  Canonical edge order of the check
     // (ascending variable node, as cn_msg_idx: a CHKTREE consumes its inputs in that order).
-    {
-        std::vector<int> edge_node((size_t)d->E, 0);
-        for (int v = 0; v < d->nvar; v++)
-            for (int e = d->vn_ptr[(size_t)v]; e < d->vn_ptr[(size_t)v + 1]; e++) edge_node[(size_t)e] = v;
-        d->cn_tidx_off.assign(d->cclass.size(), 0); d->cn_tnidx_off.assign(d->cclass.size(), 0); d->vn_tidx_off.assign(d->vclass.size(), 0);
-        for (size_t ci = 0; ci < d->cclass.size(); ci++) {
-            const auto &c = d->cclass[ci];
-            const size_t n = c.nodes.size();
-            d->cn_tidx_off[ci] = (int)d->fast_idx.size();
-            for (int k = 0; k < c.deg; k++) for (size_t j = 0; j < n; j++) d->fast_idx.push_back(d->cn_msg_idx[(size_t)(d->cn_ptr[(size_t)c.nodes[j]] + k)]);
-            d->cn_tnidx_off[ci] = (int)d->fast_idx.size();
-            for (int k = 0; k < c.deg; k++) for (size_t j = 0; j < n; j++) d->fast_idx.push_back(edge_node[(size_t)d->cn_msg_idx[(size_t)(d->cn_ptr[(size_t)c.nodes[j]] + k)]]);
-        }
-        for (size_t vi = 0; vi < d->vclass.size(); vi++) {
-            const auto &c = d->vclass[vi];
-            d->vn_tidx_off[vi] = (int)d->fast_idx.size();
-            for (int v : c.nodes) d->fast_idx.push_back(v);
-            for (int v : c.nodes) d->fast_idx.push_back(d->vn_ptr[(size_t)v]);
-        }
+    for (auto &c : d->cclass) {
+        const size_t n = c.nodes.size();
+        c.tidx_off = (int)d->fast_idx.size();
+        for (int k = 0; k < c.deg; k++) for (size_t j = 0; j < n; j++) d->fast_idx.push_back(d->cn_msg_idx[(size_t)(d->cn_ptr[(size_t)c.nodes[j]] + k)]);
+        c.tnidx_off = (int)d->fast_idx.size();
+        for (int k = 0; k < c.deg; k++) for (size_t j = 0; j < n; j++) d->fast_idx.push_back(d->edge_vn[(size_t)d->cn_msg_idx[(size_t)(d->cn_ptr[(size_t)c.nodes[j]] + k)]]);
+    }
+    for (auto &c : d->vclass) {
+        c.tidx_off = (int)d->fast_idx.size();
+        for (int v : c.nodes) d->fast_idx.push_back(v);
+        for (int v : c.nodes) d->fast_idx.push_back(d->vn_ptr[(size_t)v]);
     }
     // variable passes that follow a chained check pass skip the nodes it already updated
     for (size_t vi = 0; vi < d->vclass.size(); vi++) {
-        if (d->vclass[vi].deg != 2) continue;
-        d->vn_red_off[vi] = (int)d->fast_idx.size();
-        for (int v : d->vclass[vi].nodes)
-            if (!internal[(size_t)v]) { d->fast_idx.push_back(v); d->fast_idx.push_back(d->vn_ptr[(size_t)v]); d->vn_red_n[vi]++; }
+        auto &c = d->vclass[vi];
+        if (c.deg != 2) continue;
+        c.red_off = (int)d->fast_idx.size();
+        for (int v : c.nodes)
+            if (!internal[(size_t)v]) { d->fast_idx.push_back(v); d->fast_idx.push_back(d->vn_ptr[(size_t)v]); c.red_n++; }
         d->chain_vclass = (int)vi;
     }
     d->n_chain_nodes = 0;
@@ -182,54 +169,76 @@ static void build_fast_index(lutldpc_decoder *d) {
 // Always on (O(E) at creation); an inconsistency here would be an out-of-range row in every launch.
 static int validate_fast_index(const lutldpc_decoder *d) {
     const size_t n = d->fast_idx.size();
-    auto bad = [&](const std::string &what) { return fail(LUTLDPC_ERR_STATE, "index table check failed: " + what); };
-    for (size_t i = 0; i < d->vclass.size(); i++) {
-        const auto &c = d->vclass[i];
-        const size_t off = (size_t)d->vn_idx_off[i];
-        if (off + 2 * c.nodes.size() > n) return bad("variable class table outside the blob");
-        for (size_t j = 0; j < c.nodes.size(); j++) {
-            const int v = d->fast_idx[off + 2 * j], e = d->fast_idx[off + 2 * j + 1];
-            if (v < 0 || v >= d->nvar || e < 0 || e + c.deg > d->E) return bad("variable node / first edge out of range");
-        }
-        if (d->vn_red_off[i] >= 0) {
-            const size_t ro = (size_t)d->vn_red_off[i];
-            if (ro + 2 * (size_t)d->vn_red_n[i] > n) return bad("reduced variable class table outside the blob");
-            for (int j = 0; j < d->vn_red_n[i]; j++) {
-                const int v = d->fast_idx[ro + 2 * (size_t)j], e = d->fast_idx[ro + 2 * (size_t)j + 1];
-                if (v < 0 || v >= d->nvar || e < 0 || e + c.deg > d->E) return bad("reduced variable class entry out of range");
-            }
+    int rc = LUTLDPC_OK;
+    // the table of cnt entries at off lies inside the blob, and every `step`-th entry from `first` on in [0, hi); the first failure stays
+    auto check = [&](const char *name, int off, size_t cnt, size_t first, size_t step, int hi) {
+        if (rc) return;
+        if (off < 0 || (size_t)off + cnt > n) { rc = fail(LUTLDPC_ERR_STATE, std::string("index table check failed: ") + name + " table outside the blob"); return; }
+        for (size_t j = first; j < cnt && !rc; j += step)
+            if (d->fast_idx[(size_t)off + j] < 0 || d->fast_idx[(size_t)off + j] >= hi) rc = fail(LUTLDPC_ERR_STATE, std::string("index table check failed: ") + name + " entry out of range");
+    };
+    for (const auto &c : d->vclass) {
+        const size_t m = c.nodes.size(), r = (size_t)c.red_n;
+        const int N = d->nvar, e_hi = d->E - c.deg + 1;
+        check("variable class", c.idx_off, 2 * m, 0, 2, N); check("variable class", c.idx_off, 2 * m, 1, 2, e_hi);        // {node, first edge} per node
+        if (c.red_off >= 0) { check("reduced variable class", c.red_off, 2 * r, 0, 2, N); check("reduced variable class", c.red_off, 2 * r, 1, 2, e_hi); }
+        check("transposed variable class", c.tidx_off, m, 0, 1, N); check("transposed variable class", c.tidx_off, 2 * m, m, 1, e_hi);      // m nodes, then m first edges
+    }
+    for (const auto &c : d->cclass) {
+        const size_t cnt = c.nodes.size() * (size_t)c.deg;
+        check("check class edge", c.idx_off, cnt, 0, 1, d->E); check("check class node", c.nidx_off, cnt, 0, 1, d->nvar);
+        check("transposed check class edge", c.tidx_off, cnt, 0, 1, d->E); check("transposed check class node", c.tnidx_off, cnt, 0, 1, d->nvar);
+        if (c.chain_off >= 0) check("chain link", c.chain_off, 2 * c.nodes.size(), 0, 1, d->nvar + 1);
+    }
+    return rc;
+}
+
+// the tables of a compiled form join the blob (full-label tables on a 16-byte boundary)
+static void append_tables(lutldpc_decoder *d, ProgramForm &f, bool align16) {
+    while (align16 && (d->all_tables.size() & 15)) d->all_tables.push_back(0);
+    f.tab = {(int)d->all_tables.size(), (int)f.prog.tables.size()};
+    d->all_tables.insert(d->all_tables.end(), f.prog.tables.begin(), f.prog.tables.end());
+}
+
+// Compile the trees of one kind of tree set s into one form of every degree class, then the checks' full-label form of it.
+// Base forms: the trees as they are, with their look-ups (all_ops), the interpreter's launch plan and the balanced-tree plans.
+// Composed forms: after exact table composition (compose_tree), for the generated LDS-resident kernel.  Off by default
+// (LUTLDPC_COMPOSE=1), measured on MI355X (tools/resident_probe.py): a 4 KB table spreads its 1024 dwords over 32 banks 32 deep --
+// the three-input look-ups run into 3-4-way bank conflicts where a 256-byte table has at most two dwords per bank -- and the halved
+// look-up count does not pay for it: (3,6) N=10000 1.72 -> 1.24 M codewords/s with composition.
+static int add_forms(lutldpc_decoder *d, int kind, int s, bool composed) {
+    const std::vector<Tree> &trees = (kind == TT_CHK ? d->chk_trees : d->var_trees)[(size_t)s];
+    const std::vector<NodeClass> &cls = kind == TT_CHK ? d->cclass : d->vclass;
+    TreeSetPlan &S = *d->tree_set(kind, s);
+    if (!composed) S.cls.assign(cls.size(), TreeClassPlan());
+    for (size_t i = 0; i < cls.size(); i++) {
+        if (cls[i].tree_class >= (int)trees.size()) return fail(LUTLDPC_ERR_ARG, "tree set is missing a degree class");
+        const Tree &t = trees[(size_t)cls[i].tree_class];
+        TreeClassPlan &c = S.cls[i];
+        ProgramForm &f = composed ? c.composed : c.base;
+        std::string e;
+        if (!(composed ? compile_program(compose_tree(t, kind, d->opt.use_compose ? (uint64_t)d->opt.compose_space : 0), kind, cls[i].deg, f.prog, e)
+                       : compile_program(t, kind, cls[i].deg, f.prog, e)))
+            return fail(LUTLDPC_ERR_UNSUPPORTED, (composed ? "composed tree, degree " : "degree ") + std::to_string(cls[i].deg) + ": " + e);
+        append_tables(d, f, false);
+        if (composed) { f.prog.node_tabs.clear(); continue; }      // (they point into the temporary tree)
+        c.op_off = (int)d->all_ops.size();
+        d->all_ops.insert(d->all_ops.end(), f.prog.ops.begin(), f.prog.ops.end());
+        if (kind != TT_CHK) {
+            std::map<const TreeNode *, std::pair<uint32_t, uint32_t>> tab_of;
+            for (auto &nt : f.prog.node_tabs) tab_of[nt.first] = {(uint32_t)f.tab.off + nt.second[0], nt.second[1]};
+            c.fast = plan_fast_vn(t, kind, cls[i].deg, tab_of);
         }
     }
-    for (size_t i = 0; i < d->vclass.size() && i < d->vn_tidx_off.size(); i++) {
-        const auto &c = d->vclass[i];
-        const size_t off = (size_t)d->vn_tidx_off[i], m = c.nodes.size();
-        if (off + 2 * m > n) return bad("transposed variable class table outside the blob");
-        for (size_t j = 0; j < m; j++) {
-            const int v = d->fast_idx[off + j], e = d->fast_idx[off + m + j];
-            if (v < 0 || v >= d->nvar || e < 0 || e + c.deg > d->E) return bad("transposed variable class entry out of range");
-        }
+    if (!composed) {
+        if (int rc = build_plan(d, cls, &S, S.pass)) return rc;
+        S.valid = true;
     }
-    for (size_t i = 0; i < d->cclass.size() && i < d->cn_tidx_off.size(); i++) {
-        const auto &c = d->cclass[i];
-        const size_t cnt = c.nodes.size() * (size_t)c.deg, eo = (size_t)d->cn_tidx_off[i], no = (size_t)d->cn_tnidx_off[i];
-        if (eo + cnt > n || no + cnt > n) return bad("transposed check class table outside the blob");
-        for (size_t j = 0; j < cnt; j++) if (d->fast_idx[eo + j] < 0 || d->fast_idx[eo + j] >= d->E || d->fast_idx[no + j] < 0 || d->fast_idx[no + j] >= d->nvar) return bad("transposed check class entry out of range");
-    }
-    for (size_t i = 0; i < d->cclass.size(); i++) {
-        const auto &c = d->cclass[i];
-        const size_t off = (size_t)d->cn_idx_off[i], cnt = c.nodes.size() * (size_t)c.deg;
-        if (off + cnt > n) return bad("check class table outside the blob");
-        for (size_t j = 0; j < cnt; j++) if (d->fast_idx[off + j] < 0 || d->fast_idx[off + j] >= d->E) return bad("check edge out of range");
-        if (i < d->cn_nidx_off.size()) {
-            const size_t no = (size_t)d->cn_nidx_off[i];
-            if (no + cnt > n) return bad("check class node table outside the blob");
-            for (size_t j = 0; j < cnt; j++) if (d->fast_idx[no + j] < 0 || d->fast_idx[no + j] >= d->nvar) return bad("check node out of range");
-        }
-        if (d->chain_idx_off[i] >= 0) {
-            const size_t co = (size_t)d->chain_idx_off[i];
-            if (co + 2 * c.nodes.size() > n) return bad("chain link table outside the blob");
-            for (size_t j = 0; j < 2 * c.nodes.size(); j++) if (d->fast_idx[co + j] < 0 || d->fast_idx[co + j] > d->nvar) return bad("chain link out of range");
-        }
+    for (size_t i = 0; i < cls.size() && kind == TT_CHK && d->opt.chk_full_labels; i++) {
+        ProgramForm f;
+        if (!chk_full_label_program((composed ? S.cls[i].composed : S.cls[i].base).prog, f.prog) || f.prog.tables.empty()) continue;
+        append_tables(d, f, true);
+        (composed ? S.cls[i].composed_full : S.cls[i].full) = std::move(f);
     }
     return LUTLDPC_OK;
 }
@@ -258,93 +267,18 @@ int compile_all(lutldpc_decoder *d) {
         }
     }
     d->all_ops.clear(); d->all_tables.clear();
-    auto add_set = [&](const std::vector<Tree> &trees, const std::vector<NodeClass> &cls, int kind,
-                       std::vector<Program> &progs, PassPlan &plan, std::vector<FastClassPlan> *fast) -> int {
-        progs.resize(cls.size());
-        if (fast) fast->assign(cls.size(), FastClassPlan());
-        std::vector<size_t> op_off(cls.size()), tab_off(cls.size());
-        for (size_t i = 0; i < cls.size(); i++) {
-            if (cls[i].tree_class >= (int)trees.size()) return fail(LUTLDPC_ERR_ARG, "tree set is missing a degree class");
-            const Tree &t = trees[(size_t)cls[i].tree_class];
-            std::string e;
-            if (!compile_program(t, kind, cls[i].deg, progs[i], e))
-                return fail(LUTLDPC_ERR_UNSUPPORTED, "degree " + std::to_string(cls[i].deg) + ": " + e);
-            op_off[i] = d->all_ops.size(); tab_off[i] = d->all_tables.size();
-            d->all_ops.insert(d->all_ops.end(), progs[i].ops.begin(), progs[i].ops.end());
-            d->all_tables.insert(d->all_tables.end(), progs[i].tables.begin(), progs[i].tables.end());
-            if (fast) {
-                std::map<const TreeNode *, std::pair<uint32_t, uint32_t>> tab_of;
-                for (auto &nt : progs[i].node_tabs) tab_of[nt.first] = {(uint32_t)tab_off[i] + nt.second[0], nt.second[1]};
-                (*fast)[i] = plan_fast_vn(t, kind, cls[i].deg, tab_of);
-            }
-        }
-        return build_plan(d, cls, &progs, &op_off, &tab_off, plan);
-    };
-    // composed variants of the programs of one set (tables appended to the same blob).  Off by default (LUTLDPC_COMPOSE=1), measured
-    // on MI355X (tools/resident_probe.py): a 4 KB table spreads its 1024 dwords over 32 banks 32 deep -- the three-input look-ups run
-    // into 3-4-way bank conflicts where a 256-byte table has at most two dwords per bank -- and the halved look-up count does not pay
-    // for it: (3,6) N=10000 1.72 -> 1.24 M codewords/s with composition.
-    auto add_composed = [&](const std::vector<Tree> &trees, const std::vector<NodeClass> &cls, int kind, std::vector<Program> &progs,
-                            std::vector<std::pair<int, int>> &tabs) -> int {
-        progs.assign(cls.size(), Program()); tabs.assign(cls.size(), {0, 0});
-        for (size_t i = 0; i < cls.size(); i++) {
-            const Tree &t = trees[(size_t)cls[i].tree_class];
-            const Tree tc = d->opt.use_compose ? compose_tree(t, kind, (uint64_t)d->opt.compose_space) : compose_tree(t, kind, 0);
-            std::string e;
-            if (!compile_program(tc, kind, cls[i].deg, progs[i], e)) return fail(LUTLDPC_ERR_UNSUPPORTED, "composed tree, degree " + std::to_string(cls[i].deg) + ": " + e);
-            progs[i].node_tabs.clear();                         // (they point into the temporary tree)
-            tabs[i] = {(int)d->all_tables.size(), (int)progs[i].tables.size()};
-            d->all_tables.insert(d->all_tables.end(), progs[i].tables.begin(), progs[i].tables.end());
-        }
-        return LUTLDPC_OK;
-    };
-    size_t ns = (size_t)n_sets;
-    d->var_prog.assign(ns, {}); d->dec_prog.assign(ns, {}); d->chk_prog.assign(ns, {});
-    d->var_plan.assign(ns, {}); d->dec_plan.assign(ns, {}); d->chk_plan.assign(ns, {});
-    d->var_fast.assign(ns, {}); d->dec_fast.assign(ns, {});
-    d->chk_prog_full.assign(ns, {}); d->chk_full_tab.assign(ns, {});
-    d->chk_prog_cf.assign(ns, {}); d->chk_tab_cf.assign(ns, {});
-    d->var_prog_c.assign(ns, {}); d->dec_prog_c.assign(ns, {}); d->chk_prog_c.assign(ns, {});
-    d->var_tab_c.assign(ns, {}); d->dec_tab_c.assign(ns, {}); d->chk_tab_c.assign(ns, {});
-    for (size_t s = 0; s < ns; s++) {
+    for (auto &plans : d->tree_plans) plans.assign((size_t)n_sets, TreeSetPlan());
+    for (int s = 0; s < n_sets; s++) {
         // a set is either message-update trees or (the last one) decision trees
-        int type = d->var_trees[s].empty() ? TT_VAR : d->var_trees[s][0].type;
+        const int vkind = !d->var_trees[(size_t)s].empty() && d->var_trees[(size_t)s][0].type == TT_DEC ? TT_DEC : TT_VAR;
+        // the order in which the forms reach the blobs is the layout of the blobs
         int rc;
-        if (type == TT_DEC) rc = add_set(d->var_trees[s], d->vclass, TT_DEC, d->dec_prog[s], d->dec_plan[s], &d->dec_fast[s]);
-        else rc = add_set(d->var_trees[s], d->vclass, TT_VAR, d->var_prog[s], d->var_plan[s], &d->var_fast[s]);
-        if (rc) return rc;
-        if (!d->min_lut) {
-            rc = add_set(d->chk_trees[s], d->cclass, TT_CHK, d->chk_prog[s], d->chk_plan[s], nullptr);
-            if (rc) return rc;
-            d->chk_prog_full[s].assign(d->cclass.size(), Program());
-            d->chk_full_tab[s].assign(d->cclass.size(), {0, 0});
-            for (size_t i = 0; i < d->cclass.size() && d->opt.chk_full_labels; i++) {
-                Program f;
-                if (!chk_full_label_program(d->chk_prog[s][i], f) || f.tables.empty()) continue;
-                while (d->all_tables.size() & 15) d->all_tables.push_back(0);
-                d->chk_full_tab[s][i] = {(int)d->all_tables.size(), (int)f.tables.size()};
-                d->all_tables.insert(d->all_tables.end(), f.tables.begin(), f.tables.end());
-                d->chk_prog_full[s][i] = std::move(f);
-            }
-        }
-        if (type == TT_DEC) rc = add_composed(d->var_trees[s], d->vclass, TT_DEC, d->dec_prog_c[s], d->dec_tab_c[s]);
-        else rc = add_composed(d->var_trees[s], d->vclass, TT_VAR, d->var_prog_c[s], d->var_tab_c[s]);
-        if (rc) return rc;
-        if (!d->min_lut && (rc = add_composed(d->chk_trees[s], d->cclass, TT_CHK, d->chk_prog_c[s], d->chk_tab_c[s]))) return rc;
-        if (!d->min_lut) {
-            d->chk_prog_cf[s].assign(d->cclass.size(), Program());
-            d->chk_tab_cf[s].assign(d->cclass.size(), {0, 0});
-            for (size_t i = 0; i < d->cclass.size() && d->opt.chk_full_labels; i++) {
-                Program f;
-                if (!chk_full_label_program(d->chk_prog_c[s][i], f) || f.tables.empty()) continue;
-                while (d->all_tables.size() & 15) d->all_tables.push_back(0);
-                d->chk_tab_cf[s][i] = {(int)d->all_tables.size(), (int)f.tables.size()};
-                d->all_tables.insert(d->all_tables.end(), f.tables.begin(), f.tables.end());
-                d->chk_prog_cf[s][i] = std::move(f);
-            }
-        }
+        if ((rc = add_forms(d, vkind, s, false))) return rc;
+        if (!d->min_lut && (rc = add_forms(d, TT_CHK, s, false))) return rc;
+        if ((rc = add_forms(d, vkind, s, true))) return rc;
+        if (!d->min_lut && (rc = add_forms(d, TT_CHK, s, true))) return rc;
     }
-    if (d->min_lut) { int rc = build_plan(d, d->cclass, nullptr, nullptr, nullptr, d->cn_minsum_plan); if (rc) return rc; }
+    if (d->min_lut) { int rc = build_plan(d, d->cclass, nullptr, d->cn_minsum_plan); if (rc) return rc; }
     return LUTLDPC_OK;
 }
 
@@ -375,13 +309,12 @@ JitKernel *jit_get(int device, const std::string &src, std::string &log) {
 // Source of the streaming pass kernel of class i of tree set s as build_jit compiles it.  kind: TT_VAR, TT_DEC, TT_CHK (the
 // sign/magnitude program) or TT_CHK + 32 (the full-label program, with its own table blob)
 bool jit_class_source(const lutldpc_decoder *d, int kind, size_t s, size_t i, std::string &src, std::string &err) {
-    if (kind == TT_CHK + 32 && s < d->chk_full_tab.size() && i < d->chk_full_tab[s].size() && d->chk_full_tab[s][i].second > 0)
-        return jit_cn_source(d->chk_prog_full[s][i], d->cclass[i].deg, d->pack, d->chk_full_tab[s][i].second, src, err);
-    if (kind != TT_VAR && kind != TT_DEC && kind != TT_CHK) { err = "only variable / decision / check-tree programs are generated"; return false; }
-    const PassPlan &plan = kind == TT_VAR ? d->var_plan[s] : kind == TT_DEC ? d->dec_plan[s] : d->chk_plan[s];
-    const auto &progs = kind == TT_VAR ? d->var_prog[s] : kind == TT_DEC ? d->dec_prog[s] : d->chk_prog[s];
-    return kind == TT_CHK ? jit_cn_source(progs[i], d->cclass[i].deg, d->pack, plan.P.seg[i].tab_bytes, src, err)
-                          : jit_vn_source(progs[i], kind, d->vclass[i].deg, d->pack, plan.P.seg[i].tab_bytes, src, err);
+    const bool full = kind == TT_CHK + 32;
+    const TreeClassPlan *c = d->tree_class(full ? TT_CHK : kind, (int)s, (int)i);
+    if (!c || (full && c->full.tab.bytes == 0)) { err = "only variable / decision / check-tree programs are generated"; return false; }
+    const ProgramForm &f = full ? c->full : c->base;
+    return full || kind == TT_CHK ? jit_cn_source(f.prog, d->cclass[i].deg, d->pack, f.tab.bytes, src, err)
+                                 : jit_vn_source(f.prog, kind, d->vclass[i].deg, d->pack, f.tab.bytes, src, err);
 }
 
 // HIP loads the code object of a translation unit lazily, at the first launch of one of its kernels -- possibly in the
@@ -406,26 +339,20 @@ static int preload_code_objects(int device) {
 
 // jit.hpp: generate + compile + load a kernel for every variable / decision / CHKTREE class without a compile-time specialised one
 static void build_jit(lutldpc_decoder *d) {
-    const size_t ns = d->var_plan.size();
-    d->var_jit.assign(ns, {}); d->dec_jit.assign(ns, {}); d->chk_jit.assign(ns, {});
     if (!d->opt.use_jit || !d->opt.use_fast) return;
-    for (size_t s = 0; s < ns; s++)
+    for (size_t s = 0; s < d->tree_plans[TT_VAR].size(); s++)
         for (int kind : {TT_VAR, TT_DEC, TT_CHK}) {
-            if (kind == TT_CHK && d->min_lut) continue;
-            const PassPlan &plan = kind == TT_VAR ? d->var_plan[s] : kind == TT_DEC ? d->dec_plan[s] : d->chk_plan[s];
-            if (!plan.valid) continue;
+            TreeSetPlan &S = *d->tree_set(kind, (int)s);
             const auto &cls = kind == TT_CHK ? d->cclass : d->vclass;
-            auto &out = kind == TT_VAR ? d->var_jit[s] : kind == TT_DEC ? d->dec_jit[s] : d->chk_jit[s];
-            out.assign(cls.size(), nullptr);
-            for (size_t i = 0; i < cls.size(); i++) {
-                if (kind != TT_CHK && fast_covers(d, (kind == TT_VAR ? d->var_fast[s] : d->dec_fast[s])[i], cls[i].deg)) continue;
+            for (size_t i = 0; i < S.cls.size(); i++) {
+                if (kind != TT_CHK && fast_covers(d, S.cls[i].fast, cls[i].deg)) continue;
                 std::string src, log;
-                const bool full = kind == TT_CHK && s < d->chk_full_tab.size() && i < d->chk_full_tab[s].size() && d->chk_full_tab[s][i].second > 0;
+                const bool full = kind == TT_CHK && d->chk_form((int)s, (int)i, false) == &S.cls[i].full;
                 if (!jit_class_source(d, full ? TT_CHK + 32 : kind, s, i, src, log)) { d->jit_log = log; continue; }
                 JitKernel *k = jit_get(d->device, src, log);
                 if (!k) { d->jit_log = "generated-kernel registry full"; continue; }
                 if (!log.empty()) d->jit_log = log;
-                if (k->ok()) out[i] = k;
+                if (k->ok()) S.cls[i].jit = k;
             }
         }
 }
@@ -448,8 +375,6 @@ int upload_static(lutldpc_decoder *d) {
     HIP_TRY(d->d_cn_list.upload(d->cn_list));
     HIP_TRY(d->d_fast_idx.upload(d->fast_idx));
     HIP_TRY(d->d_chain_internal.upload(d->chain_internal));
-    d->edge_vn.resize((size_t)d->E);
-    for (int v = 0; v < d->nvar; v++) for (int e = d->vn_ptr[(size_t)v]; e < d->vn_ptr[(size_t)v + 1]; e++) d->edge_vn[(size_t)e] = v;
     HIP_TRY(d->d_edge_vn.upload(d->edge_vn));
     HIP_TRY(d->d_ops.upload(d->all_ops));
     {   // pad the table blob so that dword staging never reads past the end

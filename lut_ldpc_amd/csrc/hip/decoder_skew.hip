@@ -18,10 +18,8 @@ bool skew_eligible(const lutldpc_decoder *d) {
     for (auto &c : d->vclass) max_vn = std::max(max_vn, c.deg);
     if (fused_bucket(max_vn, max_cn) < 0) return false;
     for (int nq : d->Nq_Msg) for (auto &c : d->cclass) if (!cn_minsum_shape(nq / 2, c.deg)) return false;
-    for (size_t s = 0; s < d->var_fast.size(); s++) {
-        if (d->var_plan[s].valid == false) continue;          // decision-only set
-        for (auto &f : d->var_fast[s]) if (!f.ok) return false;       // (a balanced tree of a degree the bucket holds fits its table slots in LDS)
-    }
+    for (int s = 0; d->tree_set(TT_VAR, s); s++)              // (a decision-only set has no variable classes)
+        for (auto &c : d->tree_set(TT_VAR, s)->cls) if (!c.fast.ok) return false;       // (a balanced tree of a degree the bucket holds fits its table slots in LDS)
     return true;
 }
 

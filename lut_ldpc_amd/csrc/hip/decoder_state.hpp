@@ -3,7 +3,8 @@
 // defined here (every kernel has ONE home unit, the others call that unit's host launcher).
 //
 //   decoder.hip            C-ABI: create (knob table) / destroy / exit conditions / decode entries / profiling / describe / selftest
-//   decoder_setup.hip      tree compiler, dense index tables, chain fusion, JIT registry, static uploads
+//   decoder_setup.hip      fills the tree plans (TreeClassPlan: every compiled form of a tree, add_forms) and the dense index tables
+//                          (NodeClass: where each sits), chain fusion, JIT registry, static uploads
 //   decoder_batch.hip      batch buffers, parameter arena, placement search
 //   decoder_stream.hip     streaming decode: class parameters (the one builder and validator of ClassParams), per-class launches,
 //                          decision pass, graph replay, message trace   (kernels_generic.hpp)
@@ -92,6 +93,15 @@ struct NodeClass {
     int deg = 0;
     std::vector<int> nodes;     // node ids, ascending
     int tree_class = -1;        // index of the matching tree inside a tree set
+    // where the class's dense index tables sit in fast_idx (build_fast_index).  idx_off: variable classes {node id, first edge}
+    // per node, check classes the DEG edge ids per node; tidx_off: the same transposed for the LDS-resident decoder ([2][node] /
+    // [k][node]).  Checks only: nidx_off / tnidx_off = the NODE of every entry of idx_off / tidx_off (iteration 0 reads the
+    // initial-message rows), chain_off = {back, forward} node links of chain fusion (-1: none), npw = checks per wave where
+    // the class is chain-rich (0: npw_cn of the degree).  Variables only: red_off / red_n = dense table / count of the nodes NOT
+    // updated inside the check pass (-1: the class has no such table)
+    int idx_off = 0, tidx_off = 0;
+    int nidx_off = 0, tnidx_off = 0, chain_off = -1, npw = 0;
+    int red_off = -1, red_n = 0;
 };
 
 struct PassPlan {               // one launch: all degree classes of one pass of one tree set
@@ -100,6 +110,24 @@ struct PassPlan {               // one launch: all degree classes of one pass of
     int out_slots = 0;
     bool lds_tab = true;
     bool valid = false;
+};
+
+// One (tree kind, tree set, degree class): every compiled form of its tree (lut_program.hpp: ProgramForm) and the kernels planned
+// for it.  A new program form or kernel plan is one more field here.
+struct TreeClassPlan {
+    ProgramForm base;               // the tree as the reference walks it: interpreter and generated streaming kernels
+    int op_off = 0;                 // ... and where its look-ups sit in all_ops
+    ProgramForm full;               // checks only: over full labels (chk_full_label_program), for the generated check kernels
+    // after exact table composition (compose_tree): fewer, larger look-ups; what the generated LDS-resident kernel runs.
+    // opt.use_compose = 0: the original trees.  composed_full: checks only, as `full`
+    ProgramForm composed, composed_full;
+    FastClassPlan fast;             // variable / decision classes: balanced-tree plan of the compile-time kernel
+    const JitKernel *jit = nullptr; // generated streaming kernel (jit.hpp, build_jit), null = none
+};
+struct TreeSetPlan {                // valid: the set has trees of this kind (cls is empty otherwise); pass: the interpreter's launch
+    bool valid = false;
+    PassPlan pass;
+    std::vector<TreeClassPlan> cls; // parallel to vclass / cclass
 };
 
 #pragma GCC visibility pop
@@ -141,36 +169,33 @@ struct lutldpc_decoder {
     int Nq_Cha = 0, max_iters_created = 0, max_iters = 0, psc = 1, pisc = 0, min_lut = 1;
     std::vector<int> Nq_Msg, iter_set;         // iter_set = cumsum(reuse == 0) - 1
     TreeArray var_trees, chk_trees;
-    // ---- programs: [set][class]
-    std::vector<std::vector<Program>> var_prog, chk_prog, dec_prog;
-    // check programs over full labels (lut_program.hpp: chk_full_label_program) for the generated check kernels, and where their
-    // tables sit in the blob: [set][class], {offset, bytes}, bytes = 0: none (the generated kernel then works on sign / magnitude)
-    std::vector<std::vector<Program>> chk_prog_full;
-    std::vector<std::vector<std::pair<int, int>>> chk_full_tab;
-    std::vector<std::vector<Program>> chk_prog_cf;                    // the same for the programs the LDS-resident decoder runs (chk_prog_c)
-    std::vector<std::vector<std::pair<int, int>>> chk_tab_cf;
-    // the same trees after exact table composition (lut_program.hpp: compose_tree): fewer, larger look-ups; used by the generated
-    // LDS-resident kernel.  *_tab_c: {offset, bytes} of the class blob inside all_tables.  opt.use_compose = 0: the originals.
-    std::vector<std::vector<Program>> var_prog_c, chk_prog_c, dec_prog_c;
-    std::vector<std::vector<std::pair<int, int>>> var_tab_c, chk_tab_c, dec_tab_c;
+    // ---- programs, launch plans and kernels of every tree: [TT_VAR | TT_CHK | TT_DEC][set].  Read through the three accessors
+    // below, which answer nullptr outside the ranges (a set without trees of that kind has no classes); nothing else indexes it.
+    std::vector<TreeSetPlan> tree_plans[3];
+    const TreeSetPlan *tree_set(int kind, int set) const {
+        return kind >= 0 && kind < 3 && set >= 0 && (size_t)set < tree_plans[kind].size() ? &tree_plans[kind][(size_t)set] : nullptr;
+    }
+    const TreeClassPlan *tree_class(int kind, int set, int cls) const {
+        const TreeSetPlan *s = tree_set(kind, set);
+        return s && cls >= 0 && (size_t)cls < s->cls.size() ? &s->cls[(size_t)cls] : nullptr;
+    }
+    // the form a generated check kernel runs: over full labels where that form exists, else (sign, magnitude) as the reference
+    const ProgramForm *chk_form(int set, int cls, bool composed) const {
+        const TreeClassPlan *c = tree_class(TT_CHK, set, cls);
+        if (!c) return nullptr;
+        const ProgramForm &f = composed ? c->composed_full : c->full;
+        return f.tab.bytes > 0 ? &f : composed ? &c->composed : &c->base;
+    }
+    TreeSetPlan *tree_set(int kind, int set) { return const_cast<TreeSetPlan *>(const_cast<const lutldpc_decoder *>(this)->tree_set(kind, set)); }
+    TreeClassPlan *tree_class(int kind, int set, int cls) { return const_cast<TreeClassPlan *>(const_cast<const lutldpc_decoder *>(this)->tree_class(kind, set, cls)); }
     std::vector<Op> all_ops;
     std::vector<uint8_t> all_tables;
-    std::vector<PassPlan> var_plan, chk_plan, dec_plan;   // per tree set
     PassPlan cn_minsum_plan;
-    std::vector<std::vector<FastClassPlan>> var_fast, dec_fast;   // [set][class]
-    // dense per-class index tables of the specialised kernels: variable classes {node id, first edge}
-    // per node, check classes the DEG edge ids per node (no pointer chasing, scalar loads)
+    // dense per-class index tables of the specialised kernels (no pointer chasing, scalar loads); NodeClass says where each sits
     std::vector<int32_t> fast_idx;
-    std::vector<int> vn_idx_off, cn_idx_off;                      // per class
-    std::vector<int> cn_nidx_off;                                 // per check class: the NODE of every entry of the edge table (iteration 0 reads the initial-message rows)
-    std::vector<int> cn_tidx_off, cn_tnidx_off, vn_tidx_off;      // transposed tables of the LDS-resident decoder: [k][node] edges / nodes per check class, [2][node] {node id, first edge} per variable class
-    // chain fusion (build_fast_index): per check class the offset of its {back, forward} node table (-1 = no links),
-    // per variable class the dense table / count of the nodes NOT updated inside the check pass
-    std::vector<int> chain_idx_off, vn_red_off, vn_red_n;
-    int chain_vclass = -1, n_chain_nodes = 0;
-    std::vector<int> cn_npw_class;          // checks per wave of each check class (chain-rich classes of wide checks get at least 4)
+    int chain_vclass = -1, n_chain_nodes = 0;   // chain fusion (build_fast_index): the degree-2 class, nodes updated inside the check pass
     std::vector<uint8_t> chain_internal;    // 1 = variable node updated inside the check pass (build_fast_index)
-    std::vector<int32_t> edge_vn;           // variable node of every edge (chain_hard_kernel)
+    std::vector<int32_t> edge_vn;           // variable node of every edge (set at creation; chain_hard_kernel reads the device copy)
     int pack = 1;               // 2: nibble rows (all alphabets <= 16 labels and opt.pack = 0), 1: byte rows
     bool skew_ok = false;       // every class of every set has a case in the fused kernel
     int fused_bucket_id = 0;    // degree bucket of the fused kernel (kernels_fast.hpp: kFusedVnDeg / kFusedCnDeg)
@@ -250,7 +275,6 @@ struct lutldpc_decoder {
     std::string resident_log;
     // tree-specialised kernels for shapes the compile-time path does not cover (jit.hpp); the loaded kernels live in a
     // process-wide registry keyed by device + source text, see jit_registry(): decoders share them and they are never unloaded
-    std::vector<std::vector<const JitKernel *>> var_jit, dec_jit, chk_jit;     // [set][class], null = none
     std::string jit_log;                                               // last hiprtc diagnostic (describe())
     // repeated decodes replayed as one hipGraph launch (decode_tiles)
     struct GraphSlot { int seen = 0; hipGraphExec_t exec = nullptr; };
@@ -261,7 +285,7 @@ struct lutldpc_decoder {
     int cn_epw() const { return opt.cn_edges_per_wave > 0 ? opt.cn_edges_per_wave : 42; }
     int npw_vn(int deg) const { return opt.nodes_per_wave > 0 ? opt.nodes_per_wave : std::max(1, opt.vn_edges_per_wave / std::max(deg, 1)); }
     int npw_cn(int deg) const { return opt.nodes_per_wave_cn > 0 ? opt.nodes_per_wave_cn : std::max(1, cn_epw() / std::max(deg, 1)); }
-    int npw_cn_class(size_t ci) const { return ci < cn_npw_class.size() && cn_npw_class[ci] > 0 ? cn_npw_class[ci] : npw_cn(cclass[ci].deg); }
+    int npw_cn_class(size_t ci) const { return cclass[ci].npw > 0 ? cclass[ci].npw : npw_cn(cclass[ci].deg); }     // chain-rich classes of wide checks get at least 4
     std::string place_info = "null";                  // what the placement search did (decoder_batch.hip: place_rows), JSON
     // launch plan of the skewed pipeline for one (frame groups, psc, max_iters): the roles of every launch in DEVICE memory
     // (the kernel reads them through a pointer), the interleaved item tables, what follows each launch.  Built once, at

@@ -100,20 +100,20 @@ static ClassParams class_params(const lutldpc_decoder *d, int kind, const NodeCl
 }
 ClassParams cn_class_params(const lutldpc_decoder *d, size_t ci, HalfRange groups, int nz, int check, int skew_ii) {
     const NodeClass &c = d->cclass[ci];
-    ClassParams P = class_params(d, 0, c, (int)c.nodes.size(), d->cn_idx_off[ci], skew_ii == kPerClassLaunch ? d->npw_cn(c.deg) : d->npw_cn_class(ci), groups, nz, check);
+    ClassParams P = class_params(d, 0, c, (int)c.nodes.size(), c.idx_off, skew_ii == kPerClassLaunch ? d->npw_cn(c.deg) : d->npw_cn_class(ci), groups, nz, check);
     if (skew_ii == kPerClassLaunch) return P;
     const int ii = skew_ii, buf_w = kVfailSlots * d->Bcap / 4;        // words per flag buffer
     P.vfail_off_w = (ii & 1) * buf_w;                                 // parity flags: this iteration's exit test
-    if (ii == 0 && d->opt.first_from_nodes) { P.first = 1; P.nidx_off = d->cn_nidx_off[ci]; }
+    if (ii == 0 && d->opt.first_from_nodes) { P.first = 1; P.nidx_off = c.nidx_off; }
     const bool on = ii != d->max_iters - 1 && chain_active(d, d->iter_set[(size_t)ii]);
     // decided bits of the nodes updated here: stored by the check pass that reads their messages, unless they are recovered at
     // the end with everything else (late_hard_active + chain_hard_kernel)
     const bool hard = d->psc && ii >= 1 && chain_active(d, d->iter_set[(size_t)(ii - 1)]) && !late_hard_active(d, true, nullptr);
-    if ((on || hard) && d->chain_idx_off[ci] >= 0) {
-        P.chain.idx_off = d->chain_idx_off[ci];
+    if ((on || hard) && c.chain_off >= 0) {
+        P.chain.idx_off = c.chain_off;
         P.chain.hard = hard ? 1 : 0;
         if (on) {
-            const FastClassPlan &F2 = d->var_fast[(size_t)d->iter_set[(size_t)ii]][(size_t)d->chain_vclass];
+            const FastClassPlan &F2 = d->tree_class(TT_VAR, d->iter_set[(size_t)ii], d->chain_vclass)->fast;
             P.chain.on = 1;
             P.chain.tab_off = F2.tab_off[0]; P.chain.tab_len = F2.tab_len[0]; P.chain.tab_shift = F2.tab_shift[0];
             P.chain.check = d->psc ? 1 : 0;
@@ -125,26 +125,24 @@ ClassParams cn_class_params(const lutldpc_decoder *d, size_t ci, HalfRange group
 }
 ClassParams lut_cn_class_params(const lutldpc_decoder *d, int set, size_t ci, HalfRange groups, int nz, int check) {
     ClassParams P = cn_class_params(d, ci, groups, nz, check);
-    const PassSeg &S = d->chk_plan[(size_t)set].P.seg[ci];           // the class blob the kernel was generated for: over full labels where there is one
-    const bool full = (size_t)set < d->chk_full_tab.size() && ci < d->chk_full_tab[(size_t)set].size() && d->chk_full_tab[(size_t)set][ci].second > 0;
-    P.tab_off[0] = full ? d->chk_full_tab[(size_t)set][ci].first : S.tab_off;
-    P.tab_len[0] = full ? d->chk_full_tab[(size_t)set][ci].second : S.tab_bytes;
+    const TabRef tab = d->chk_form(set, (int)ci, false)->tab;        // the class blob the kernel was generated for
+    P.tab_off[0] = tab.off; P.tab_len[0] = tab.bytes;
     return P;
 }
 ClassParams vn_class_params(const lutldpc_decoder *d, int kind, int set, size_t ci, HalfRange groups, int nz, int check, int write_hard, int skew_ii) {
     const NodeClass &c = d->vclass[ci];
-    int n_nodes = (int)c.nodes.size(), idx_off = d->vn_idx_off[ci];
-    if (skew_ii != kPerClassLaunch && chain_active(d, set) && (int)ci == d->chain_vclass) { n_nodes = d->vn_red_n[ci]; idx_off = d->vn_red_off[ci]; }   // the others are updated by the check pass
+    int n_nodes = (int)c.nodes.size(), idx_off = c.idx_off;
+    if (skew_ii != kPerClassLaunch && chain_active(d, set) && (int)ci == d->chain_vclass) { n_nodes = c.red_n; idx_off = c.red_off; }   // the others are updated by the check pass
     ClassParams P = class_params(d, 1, c, n_nodes, idx_off, d->npw_vn(c.deg), groups, nz, check);
     P.write_hard = write_hard;
     if (skew_ii != kPerClassLaunch) P.vfail_off_w = ((skew_ii + 1) & 1) * (kVfailSlots * d->Bcap / 4);      // unanimity flags: the exit test after the NEXT check pass
-    const FastClassPlan &f = (kind == TT_DEC ? d->dec_fast : d->var_fast)[(size_t)set][ci];
+    const TreeClassPlan &t = *d->tree_class(kind, set, (int)ci);
+    const FastClassPlan &f = t.fast;
     if (fast_covers(d, f, c.deg)) {                                   // balanced tree: its tables in canonical order
         P.shift_msg = f.shift_msg;
         for (int t = 0; t < f.n_tables; t++) { P.tab_off[t] = f.tab_off[t]; P.tab_len[t] = f.tab_len[t]; P.tab_shift[t] = f.tab_shift[t]; }
     } else {                                                          // generated kernel: the class blob
-        const PassSeg &S = (kind == TT_DEC ? d->dec_plan : d->var_plan)[(size_t)set].P.seg[ci];
-        P.tab_off[0] = S.tab_off; P.tab_len[0] = S.tab_bytes;
+        P.tab_off[0] = t.base.tab.off; P.tab_len[0] = t.base.tab.bytes;
     }
     return P;
 }
@@ -192,8 +190,10 @@ static int check_class_launch(const lutldpc_decoder *d, const ClassParams &P, in
 }
 
 template <int KIND>
-static int launch_tree_pass(lutldpc_decoder *d, PassPlan &plan, int set, const std::vector<const JitKernel *> *jit, int G, int nz, int check, int write_hard, int kind_id) {
-    if (!plan.valid) return fail(LUTLDPC_ERR_STATE, "pass plan missing for this tree set");
+static int launch_tree_pass(lutldpc_decoder *d, int set, int G, int nz, int check, int write_hard, int kind_id) {
+    const TreeSetPlan *S = d->tree_set(KIND, set);
+    if (!S || !S->valid) return fail(LUTLDPC_ERR_STATE, "pass plan missing for this tree set");
+    const PassPlan &plan = S->pass;
     Timed t(d, kind_id);
     PassParams P = plan.P;
     P.G = G; P.nz = nz; P.check = check; P.write_hard = write_hard; P.vfail_stride_w = d->Bcap / 4;
@@ -208,7 +208,7 @@ static int launch_tree_pass(lutldpc_decoder *d, PassPlan &plan, int set, const s
     // specialised kernels take the classes they know, one launch per degree class
     if constexpr (KIND != TT_CHK)
         for (int i = 0; i < P.n_seg && sign_bit; i++) {
-            if (!fast_covers(d, (KIND == TT_DEC ? d->dec_fast : d->var_fast)[(size_t)set][(size_t)i], P.seg[i].deg)) continue;
+            if (!fast_covers(d, S->cls[(size_t)i].fast, P.seg[i].deg)) continue;
             bool ok = false;
             const ClassParams FP = class_of(i);
             if (int rc = check_class_launch(d, FP, i, KIND, false)) return rc;
@@ -217,9 +217,9 @@ static int launch_tree_pass(lutldpc_decoder *d, PassPlan &plan, int set, const s
             if (ok) keep[(size_t)i] = 0;
         }
     // run-time generated kernels (jit.hpp) for the classes without a compile-time one
-    if (jit && sign_bit)
-        for (int i = 0; i < P.n_seg && (size_t)i < jit->size(); i++) {
-            const JitKernel *k = (*jit)[(size_t)i];
+    if (sign_bit)
+        for (int i = 0; i < P.n_seg; i++) {
+            const JitKernel *k = S->cls[(size_t)i].jit;
             if (!keep[(size_t)i] || !k) continue;
             const ClassParams F = class_of(i);
             if (int rc = check_class_launch(d, F, i, KIND, true)) return rc;
@@ -294,8 +294,8 @@ bool late_hard_active(const lutldpc_decoder *d, bool skewed, bool *chain_skip) {
 // class has the compile-time kernel (its root table is staged)
 bool chain_active(const lutldpc_decoder *d, int set) {
     if (!d->opt.use_chain || d->chain_vclass < 0 || d->n_chain_nodes == 0) return false;
-    const FastClassPlan &f = d->var_fast[(size_t)set][(size_t)d->chain_vclass];
-    return f.ok && f.n_tables == 1 && f.tab_len[0] <= 1024;
+    const TreeClassPlan *t = d->tree_class(TT_VAR, set, d->chain_vclass);
+    return t && t->fast.ok && t->fast.n_tables == 1 && t->fast.tab_len[0] <= 1024;
 }
 
 // Decided bits of the frames that left through the exit test, read off their frozen messages (hard_from_frozen_kernel) and, for
@@ -310,10 +310,10 @@ int launch_late_hard(lutldpc_decoder *d, bool skewed, int g0, int G, const int32
                                         d->Nq_Msg[0] / 2, g0, ctl));
     if (chain_skip)
         for (size_t i = 0; i < d->cclass.size(); i++) {
-            if (d->chain_idx_off[i] < 0) continue;
+            if (d->cclass[i].chain_off < 0) continue;
             const int n = (int)d->cclass[i].nodes.size(), npw = d->npw_cn_class(i), runs = (n + npw - 1) / npw;
             PACK_DISPATCH(d, launch_k(chain_hard_kernel<PK>, dim3(std::min<unsigned>(512u, (unsigned)((runs + 3) / 4)), (unsigned)G), dim3(256), 0, d->stream, d->d_hard.p,
-                                                reinterpret_cast<const uint32_t *>(d->d_state.p), d->d_fast_idx.p + d->cn_idx_off[i], d->d_fast_idx.p + d->chain_idx_off[i],
+                                                reinterpret_cast<const uint32_t *>(d->d_state.p), d->d_fast_idx.p + d->cclass[i].idx_off, d->d_fast_idx.p + d->cclass[i].chain_off,
                                                 d->d_edge_vn.p, n, d->cclass[i].deg, npw, d->nvar, g0, ctl));
         }
     LAUNCH_CHECK();
@@ -351,7 +351,7 @@ static int decode_tiles_launch(lutldpc_decoder *d, int B) {
     const int Bpad = d->bpad(B), G = Bpad / d->tile();
     const int N = d->nvar, E = d->E, I = d->max_iters;
     const int last_set = d->iter_set[(size_t)(I - 1)];
-    if (!d->dec_plan[(size_t)last_set].valid)
+    if (!d->tree_set(TT_DEC, last_set)->valid)
         return fail(LUTLDPC_ERR_STATE, "the tree set of iteration max_iters-1 is not a decision tree set");
     if ((rc = launch_state(d, B, Bpad, 0, 0))) return rc;
     const bool tracing = d->trace.level > 1;
@@ -395,13 +395,13 @@ static int decode_tiles_launch(lutldpc_decoder *d, int B) {
         const int nz_in = d->Nq_Msg[(size_t)ii] / 2;
         const int chk_check = (d->psc && ii > 0) ? 1 : 0;    // finishes the test started by VN pass ii-1
         if (d->min_lut) rc = launch_cn_minsum(d, G, nz_in, chk_check);
-        else rc = launch_tree_pass<TT_CHK>(d, d->chk_plan[(size_t)set], set, d->chk_jit.empty() ? nullptr : &d->chk_jit[(size_t)set], G, nz_in, chk_check, 0, LUTLDPC_K_CN_PASS);
+        else rc = launch_tree_pass<TT_CHK>(d, set, G, nz_in, chk_check, 0, LUTLDPC_K_CN_PASS);
         if (rc) return rc;
         if (chk_check && (rc = launch_state(d, B, Bpad, 2, ii))) return rc;   // :327-329 returns (ii-1)+1
         if (d->trace.level > 2 && (rc = trace_dump(d))) return rc;             // :311-317
         if (ii != I - 1) {
             const int nz_out = d->Nq_Msg[(size_t)(ii + 1)] / 2;
-            rc = launch_tree_pass<TT_VAR>(d, d->var_plan[(size_t)set], set, d->var_jit.empty() ? nullptr : &d->var_jit[(size_t)set], G, nz_out, d->psc ? 1 : 0,
+            rc = launch_tree_pass<TT_VAR>(d, set, G, nz_out, d->psc ? 1 : 0,
                                           (d->psc && !late_hard_active(d, false, nullptr)) ? 1 : 0, LUTLDPC_K_VN_PASS);
             if (rc) return rc;
         }
@@ -423,7 +423,7 @@ static int decode_tiles_launch(lutldpc_decoder *d, int B) {
         }
     }
     // :340-349
-    if ((rc = launch_tree_pass<TT_DEC>(d, d->dec_plan[(size_t)last_set], last_set, d->dec_jit.empty() ? nullptr : &d->dec_jit[(size_t)last_set], G, 0, 0, 0, LUTLDPC_K_DECISION))) return rc;
+    if ((rc = launch_tree_pass<TT_DEC>(d, last_set, G, 0, 0, 0, LUTLDPC_K_DECISION))) return rc;
     const int fsel = skewed ? (I & 1) : 0;            // the flag buffer no pass of the skewed pipeline has written since its last test
     if ((rc = launch_syndrome(d, G, fsel))) return rc;
     if ((rc = launch_state(d, B, Bpad, 3, I, 0, -1, fsel))) return rc;

@@ -41,9 +41,8 @@ struct ResidentSpec {
     int U = 0;                                               // frames per trip of the look-up loops (0: 2 up to degree 8, else 1)
     std::vector<int> nq_msg, iter_set;                       // per iteration
     std::vector<ResidentClass> vcls, ccls;
-    // [set][class]: program (null: the set has none of this kind) and {offset, bytes} of the class blob in the table blob
-    std::vector<std::vector<const Program *>> var_prog, dec_prog, chk_prog;
-    std::vector<std::vector<std::pair<int, int>>> var_tab, dec_tab, chk_tab;
+    // [set][class]: the program the kernel runs and where its class blob sits in the table blob (a set without trees of a kind: no classes)
+    std::vector<std::vector<const ProgramForm *>> var, dec, chk;
 };
 
 namespace resident_detail {
@@ -110,14 +109,14 @@ inline void resident_table_bytes(const ResidentSpec &R, std::vector<int> &tv_off
     tv_bytes = 0;
     for (size_t c = 0; c < R.vcls.size(); c++) {
         int m = 0;
-        for (size_t s = 0; s < R.var_tab.size(); s++) { if (c < R.var_tab[s].size()) m = std::max(m, R.var_tab[s][c].second); if (c < R.dec_tab[s].size()) m = std::max(m, R.dec_tab[s][c].second); }
+        for (size_t s = 0; s < R.var.size(); s++) { if (c < R.var[s].size()) m = std::max(m, R.var[s][c]->tab.bytes); if (c < R.dec[s].size()) m = std::max(m, R.dec[s][c]->tab.bytes); }
         tv_off[c] = tv_bytes; tv_bytes += pad16(m);
     }
     tc_bytes = 0;
     if (!R.min_lut)
         for (size_t c = 0; c < R.ccls.size(); c++) {
             int m = 0;
-            for (size_t s = 0; s < R.chk_tab.size(); s++) if (c < R.chk_tab[s].size()) m = std::max(m, R.chk_tab[s][c].second);
+            for (size_t s = 0; s < R.chk.size(); s++) if (c < R.chk[s].size()) m = std::max(m, R.chk[s][c]->tab.bytes);
             tc_off[c] = tc_bytes; tc_bytes += pad16(m);
         }
 }
@@ -131,7 +130,7 @@ inline bool jit_resident_source(const ResidentSpec &R, std::string &src, std::st
 {
     using namespace resident_detail;
     const int PACK = R.pack, BITS = 8 / PACK, S = R.S, NT = R.NT, E = R.E, N = R.N, I = R.I;
-    const size_t n_sets_tree = R.var_prog.size();
+    const size_t n_sets_tree = R.var.size();
     if (I < 1 || (int)R.nq_msg.size() != I || (int)R.iter_set.size() != I) { err = "bad iteration tables"; return false; }
     std::vector<int> tv_off, tc_off; int tv_bytes, tc_bytes;
     resident_table_bytes(R, tv_off, tv_bytes, tc_off, tc_bytes);
@@ -186,18 +185,18 @@ inline bool jit_resident_source(const ResidentSpec &R, std::string &src, std::st
       << "        const uint32_t *s4 = reinterpret_cast<const uint32_t *>(A.tables + off);\n"
       << "        for (int i = tid; i < (len + 3) / 4; i += NT) reinterpret_cast<uint32_t *>(dst)[i] = s4[i];\n    };\n";
     // per set: offsets / lengths of the class blobs
-    auto emit_tabs = [&](const std::string &nm, const std::vector<std::vector<std::pair<int, int>>> &tabs, size_t ncls) {
+    auto emit_tabs = [&](const std::string &nm, const std::vector<std::vector<const ProgramForm *>> &tabs, size_t ncls) {
         std::vector<int> off, len;
         for (size_t s = 0; s < n_sets_tree; s++)
             for (size_t c = 0; c < ncls; c++) {
                 const bool have = s < tabs.size() && c < tabs[s].size();
-                off.push_back(have ? tabs[s][c].first : 0); len.push_back(have ? tabs[s][c].second : 0);
+                off.push_back(have ? tabs[s][c]->tab.off : 0); len.push_back(have ? tabs[s][c]->tab.bytes : 0);
             }
         emit_int_array(o, nm + "Off", off); emit_int_array(o, nm + "Len", len);
     };
     const size_t NVC = R.vcls.size(), NCC = R.ccls.size();
-    emit_tabs("kVar", R.var_tab, NVC); emit_tabs("kDec", R.dec_tab, NVC);
-    if (!R.min_lut) emit_tabs("kChk", R.chk_tab, NCC);
+    emit_tabs("kVar", R.var, NVC); emit_tabs("kDec", R.dec, NVC);
+    if (!R.min_lut) emit_tabs("kChk", R.chk, NCC);
     {
         std::vector<int> a(tv_off), b(tc_off);
         emit_int_array(o, "kTvOff", a);
@@ -361,9 +360,9 @@ inline bool jit_resident_source(const ResidentSpec &R, std::string &src, std::st
             std::vector<std::string> bodies;
             std::vector<int> variant_of(n_sets_tree, -1);
             for (size_t s = 0; s < n_sets_tree; s++) {
-                if (s >= R.chk_prog.size() || c >= R.chk_prog[s].size() || !R.chk_prog[s][c]) continue;
+                if (s >= R.chk.size() || c >= R.chk[s].size()) continue;
                 std::ostringstream b;
-                if (!emit_chk_frames(b, *R.chk_prog[s][c], C.deg, "                ", err)) return false;
+                if (!emit_chk_frames(b, R.chk[s][c]->prog, C.deg, "                ", err)) return false;
                 size_t v = 0;
                 while (v < bodies.size() && bodies[v] != b.str()) v++;
                 if (v == bodies.size()) bodies.push_back(b.str());
@@ -389,7 +388,7 @@ inline bool jit_resident_source(const ResidentSpec &R, std::string &src, std::st
 
     // ---- the variable pass / the decision pass: every thread walks its own items
     auto emit_vn_pass = [&](const std::string &fname, int kind) -> bool {
-        const auto &progs = kind == TT_VAR ? R.var_prog : R.dec_prog;
+        const auto &progs = kind == TT_VAR ? R.var : R.dec;
         o << "    auto " << fname << " = [&](int set, int ii, bool chk) {\n        (void)ii; (void)chk;\n";
         if (kind == TT_VAR) {
             if (msg_pow2) o << "        const int sbit = __builtin_ctz((unsigned)kNz[ii + 1] | 0x100u);\n";
@@ -401,9 +400,9 @@ inline bool jit_resident_source(const ResidentSpec &R, std::string &src, std::st
         for (size_t c = 0; c < NVC; c++) {
             const int deg = R.vcls[c].deg, U = R.U > 0 ? R.U : (deg <= 8 ? 2 : 1);
             for (size_t s = 0; s < n_sets_tree; s++) {
-                if (s >= progs.size() || c >= progs[s].size() || !progs[s][c]) continue;
+                if (s >= progs.size() || c >= progs[s].size()) continue;
                 std::ostringstream b;
-                if (!emit_var_frames(b, *progs[s][c], kind, deg, ((4 * PACK) % U) ? 1 : U, "                ", err)) return false;
+                if (!emit_var_frames(b, progs[s][c]->prog, kind, deg, ((4 * PACK) % U) ? 1 : U, "                ", err)) return false;
                 size_t v = 0;
                 while (v < bodies[c].size() && bodies[c][v] != b.str()) v++;
                 if (v == bodies[c].size()) bodies[c].push_back(b.str());

@@ -134,6 +134,10 @@ struct Program {
     // for completeness): out_from_input[i] = input slot or -1
 };
 
+// one compiled form of a tree and where its tables sit in the decoder's table blob (bytes == 0: the form does not exist)
+struct TabRef { int off = 0, bytes = 0; };
+struct ProgramForm { Program prog; TabRef tab; };
+
 namespace detail {
 
 struct ValKey {

@@ -223,3 +223,37 @@ def test_describe_names_the_device_code_by_a_hash_of_its_sources():
     files = sorted([*hip.glob("*.hpp"), *hip.glob("*.hip")], key=lambda p: "hip/" + p.name)
     assert h == hashlib.sha256(b"".join(p.read_bytes() for p in files)).hexdigest()[:16]
     dec.close()
+
+
+# which tree sets answer program_stats per kind (0 / 1 / 2: variable, check, decision trees; + 16: composed; 33: full-label checks),
+# class 0 of these (3,6)-regular codes.  mixed: seven sets behind a reuse vector, min-sum checks, the last set decides
+ANSWERING_SETS = {
+    "reg36_n1000_mixed": (7, {0: range(6), 1: (), 2: (6,), 16: range(6), 17: (), 18: (6,), 33: ()}),
+    "reg36_n1000_q3_chklut": (10, {0: range(9), 1: range(10), 2: (9,), 16: range(9), 17: range(10), 18: (9,), 33: range(10)}),
+}
+
+
+@pytest.mark.parametrize("name", list(ANSWERING_SETS))
+def test_program_lookup_bounds(name):
+    """Every program is found through the bounds-checked accessors of the tree plans (decoder_state.hpp): inside the code's ranges a
+    (kind, set, class) answers exactly where the set has trees of that kind, and the first index past a range, and -1, is refused."""
+    import lut_ldpc_amd as L
+    n_sets, answering = ANSWERING_SETS[name]
+    cd = oracle_codec(name)
+    dec = product_decoder(cd, device=-1)
+    assert cd.n_sets() == n_sets and len(set(cd.code.dv.tolist())) == 1 and len(set(cd.code.dc.tolist())) == 1
+
+    def answers(kind, s, cls):
+        try:
+            return dec.program_stats(kind, s, cls)["ops"] > 0
+        except L.LutLdpcError:
+            return False
+
+    for kind, sets in answering.items():
+        assert [s for s in range(n_sets) if answers(kind, s, 0)] == list(sets), kind
+        for s, cls in [(-1, 0), (n_sets, 0), (0, -1), (0, 1), (n_sets - 1, -1), (n_sets - 1, 1)]:
+            with pytest.raises(L.LutLdpcError):
+                dec.program_stats(kind, s, cls)
+            with pytest.raises(L.LutLdpcError):
+                dec.jit_source(kind, s, cls)
+    dec.close()
