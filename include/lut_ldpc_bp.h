@@ -11,6 +11,10 @@
  *
  * Arithmetic (integers throughout; "QLLR" = int32):
  *   to_qllr(l)   = clip(floor(0.5 + 2^d1 * l), +-QMAX),   QMAX = 2^(d4-1) - 1          (d4: BP.qllr_total_res, default 28)
+ *                  to_qllr(+-inf) = +-QMAX by the same formula; to_qllr(NaN) = 0, an erasure (decided here, tested explicitly:
+ *                  a conversion of NaN to int is undefined and differs between host and device)
+ *   QLLR input   : lutldpc_bp_decode_qllr_batch clips every value to +-QMAX on entry (decided here: beyond +-QMAX the sums of
+ *                  boxplus would overflow), so LLRin and every variable-to-check message lie in [-QMAX, QMAX] whichever entry was used
  *   T[i]         = to_qllr(log(1 + exp(-i * 2^(d3-d1)))),  i = 0 .. d2-1                (d2: BP.qllr_table_size, 0 = min-sum)
  *   logexp(x)    = (x >> d3) >= d2 ? 0 : T[x >> d3]                                      (x >= 0, no interpolation)
  *   boxplus(a,b) = sgn(a) sgn(b) min(|a|,|b|) + logexp(|a+b|) - logexp(|a-b|)            (a > 0 counts as positive, 0 as negative)
@@ -61,7 +65,7 @@ int lutldpc_bp_logexp_table(lutldpc_bp_decoder *d, int32_t *out, int cap);
 /* LDPC_Code::decode(const vec &llr, bvec &bits) for B frames: llr[B*nvar] double (host), out_bits[B*nvar] = LLRout < 0,
  * out_iters[B] = the return value of bp_decode, out_qllr (optional, B*nvar) = LLRout. */
 int lutldpc_bp_decode_llr_batch(lutldpc_bp_decoder *d, const double *llr, int B, uint8_t *out_bits, int32_t *out_iters, int32_t *out_qllr);
-/* LDPC_Code::bp_decode(QLLRvec) for B frames on quantised input (host). */
+/* LDPC_Code::bp_decode(QLLRvec) for B frames on quantised input (host); any int32 is accepted and clipped to +-QMAX. */
 int lutldpc_bp_decode_qllr_batch(lutldpc_bp_decoder *d, const int32_t *qllr, int B, uint8_t *out_bits, int32_t *out_iters, int32_t *out_qllr);
 
 #ifdef __cplusplus

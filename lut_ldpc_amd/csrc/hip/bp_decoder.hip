@@ -52,7 +52,7 @@ __device__ __forceinline__ int bp_boxplus(const int32_t *__restrict__ T, const B
 }
 __device__ __forceinline__ int bp_clip(long long x, int qmax) { return x > qmax ? qmax : (x < -qmax ? -qmax : (int)x); }
 
-// frame-major doubles -> rows of QLLRs (to_qllr), or frame-major ints -> rows
+// frame-major doubles -> rows of QLLRs (to_qllr, NaN -> 0), or frame-major ints -> rows (clipped to +-QMAX)
 __global__ __launch_bounds__(256) void bp_load_kernel(const double *__restrict__ llr, const int32_t *__restrict__ q, int32_t *__restrict__ rows,
                                                       int B, int N, int Bpad, double scale, int qmax)
 {
@@ -63,8 +63,8 @@ __global__ __launch_bounds__(256) void bp_load_kernel(const double *__restrict__
         if (f < B) {
             if (llr) {
                 const double t = floor(0.5 + scale * llr[(size_t)f * N + v]);
-                x = t >= (double)qmax ? qmax : (t <= -(double)qmax ? -qmax : (int)t);
-            } else x = q[(size_t)f * N + v];
+                x = t != t ? 0 : (t >= (double)qmax ? qmax : (t <= -(double)qmax ? -qmax : (int)t));      // NaN: an erasure
+            } else x = bp_clip(q[(size_t)f * N + v], qmax);                                               // clipped on entry
         }
         rows[(size_t)v * Bpad + f] = x;
     }
@@ -219,6 +219,7 @@ namespace {
 
 int to_qllr_host(const lutldpc_bp_decoder *d, double l) {
     const double v = std::floor(0.5 + std::ldexp(1.0, d->d1) * l);
+    if (v != v) return 0;                                      // NaN: an erasure
     if (v >= (double)d->qmax) return d->qmax;
     if (v <= -(double)d->qmax) return -d->qmax;
     return (int)v;

@@ -23,6 +23,7 @@ static int clip(long long x, int qmax) { return x > qmax ? qmax : (x < -qmax ? -
 int or_bp_to_qllr(const or_bp *b, double l)
 {
     const double v = floor(0.5 + ldexp(1.0, b->d1) * l);
+    if (v != v) return 0;                                      /* NaN: an erasure */
     if (v >= (double)b->qmax) return b->qmax;
     if (v <= -(double)b->qmax) return -b->qmax;
     return (int)v;
@@ -128,12 +129,14 @@ void or_bp_decode_qllr_batch(const or_bp *b, const int *qllr, int B, uint8_t *ou
 {
     const int N = b->code->nvar, E = b->code->nedges;
     int *mvc = (int *)malloc(sizeof(int) * (size_t)E), *mcv = (int *)malloc(sizeof(int) * (size_t)E), *out = (int *)malloc(sizeof(int) * (size_t)N);
+    int *in = (int *)malloc(sizeof(int) * (size_t)N);
     for (int f = 0; f < B; f++) {
-        out_iters[f] = decode_one(b, qllr + (size_t)f * N, out, mvc, mcv);
+        for (int v = 0; v < N; v++) in[v] = clip(qllr[(size_t)f * N + v], b->qmax);      /* clipped to +-QMAX on entry */
+        out_iters[f] = decode_one(b, in, out, mvc, mcv);
         for (int v = 0; v < N; v++) out_bits[(size_t)f * N + v] = out[v] < 0;
         if (out_qllr) memcpy(out_qllr + (size_t)f * N, out, sizeof(int) * (size_t)N);
     }
-    free(mvc); free(mcv); free(out);
+    free(mvc); free(mcv); free(out); free(in);
 }
 void or_bp_decode_llr_batch(const or_bp *b, const double *llr, int B, uint8_t *out_bits, int32_t *out_iters, int *out_qllr)
 {
