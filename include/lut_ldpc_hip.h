@@ -13,6 +13,11 @@
  * memory and one HIP stream and is NOT re-entrant (like the reference object, whose
  * lut_decode mutates the member `msgs`, src/LDPC_Code_LUT.hpp:311): use one handle per host
  * thread.  All label arrays are uint8 and frame-major: element [f*nvar + v].
+ *
+ * Errors of the batch entries (every entry below that takes a batch size B): argument errors before state errors.  A NULL
+ * handle or B <= 0 is LUTLDPC_ERR_ARG on any handle; a handle created without a device (device < 0, host-only) then answers
+ * LUTLDPC_ERR_STATE, with one message text for all entries; only then is the handle's device made current.  The checks an
+ * entry documents for its own arguments keep the places given with it.
  */
 #ifndef LUT_LDPC_HIP_H
 #define LUT_LDPC_HIP_H
@@ -130,7 +135,8 @@ int lutldpc_decoder_decode_llr_batch(lutldpc_decoder *d, const double *llr, int 
  * for a sent 1.  Frame f of the SNR point uses the Philox4x32-10 stream
  * (key = seed, counter = (f_lo, f_hi, bit-pair index, stream)), so any split of the frame range
  * over calls / GPUs generates the same frames.
- *   codewords   host [B*nvar] sent bits, or NULL for the all-zero codeword
+ *   codewords   host [B*nvar] sent bits, bytes 0 or 1 (as encode_random returns them; bit 0 of a byte is what counts: the
+ *               device keeps the sent bits in one form, a bitmap per node and frame group), or NULL for the all-zero codeword
  *   K_info      number of leading bits counted as data bits (nvar - rank(H))
  *   frame_stats host [B*4] int32: {lut_decode return value, frame error 0/1, data bit errors,
  *               uncoded (slicer) bit errors over all nvar bits}
@@ -168,7 +174,7 @@ int lutldpc_decoder_encode_random(lutldpc_decoder *d, uint64_t seed, uint32_t st
 int lutldpc_decoder_sim_batch_random(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream,
                                      uint64_t frame0, int B, int K_info, int32_t *frame_stats, uint8_t *cha_out, uint8_t *bits_out);
 
-/* The labels the sampler would produce for those frames (host, frame-major [B*nvar]); for tests. */
+/* The labels the sampler would produce for those frames (host, frame-major [B*nvar]); codewords as for sim_batch; for tests. */
 int lutldpc_decoder_sample_labels(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream,
                                   uint64_t frame0, int B, const uint8_t *codewords, uint8_t *cha, uint8_t *msg0);
 

@@ -172,6 +172,25 @@ lutldpc_decoder::~lutldpc_decoder() {
     for (auto &e : ev_pool) (void)hipEventDestroy(e);
 }
 
+// ----------------------------------------------------------------------------- decode entries
+// frame-major labels of B frames in d_in_cha / d_in_msg (uploaded, or quantised there) -> decided bits and iteration codes on the
+// host.  decode_device leaves the bits in the staging buffer in either of its branches; synchronises.
+static int decode_staged_labels(lutldpc_decoder *d, int B, uint8_t *out_bits, int32_t *out_iters) {
+    const size_t n = (size_t)B * (size_t)d->nvar;
+    HIP_TRY(d->d_out_bits.alloc(n)); HIP_TRY(d->d_out_iters.alloc((size_t)B));
+    int rc = decode_device(d, d->d_in_cha.p, d->d_in_msg.p, B, d->d_out_bits.p, d->d_out_iters.p);
+    if (rc || (rc = copy_to_host(d, out_bits, d->d_out_bits.p, n)) || (rc = iters_to_host(d, out_iters, B))) return rc;
+    HIP_TRY(hipStreamSynchronize(d->stream));
+    return LUTLDPC_OK;
+}
+
+// clears the trace sink of a handle on every way out of a traced decode (as CountedScope of decoder_stats.hip)
+struct TraceScope {
+    lutldpc_decoder *d;
+    explicit TraceScope(lutldpc_decoder *d_) : d(d_) {}
+    ~TraceScope() { d->trace = lutldpc_decoder::Trace(); }
+};
+
 #pragma GCC visibility pop
 
 // =============================================================================== C-ABI
@@ -279,27 +298,17 @@ int lutldpc_decoder_set_exit_conditions(lutldpc_decoder *d, int max_iters, int p
 int lutldpc_decoder_decode_batch_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d_msg0, int B,
                                         uint8_t *d_out_bits, int32_t *d_out_iters, int sync) {
     if (!d || !d_cha || !d_msg0 || !d_out_bits || !d_out_iters) return fail(LUTLDPC_ERR_ARG, "NULL argument");
-    int rc = decode_device(d, d_cha, d_msg0, B, d_out_bits, d_out_iters);
-    if (rc) return rc;
+    int rc = batch_entry(d, B);
+    if (rc || (rc = decode_device(d, d_cha, d_msg0, B, d_out_bits, d_out_iters))) return rc;
     if (sync) HIP_TRY(hipStreamSynchronize(d->stream));
     return LUTLDPC_OK;
 }
 
 int lutldpc_decoder_decode_batch(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0, int B, uint8_t *out_bits, int32_t *out_iters) {
     if (!d || !cha || !msg0 || !out_bits || !out_iters) return fail(LUTLDPC_ERR_ARG, "NULL argument");
-    if (d->device < 0) return fail(LUTLDPC_ERR_STATE, "decoder was created without a device (host-only handle)");
-    if (B <= 0) return fail(LUTLDPC_ERR_ARG, "B must be positive");
-    HIP_TRY(hipSetDevice(d->device));
-    size_t n = (size_t)B * (size_t)d->nvar;
-    HIP_TRY(d->d_in_cha.alloc(n)); HIP_TRY(d->d_in_msg.alloc(n)); HIP_TRY(d->d_out_bits.alloc(n)); HIP_TRY(d->d_out_iters.alloc((size_t)B));
-    HIP_TRY(hipMemcpyAsync(d->d_in_cha.p, cha, n, hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(d->d_in_msg.p, msg0, n, hipMemcpyHostToDevice, d->stream));
-    int rc = decode_device(d, d->d_in_cha.p, d->d_in_msg.p, B, d->d_out_bits.p, d->d_out_iters.p);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out_bits, d->d_out_bits.p, n, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipMemcpyAsync(out_iters, d->d_out_iters.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipStreamSynchronize(d->stream));
-    return LUTLDPC_OK;
+    int rc = batch_entry(d, B);
+    if (rc || (rc = labels_from_host(d, cha, msg0, B))) return rc;
+    return decode_staged_labels(d, B, out_bits, out_iters);
 }
 
 // lut_decode of a small batch with the message dumps of output_verbosity = level (2: initial + after every variable update,
@@ -308,13 +317,15 @@ int lutldpc_decoder_decode_batch_trace(lutldpc_decoder *d, const uint8_t *cha, c
                                        uint8_t *trace, int64_t trace_cap, int32_t *n_dumps) {
     if (!d || !cha || !msg0 || !out_bits || !out_iters || !trace) return fail(LUTLDPC_ERR_ARG, "NULL argument");
     if (level < 2 || level > 3) return fail(LUTLDPC_ERR_ARG, "trace level must be 2 or 3");
-    if (B <= 0 || B > 4096) return fail(LUTLDPC_ERR_ARG, "the message trace is a debug path: 1..4096 frames");
+    int rc = batch_entry(d, B);
+    if (rc) return rc;
+    if (B > 4096) return fail(LUTLDPC_ERR_ARG, "the message trace is a debug path: 1..4096 frames");
     const int64_t need = (int64_t)(1 + d->max_iters * (level - 1)) * B * d->E;
     if (trace_cap < need) return fail(LUTLDPC_ERR_ARG, "trace buffer too small: " + std::to_string(need) + " bytes needed");
+    TraceScope scope(d);
     d->trace.level = level; d->trace.host = trace; d->trace.cap = (size_t)trace_cap; d->trace.n = 0; d->trace.B = B;
-    const int rc = lutldpc_decoder_decode_batch(d, cha, msg0, B, out_bits, out_iters);
+    if ((rc = labels_from_host(d, cha, msg0, B)) == LUTLDPC_OK) rc = decode_staged_labels(d, B, out_bits, out_iters);
     if (n_dumps) *n_dumps = d->trace.n;
-    d->trace = lutldpc_decoder::Trace();
     return rc;
 }
 
@@ -322,28 +333,21 @@ int lutldpc_decoder_decode_llr_batch(lutldpc_decoder *d, const double *llr, int 
                                      const double *qb_Msg, int n_qb_Msg, int mode, const int32_t *map,
                                      uint8_t *out_bits, int32_t *out_iters) {
     if (!d || !llr || !qb_Cha || !out_bits || !out_iters) return fail(LUTLDPC_ERR_ARG, "NULL argument");
-    if (d->device < 0) return fail(LUTLDPC_ERR_STATE, "decoder was created without a device (host-only handle)");
-    if (B <= 0) return fail(LUTLDPC_ERR_ARG, "B must be positive");
+    int rc = batch_entry(d, B);
+    if (rc) return rc;
     if (n_qb_Cha != d->Nq_Cha - 1) return fail(LUTLDPC_ERR_ARG, "qb_Cha must hold Nq_Cha-1 boundaries");
     if (mode == 0 && (!qb_Msg || n_qb_Msg != d->Nq_Msg[0] - 1)) return fail(LUTLDPC_ERR_ARG, "qb_Msg must hold Nq_Msg[0]-1 boundaries");
     if (mode == 1 && !map) return fail(LUTLDPC_ERR_ARG, "QCHA mode needs cha2msg_map");
     if (mode != 0 && mode != 1) return fail(LUTLDPC_ERR_ARG, "initial_message_mode must be 0 (CONT) or 1 (QCHA)");   // src/LDPC_Code_LUT.cpp:218-220
-    HIP_TRY(hipSetDevice(d->device));
     size_t n = (size_t)B * (size_t)d->nvar;
-    HIP_TRY(d->d_llr.alloc(n)); HIP_TRY(d->d_in_cha.alloc(n)); HIP_TRY(d->d_in_msg.alloc(n)); HIP_TRY(d->d_out_bits.alloc(n)); HIP_TRY(d->d_out_iters.alloc((size_t)B));
+    HIP_TRY(d->d_llr.alloc(n)); HIP_TRY(d->d_in_cha.alloc(n)); HIP_TRY(d->d_in_msg.alloc(n));
     HIP_TRY(d->d_qb_cha.alloc((size_t)n_qb_Cha)); HIP_TRY(d->d_qb_msg.alloc((size_t)(n_qb_Msg > 0 ? n_qb_Msg : 1))); HIP_TRY(d->d_map.alloc((size_t)d->Nq_Cha));
     HIP_TRY(hipMemcpyAsync(d->d_llr.p, llr, n * sizeof(double), hipMemcpyHostToDevice, d->stream));
     HIP_TRY(hipMemcpyAsync(d->d_qb_cha.p, qb_Cha, sizeof(double) * (size_t)n_qb_Cha, hipMemcpyHostToDevice, d->stream));
     if (mode == 0) HIP_TRY(hipMemcpyAsync(d->d_qb_msg.p, qb_Msg, sizeof(double) * (size_t)n_qb_Msg, hipMemcpyHostToDevice, d->stream));
     else HIP_TRY(hipMemcpyAsync(d->d_map.p, map, sizeof(int32_t) * (size_t)d->Nq_Cha, hipMemcpyHostToDevice, d->stream));
-    int rc = launch_quantize_llr(d, n, n_qb_Cha, n_qb_Msg, mode);
-    if (rc) return rc;
-    rc = decode_device(d, d->d_in_cha.p, d->d_in_msg.p, B, d->d_out_bits.p, d->d_out_iters.p);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out_bits, d->d_out_bits.p, n, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipMemcpyAsync(out_iters, d->d_out_iters.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipStreamSynchronize(d->stream));
-    return LUTLDPC_OK;
+    if ((rc = launch_quantize_llr(d, n, n_qb_Cha, n_qb_Msg, mode))) return rc;
+    return decode_staged_labels(d, B, out_bits, out_iters);
 }
 
 void *lutldpc_decoder_stream(lutldpc_decoder *d) { return d ? (void *)d->stream.s : nullptr; }

@@ -1,5 +1,6 @@
-// decoder_batch.hip -- the batch buffers of a decoder, the device arena of kernel parameter structures and the placement
-// search for the row buffers of a large batch.
+// decoder_batch.hip -- the batch buffers of a decoder, the device arena of kernel parameter structures, the placement
+// search for the row buffers of a large batch, and the entry layer: the guard, labels-in and results-out steps every batch
+// entry of the C-ABI shares.
 #include "decoder_state.hpp"
 
 #pragma GCC visibility push(hidden)
@@ -166,5 +167,53 @@ int check_batch_buffers(const lutldpc_decoder *d, int Bpad) {
     if (!d->d_fast_idx.p || !d->d_tables.p || !d->stream) return bad("static tables / stream");
     return LUTLDPC_OK;
 }
+
+// ----------------------------------------------------------------------------- entry layer (decoder_state.hpp)
+int device_entry(lutldpc_decoder *d) {
+    if (!d) return fail(LUTLDPC_ERR_ARG, "NULL decoder");
+    if (d->device < 0) return fail(LUTLDPC_ERR_STATE, "decoder was created without a device (host-only handle)");
+    HIP_TRY(hipSetDevice(d->device));
+    return LUTLDPC_OK;
+}
+int batch_entry(lutldpc_decoder *d, int B) {
+    if (!d) return fail(LUTLDPC_ERR_ARG, "NULL decoder");
+    if (B <= 0) return fail(LUTLDPC_ERR_ARG, "B must be positive");
+    return device_entry(d);
+}
+
+int tiles_from_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d_msg0, int B) {
+    int rc = ensure_batch(d, B);
+    if (rc) return rc;
+    const int G = d->bpad(B) / d->tile();
+    Timed t(d, LUTLDPC_K_LAYOUT);
+    if ((rc = launch_transpose_in(d, d_cha, d->d_cha_t.p, B, G, d->Nq_Cha))) return rc;
+    return launch_transpose_in(d, d_msg0, d->d_msg0_t.p, B, G, d->Nq_Msg[0]);
+}
+int labels_from_host(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0, int B) {
+    const size_t n = (size_t)B * (size_t)d->nvar;
+    HIP_TRY(d->d_in_cha.alloc(n)); HIP_TRY(d->d_in_msg.alloc(n));
+    HIP_TRY(hipMemcpyAsync(d->d_in_cha.p, cha, n, hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(hipMemcpyAsync(d->d_in_msg.p, msg0, n, hipMemcpyHostToDevice, d->stream));
+    return LUTLDPC_OK;
+}
+int tiles_from_host(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0, int B) {
+    if (int rc = labels_from_host(d, cha, msg0, B)) return rc;
+    return tiles_from_device(d, d->d_in_cha.p, d->d_in_msg.p, B);
+}
+
+int copy_to_host(lutldpc_decoder *d, void *host_dst, const void *src, size_t bytes) {
+    HIP_TRY(hipMemcpyAsync(host_dst, src, bytes, hipMemcpyDeviceToHost, d->stream));
+    return LUTLDPC_OK;
+}
+int rows_to_host(lutldpc_decoder *d, const uint8_t *rows, uint8_t *host_dst, int B, int n_rows) {
+    const size_t n = (size_t)B * (size_t)(n_rows > 0 ? n_rows : d->nvar);
+    HIP_TRY(d->d_out_bits.alloc(n));
+    {
+        Timed t(d, LUTLDPC_K_LAYOUT);
+        if (int rc = launch_transpose_out(d, rows, d->d_out_bits.p, B, d->bpad(B) / d->tile(), n_rows)) return rc;
+    }
+    return copy_to_host(d, host_dst, d->d_out_bits.p, n);
+}
+int iters_to_host(lutldpc_decoder *d, int32_t *dst, int B) { return copy_to_host(d, dst, d->d_iters.p, sizeof(int32_t) * (size_t)B); }
 
 #pragma GCC visibility pop

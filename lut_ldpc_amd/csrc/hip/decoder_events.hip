@@ -100,30 +100,14 @@ int lutldpc_decoder_events_batch(lutldpc_decoder *d, const uint8_t *cha, const u
     int rc;
     if ((rc = event_request_check(req))) return rc;
     if (!d || !cha || !msg0) return fail(LUTLDPC_ERR_ARG, "NULL argument");
-    if (B <= 0 || K_info < 0 || K_info > d->nvar) return fail(LUTLDPC_ERR_ARG, "bad B / K_info");
-    if (d->device < 0) return fail(LUTLDPC_ERR_STATE, "decoder was created without a device (host-only handle)");
-    HIP_TRY(hipSetDevice(d->device));
-    const size_t n = (size_t)B * (size_t)d->nvar;
-    HIP_TRY(d->d_in_cha.alloc(n)); HIP_TRY(d->d_in_msg.alloc(n));
-    HIP_TRY(hipMemcpyAsync(d->d_in_cha.p, cha, n, hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(d->d_in_msg.p, msg0, n, hipMemcpyHostToDevice, d->stream));
-    if ((rc = ensure_batch(d, B))) return rc;
-    const int G = d->bpad(B) / d->tile();
-    {
-        Timed t(d, LUTLDPC_K_LAYOUT);
-        if ((rc = launch_transpose_in(d, d->d_in_cha.p, d->d_cha_t.p, B, G, d->Nq_Cha))) return rc;
-        if ((rc = launch_transpose_in(d, d->d_in_msg.p, d->d_msg0_t.p, B, G, d->Nq_Msg[0]))) return rc;
-    }
-    if (sent && (rc = sent_rows_from_host(d, sent, B))) return rc;
+    if (K_info < 0 || K_info > d->nvar) return fail(LUTLDPC_ERR_ARG, "bad K_info");
+    if ((rc = batch_entry(d, B))) return rc;
+    const uint8_t *sent_rows = nullptr;
+    if ((rc = tiles_from_host(d, cha, msg0, B)) || (rc = sent_rows_from_host(d, sent, B, &sent_rows))) return rc;
     if ((rc = decode_tiles(d, B))) return rc;
-    if (out_bits) {
-        Timed t(d, LUTLDPC_K_LAYOUT);
-        HIP_TRY(d->d_out_bits.alloc(n));
-        if ((rc = launch_transpose_out(d, d->d_hard.p, d->d_out_bits.p, B, G))) return rc;
-        HIP_TRY(hipMemcpyAsync(out_bits, d->d_out_bits.p, n, hipMemcpyDeviceToHost, d->stream));
-    }
-    if (out_iters) HIP_TRY(hipMemcpyAsync(out_iters, d->d_iters.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, d->stream));
-    return capture_events(d, B, K_info, sent ? d->d_sent.p : nullptr, nullptr, req);
+    if (out_bits && (rc = rows_to_host(d, d->d_hard.p, out_bits, B))) return rc;
+    if (out_iters && (rc = iters_to_host(d, out_iters, B))) return rc;
+    return capture_events(d, B, K_info, sent_rows, nullptr, req);
 }
 
 int lutldpc_decoder_sim_batch_events(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0,
@@ -132,7 +116,7 @@ int lutldpc_decoder_sim_batch_events(lutldpc_decoder *d, const lutldpc_channel_c
     int rc;
     if ((rc = event_request_check(req))) return rc;
     if (!d || !frame_stats) return fail(LUTLDPC_ERR_ARG, "NULL argument");
-    if (B <= 0 || K_info < 0 || K_info > d->nvar) return fail(LUTLDPC_ERR_ARG, "bad B / K_info");
+    if (K_info < 0 || K_info > d->nvar) return fail(LUTLDPC_ERR_ARG, "bad K_info");
     return sim_batch_impl(d, cells, seed, stream, frame0, B, device_codewords ? nullptr : codewords, device_codewords != 0, K_info, frame_stats, nullptr, nullptr, req);
 }
 

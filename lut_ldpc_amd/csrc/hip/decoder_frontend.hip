@@ -28,21 +28,14 @@ int fill_cells(const lutldpc_channel_cells *c, const lutldpc_decoder *d, Channel
     return LUTLDPC_OK;
 }
 
-// sampler -> d_cha_t / d_msg0_t (tile layout); stats zeroed and slicer errors accumulated.  sent_rows (device, d_sent): the
-// codewords as sent-bit rows, made by encode_tiles; otherwise codewords_host (frame-major, uploaded) or none (all-zero)
-int sample_tiles(lutldpc_decoder *d, const ChannelCells &C, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *codewords_host,
-                 const uint8_t *sent_rows) {
+// sampler -> d_cha_t / d_msg0_t (tile layout); stats zeroed and slicer errors accumulated.  sent_rows: the sent bits of the
+// batch (sent_rows_of), null = all-zero codeword
+int sample_tiles(lutldpc_decoder *d, const ChannelCells &C, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *sent_rows) {
     int rc = ensure_batch(d, B);
     if (rc) return rc;
     const int Bpad = d->bpad(B), G = Bpad / d->tile(), N = d->nvar;
     HIP_TRY(d->d_stats.alloc((size_t)Bpad * 4));
     HIP_TRY(hipMemsetAsync(d->d_stats.p, 0, sizeof(int32_t) * (size_t)Bpad * 4, d->stream));
-    const uint8_t *cw = nullptr;
-    if (codewords_host) {
-        HIP_TRY(d->d_codewords.alloc((size_t)B * N));
-        HIP_TRY(hipMemcpyAsync(d->d_codewords.p, codewords_host, (size_t)B * N, hipMemcpyHostToDevice, d->stream));
-        cw = d->d_codewords.p;
-    }
     Timed t(d, LUTLDPC_K_FRONTEND);
     const int ppt = 8, npairs = (N + 1) / 2;
     dim3 grid((unsigned)((npairs + 4 * ppt - 1) / (4 * ppt)), (unsigned)G);
@@ -51,8 +44,8 @@ int sample_tiles(lutldpc_decoder *d, const ChannelCells &C, uint64_t seed, uint3
         PACK_DISPATCH(d, launch_k(sample_labels_kernel<PK, true>, grid, dim3(256), 0, d->stream, dC, (uint32_t)seed, (uint32_t)(seed >> 32), stream, frame0, B, N,
                            sent_rows, d->d_cha_t.p, d->d_msg0_t.p, d->d_stats.p, ppt));
     else
-        PACK_DISPATCH(d, launch_k(sample_labels_kernel<PK>, grid, dim3(256), 0, d->stream, dC, (uint32_t)seed, (uint32_t)(seed >> 32), stream, frame0, B, N, cw,
-                           d->d_cha_t.p, d->d_msg0_t.p, d->d_stats.p, ppt));
+        PACK_DISPATCH(d, launch_k(sample_labels_kernel<PK>, grid, dim3(256), 0, d->stream, dC, (uint32_t)seed, (uint32_t)(seed >> 32), stream, frame0, B, N,
+                           sent_rows, d->d_cha_t.p, d->d_msg0_t.p, d->d_stats.p, ppt));
     LAUNCH_CHECK();
     return LUTLDPC_OK;
 }
@@ -82,58 +75,47 @@ static int launch_sent_to_bytes(lutldpc_decoder *d, uint8_t *dst, int B) {
     return LUTLDPC_OK;
 }
 
+// The one device form of the sent bits of a batch: sent-bit rows in d_sent -- made by the encoder from (seed, stream, frame)
+// (device_codewords), or converted once from the caller's frame-major bytes (codewords, host) -- or *rows = null: the all-zero
+// codeword.  Sampler, error counters, histograms and the capture all read this.
+int sent_rows_of(lutldpc_decoder *d, const uint8_t *codewords, bool device_codewords, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
+                 const uint8_t **rows) {
+    if (!device_codewords) return sent_rows_from_host(d, codewords, B, rows);
+    const int rc = encode_tiles(d, seed, stream, frame0, B);
+    *rows = d->d_sent.p;
+    return rc;
+}
+
 // lutldpc_decoder_sim_batch (codewords: host, frame-major, or null) and lutldpc_decoder_sim_batch_random (device_codewords:
 // made by the encoder on the device from (seed, stream, frame))
 int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
                    const uint8_t *codewords, bool device_codewords, int K_info, int32_t *frame_stats, uint8_t *cha_out, uint8_t *bits_out, lutldpc_event_request *req) {
     if (!d || !frame_stats) return fail(LUTLDPC_ERR_ARG, "NULL argument");
-    if (d->device < 0) return fail(LUTLDPC_ERR_STATE, "decoder was created without a device (host-only handle)");
-    if (B <= 0 || K_info < 0 || K_info > d->nvar) return fail(LUTLDPC_ERR_ARG, "bad B / K_info");
+    int rc = batch_entry(d, B);
+    if (rc) return rc;
+    if (K_info < 0 || K_info > d->nvar) return fail(LUTLDPC_ERR_ARG, "bad K_info");
     if (device_codewords && !d->gen_set) return fail(LUTLDPC_ERR_STATE, "sim_batch_random: no generator set (lutldpc_decoder_set_generator)");
     ChannelCells C;
-    int rc = fill_cells(cells, d, C);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(d->device));
-    if (device_codewords) {
-        if ((rc = ensure_batch(d, B))) return rc;
-        if ((rc = encode_tiles(d, seed, stream, frame0, B))) return rc;
-    }
-    if ((rc = sample_tiles(d, C, seed, stream, frame0, B, codewords, device_codewords ? d->d_sent.p : nullptr))) return rc;
+    if ((rc = fill_cells(cells, d, C))) return rc;
+    const uint8_t *sent_rows = nullptr;
+    if ((rc = sent_rows_of(d, codewords, device_codewords, seed, stream, frame0, B, &sent_rows))) return rc;
+    if ((rc = sample_tiles(d, C, seed, stream, frame0, B, sent_rows))) return rc;
     if ((rc = decode_tiles(d, B))) return rc;
     {
         Timed t(d, LUTLDPC_K_FRONTEND);
         const int Bpad = d->bpad(B), G = Bpad / d->tile(), rpw = 64;
         const int rows = K_info > 0 ? K_info : 1;
         const dim3 grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)), (unsigned)G);
-        if (device_codewords)
-            PACK_DISPATCH(d, launch_k(count_errors_kernel<PK, true>, grid, dim3(256), 0, d->stream, d->d_hard.p, d->d_sent.p, B, d->nvar, K_info, d->d_iters.p,
-                               d->d_stats.p, rpw));
+        if (sent_rows)
+            PACK_DISPATCH(d, launch_k(count_errors_kernel<PK, true>, grid, dim3(256), 0, d->stream, d->d_hard.p, sent_rows, B, d->nvar, K_info, d->d_iters.p, d->d_stats.p, rpw));
         else
-            PACK_DISPATCH(d, launch_k(count_errors_kernel<PK>, grid, dim3(256), 0, d->stream, d->d_hard.p,
-                               codewords ? d->d_codewords.p : nullptr, B, d->nvar, K_info, d->d_iters.p, d->d_stats.p, rpw));
+            PACK_DISPATCH(d, launch_k(count_errors_kernel<PK>, grid, dim3(256), 0, d->stream, d->d_hard.p, sent_rows, B, d->nvar, K_info, d->d_iters.p, d->d_stats.p, rpw));
         LAUNCH_CHECK();
     }
-    HIP_TRY(hipMemcpyAsync(frame_stats, d->d_stats.p, sizeof(int32_t) * (size_t)B * 4, hipMemcpyDeviceToHost, d->stream));
-    if (cha_out || bits_out) {
-        const int Bpad = d->bpad(B), G = Bpad / d->tile(), N = d->nvar;
-        const size_t n = (size_t)B * N;
-        HIP_TRY(d->d_out_bits.alloc(n));
-        if (cha_out) {
-            if ((rc = launch_transpose_out(d, d->d_cha_t.p, d->d_out_bits.p, B, G))) return rc;
-            LAUNCH_CHECK();
-            HIP_TRY(hipMemcpyAsync(cha_out, d->d_out_bits.p, n, hipMemcpyDeviceToHost, d->stream));
-        }
-        if (bits_out) {
-            if ((rc = launch_transpose_out(d, d->d_hard.p, d->d_out_bits.p, B, G))) return rc;
-            LAUNCH_CHECK();
-            HIP_TRY(hipMemcpyAsync(bits_out, d->d_out_bits.p, n, hipMemcpyDeviceToHost, d->stream));
-        }
-    }
-    if (req) {
-        // the capture reads sent-bit rows in all three cases: the encoder's, the caller's codewords converted once, or none
-        if (codewords && (rc = sent_rows_from_device(d, B))) return rc;
-        if ((rc = capture_events(d, B, K_info, device_codewords || codewords ? d->d_sent.p : nullptr, d->d_stats.p, req))) return rc;
-    }
+    if ((rc = copy_to_host(d, frame_stats, d->d_stats.p, sizeof(int32_t) * (size_t)B * 4))) return rc;
+    if (cha_out && (rc = rows_to_host(d, d->d_cha_t.p, cha_out, B))) return rc;
+    if (bits_out && (rc = rows_to_host(d, d->d_hard.p, bits_out, B))) return rc;
+    if (req && (rc = capture_events(d, B, K_info, sent_rows, d->d_stats.p, req))) return rc;
     HIP_TRY(hipStreamSynchronize(d->stream));
     return LUTLDPC_OK;
 }
@@ -156,9 +138,8 @@ int lutldpc_decoder_set_generator(lutldpc_decoder *d, int K, int R, const uint64
     if (!d) return fail(LUTLDPC_ERR_ARG, "NULL decoder");
     if (!rows) return fail(LUTLDPC_ERR_ARG, "generator rows are NULL");
     if (K < 1 || R < 0 || K + R != d->nvar) return fail(LUTLDPC_ERR_ARG, "generator: K + R must equal nvar (K >= 1)");
-    if (d->device < 0) return fail(LUTLDPC_ERR_STATE, "decoder was created without a device (host-only handle)");
+    if (int rc = device_entry(d)) return rc;
     if (K > kEncMaxInfoBits) return fail(LUTLDPC_ERR_UNSUPPORTED, "generator: more than 8192 information bits (device encoder limit)");
-    HIP_TRY(hipSetDevice(d->device));
     const int WK = (K + 63) / 64, W32p = 4 * ((K + 127) / 128), Rp = (R + kEncTileRows - 1) / kEncTileRows * kEncTileRows;
     std::vector<uint32_t> a((size_t)std::max(Rp, 1) * W32p, 0u);
     for (int i = 0; i < R; i++)
@@ -176,17 +157,12 @@ int lutldpc_decoder_set_generator(lutldpc_decoder *d, int K, int R, const uint64
 }
 
 int lutldpc_decoder_encode_random(lutldpc_decoder *d, uint64_t seed, uint32_t stream, uint64_t frame0, int B, uint8_t *codewords) {
-    if (!d) return fail(LUTLDPC_ERR_ARG, "NULL decoder");
-    if (B <= 0) return fail(LUTLDPC_ERR_ARG, "B must be positive");
-    if (d->device < 0) return fail(LUTLDPC_ERR_STATE, "decoder was created without a device (host-only handle)");
-    HIP_TRY(hipSetDevice(d->device));
-    int rc = encode_tiles(d, seed, stream, frame0, B);
-    if (rc) return rc;
+    int rc = batch_entry(d, B);
+    if (rc || (rc = encode_tiles(d, seed, stream, frame0, B))) return rc;
     if (codewords) {
         const size_t n = (size_t)B * d->nvar;
         HIP_TRY(d->d_out_bits.alloc(n));
-        if ((rc = launch_sent_to_bytes(d, d->d_out_bits.p, B))) return rc;
-        HIP_TRY(hipMemcpyAsync(codewords, d->d_out_bits.p, n, hipMemcpyDeviceToHost, d->stream));
+        if ((rc = launch_sent_to_bytes(d, d->d_out_bits.p, B)) || (rc = copy_to_host(d, codewords, d->d_out_bits.p, n))) return rc;
     }
     HIP_TRY(hipStreamSynchronize(d->stream));
     return LUTLDPC_OK;
@@ -195,20 +171,14 @@ int lutldpc_decoder_encode_random(lutldpc_decoder *d, uint64_t seed, uint32_t st
 int lutldpc_decoder_sample_labels(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
                                   const uint8_t *codewords, uint8_t *cha, uint8_t *msg0) {
     if (!d || !cha || !msg0) return fail(LUTLDPC_ERR_ARG, "NULL argument");
-    if (d->device < 0) return fail(LUTLDPC_ERR_STATE, "decoder was created without a device (host-only handle)");
-    if (B <= 0) return fail(LUTLDPC_ERR_ARG, "B must be positive");
-    ChannelCells C;
-    int rc = fill_cells(cells, d, C);
+    int rc = batch_entry(d, B);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(d->device));
-    if ((rc = sample_tiles(d, C, seed, stream, frame0, B, codewords))) return rc;
-    const int Bpad = d->bpad(B), G = Bpad / d->tile(), N = d->nvar;
-    const size_t n = (size_t)B * N;
-    HIP_TRY(d->d_in_cha.alloc(n)); HIP_TRY(d->d_in_msg.alloc(n));
-    if ((rc = launch_transpose_out(d, d->d_cha_t.p, d->d_in_cha.p, B, G))) return rc;
-    if ((rc = launch_transpose_out(d, d->d_msg0_t.p, d->d_in_msg.p, B, G))) return rc;
-    HIP_TRY(hipMemcpyAsync(cha, d->d_in_cha.p, n, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(hipMemcpyAsync(msg0, d->d_in_msg.p, n, hipMemcpyDeviceToHost, d->stream));
+    ChannelCells C;
+    if ((rc = fill_cells(cells, d, C))) return rc;
+    const uint8_t *sent_rows = nullptr;
+    if ((rc = sent_rows_from_host(d, codewords, B, &sent_rows))) return rc;
+    if ((rc = sample_tiles(d, C, seed, stream, frame0, B, sent_rows))) return rc;
+    if ((rc = rows_to_host(d, d->d_cha_t.p, cha, B)) || (rc = rows_to_host(d, d->d_msg0_t.p, msg0, B))) return rc;
     HIP_TRY(hipStreamSynchronize(d->stream));
     return LUTLDPC_OK;
 }

@@ -5,7 +5,8 @@
 //   decoder.hip            C-ABI: create (knob table) / destroy / exit conditions / decode entries / profiling / describe / selftest
 //   decoder_setup.hip      fills the tree plans (TreeClassPlan: every compiled form of a tree, add_forms) and the dense index tables
 //                          (NodeClass: where each sits), chain fusion, JIT registry, static uploads
-//   decoder_batch.hip      batch buffers, parameter arena, placement search
+//   decoder_batch.hip      batch buffers, parameter arena, placement search; the entry layer of the batch entries: one guard
+//                          (batch_entry), labels in (tiles_from_host / _device), results out (rows_to_host, iters_to_host)
 //   decoder_stream.hip     streaming decode: class parameters (the one builder and validator of ClassParams), per-class launches,
 //                          decision pass, graph replay, message trace   (kernels_generic.hpp)
 //   decoder_skew.hip       skewed two-half pipeline through pass_fused_kernel, compaction                     (kernels_compact.hpp)
@@ -216,7 +217,7 @@ struct lutldpc_decoder {
     DevBuf<int32_t> d_out_iters;
     DevBuf<double> d_llr, d_qb_cha, d_qb_msg;
     DevBuf<int32_t> d_map;
-    DevBuf<uint8_t> d_codewords;
+    DevBuf<uint8_t> d_codewords;                      // upload staging of sent_rows_from_host; no kernel but its conversion reads it
     DevBuf<int32_t> d_stats;
     // systematic generator of the random codewords made on the device (kernels_encode.hpp): gen_R parity rows over gen_K
     // information bits, stored as whole 32-row tiles of gen_W32p = 4*ceil(K/128) dwords; d_sent: the sent-bit rows of a batch
@@ -372,6 +373,21 @@ bool jit_class_source(const lutldpc_decoder *d, int kind, size_t s, size_t i, st
 // ---- decoder_batch.hip
 int ensure_batch(lutldpc_decoder *d, int B);
 int check_batch_buffers(const lutldpc_decoder *d, int Bpad);
+// The entry layer: what every batch entry of the C-ABI does around decode_tiles.
+// The guard, in the order of the header's error contract: NULL handle, B <= 0 (LUTLDPC_ERR_ARG), host-only handle
+// (LUTLDPC_ERR_STATE), then the handle's device made current.  device_entry: the same without a batch (set_generator).
+int device_entry(lutldpc_decoder *d);
+int batch_entry(lutldpc_decoder *d, int B);
+// labels in: frame-major labels of B frames -> d_cha_t / d_msg0_t.  labels_from_host uploads them to d_in_cha / d_in_msg and stops
+// there (decode_device decides whether rows are needed), tiles_from_host goes on to the rows.
+int tiles_from_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d_msg0, int B);
+int labels_from_host(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0, int B);
+int tiles_from_host(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0, int B);
+// results out, asynchronous on the decoder's stream.  Rows are staged through d_out_bits (copies on one stream are ordered: a
+// caller may fetch several row sets one after the other).
+int copy_to_host(lutldpc_decoder *d, void *host_dst, const void *src, size_t bytes);
+int rows_to_host(lutldpc_decoder *d, const uint8_t *rows, uint8_t *host_dst, int B, int n_rows = 0);      // n_rows = 0: nvar
+int iters_to_host(lutldpc_decoder *d, int32_t *dst, int B);                                                // d_iters of the last decode_tiles
 
 // ---- decoder_stream.hip (home of the kernels of kernels_generic.hpp)
 hipError_t preload_stream_kernels();
@@ -425,10 +441,13 @@ int launch_resident(lutldpc_decoder *d, int G, int B);
 // ---- decoder_frontend.hip (home of the kernels of kernels_frontend.hpp and kernels_encode.hpp)
 hipError_t preload_frontend_kernels();
 int fill_cells(const lutldpc_channel_cells *c, const lutldpc_decoder *d, ChannelCells &C);
-// sampler -> d_cha_t / d_msg0_t; the sent bits: sent_rows (device, sent-bit rows), else codewords_host (frame-major), else all-zero
-int sample_tiles(lutldpc_decoder *d, const ChannelCells &C, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *codewords_host,
-                 const uint8_t *sent_rows = nullptr);
+// sampler -> d_cha_t / d_msg0_t; sent_rows: the sent bits as sent-bit rows (device), null = all-zero codeword
+int sample_tiles(lutldpc_decoder *d, const ChannelCells &C, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *sent_rows);
 int encode_tiles(lutldpc_decoder *d, uint64_t seed, uint32_t stream, uint64_t frame0, int B);       // random codewords -> d_sent
+// the sent bits of a batch in their one device form: *rows = d_sent filled by the encoder (device_codewords) or from the caller's
+// frame-major bytes (codewords, host), or null = all-zero codeword
+int sent_rows_of(lutldpc_decoder *d, const uint8_t *codewords, bool device_codewords, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
+                 const uint8_t **rows);
 // lutldpc_decoder_sim_batch / _random; req != null: the capture of decoder_events.hip on top (lutldpc_decoder_sim_batch_events)
 int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *codewords,
                    bool device_codewords, int K_info, int32_t *frame_stats, uint8_t *cha_out, uint8_t *bits_out, lutldpc_event_request *req = nullptr);
@@ -436,8 +455,8 @@ int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint6
 // ---- decoder_stats.hip (home of the kernels of kernels_stats.hpp)
 hipError_t preload_stats_kernels();
 int hist_dump(lutldpc_decoder *d);           // one dump of a counted decode: the message rows into d->trace.hist (decode_tiles_launch)
-int sent_rows_from_device(lutldpc_decoder *d, int B);                              // d_codewords (frame-major, B frames) -> d_sent
-int sent_rows_from_host(lutldpc_decoder *d, const uint8_t *codewords, int B);     // host frame-major codewords -> d_codewords -> d_sent
+// host frame-major codewords (bytes 0 / 1) -> d_codewords -> *rows = d_sent; codewords = null: *rows = null (all-zero codeword)
+int sent_rows_from_host(lutldpc_decoder *d, const uint8_t *codewords, int B, const uint8_t **rows);
 
 // ---- decoder_events.hip (home of the kernels of kernels_events.hpp)
 hipError_t preload_events_kernels();

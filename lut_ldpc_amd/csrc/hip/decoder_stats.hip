@@ -71,14 +71,12 @@ static int hist_check_args(lutldpc_decoder *d, int B, int level, int mode, int n
     if (!d || !hist) return fail(LUTLDPC_ERR_ARG, "NULL argument");
     if (level < 2 || level > 3) return fail(LUTLDPC_ERR_ARG, "histogram level must be 2 or 3");
     if (mode < 0 || mode > 1) return fail(LUTLDPC_ERR_ARG, "histogram mode must be 0 (all) or 1 (active)");
-    if (B <= 0) return fail(LUTLDPC_ERR_ARG, "B must be positive");
     if (n_labels < max_msg_alphabet(d)) return fail(LUTLDPC_ERR_ARG, "n_labels below the largest message alphabet (" + std::to_string(max_msg_alphabet(d)) + ")");
     const int nd = 1 + d->max_iters * (level - 1);
     const int64_t need = (int64_t)nd * d->hist_groups * 2 * n_labels;
     if (hist_cap < need) return fail(LUTLDPC_ERR_ARG, "hist too small: " + std::to_string(need) + " int64 needed");
     *n_dumps_out = nd;
-    if (d->device < 0) return fail(LUTLDPC_ERR_STATE, "decoder was created without a device (host-only handle)");
-    return LUTLDPC_OK;
+    return batch_entry(d, B);
 }
 
 // Does a normal decode of G frame groups move channel rows?  Only the compaction of the skewed pipeline does (launch_compaction
@@ -88,22 +86,20 @@ static bool decode_moves_labels(const lutldpc_decoder *d, int G) {
     return !resident_active(d) && d->opt.skew && d->skew_ok && d->psc && compaction_on(d, G);
 }
 
-// frame-major codewords of B frames in d_codewords -> d_sent (sent-bit rows of bpad(B) frames)
-int sent_rows_from_device(lutldpc_decoder *d, int B) {
+// host frame-major codewords of B frames (bytes 0 / 1: bit 0 counts) -> d_codewords (upload staging) -> *rows = d_sent (sent-bit
+// rows of bpad(B) frames); codewords = null: *rows = null, the all-zero codeword
+int sent_rows_from_host(lutldpc_decoder *d, const uint8_t *codewords, int B, const uint8_t **rows) {
+    *rows = nullptr;
+    if (!codewords) return LUTLDPC_OK;
     const int G = d->bpad(B) / d->tile(), N = d->nvar;
     const size_t n_bytes = (size_t)G * N * (d->pack == 2 ? sent_row_bytes<2>() : sent_row_bytes<1>());
-    HIP_TRY(d->d_sent.alloc(n_bytes));
+    HIP_TRY(d->d_codewords.alloc((size_t)B * N)); HIP_TRY(d->d_sent.alloc(n_bytes));
+    HIP_TRY(hipMemcpyAsync(d->d_codewords.p, codewords, (size_t)B * N, hipMemcpyHostToDevice, d->stream));
     Timed t(d, LUTLDPC_K_LAYOUT);
     PACK_DISPATCH(d, launch_k(bytes_to_sent_rows_kernel<PK>, dim3((unsigned)((n_bytes + 255) / 256)), dim3(256), 0, d->stream, d->d_codewords.p, B, N, n_bytes, d->d_sent.p));
     LAUNCH_CHECK();
+    *rows = d->d_sent.p;
     return LUTLDPC_OK;
-}
-
-// host frame-major codewords -> d_sent
-int sent_rows_from_host(lutldpc_decoder *d, const uint8_t *codewords, int B) {
-    HIP_TRY(d->d_codewords.alloc((size_t)B * d->nvar));
-    HIP_TRY(hipMemcpyAsync(d->d_codewords.p, codewords, (size_t)B * d->nvar, hipMemcpyHostToDevice, d->stream));
-    return sent_rows_from_device(d, B);
 }
 
 // restores the exit conditions and the trace sink of a handle on every way out of the counted pass
@@ -127,14 +123,8 @@ static int histogram_tiles(lutldpc_decoder *d, int B, int level, int mode, int n
     HIP_TRY(hipMemsetAsync(d->d_hist.p, 0, n_hist * sizeof(unsigned long long), d->stream));
     if (mode == 1 || out_bits || out_iters) {
         if ((rc = decode_tiles(d, B))) return rc;
-        Timed t(d, LUTLDPC_K_LAYOUT);
-        if (out_bits) {
-            const size_t n = (size_t)B * d->nvar;
-            HIP_TRY(d->d_out_bits.alloc(n));
-            if ((rc = launch_transpose_out(d, d->d_hard.p, d->d_out_bits.p, B, G))) return rc;
-            HIP_TRY(hipMemcpyAsync(out_bits, d->d_out_bits.p, n, hipMemcpyDeviceToHost, d->stream));
-        }
-        if (out_iters) HIP_TRY(hipMemcpyAsync(out_iters, d->d_iters.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, d->stream));
+        if (out_bits && (rc = rows_to_host(d, d->d_hard.p, out_bits, B))) return rc;
+        if (out_iters && (rc = iters_to_host(d, out_iters, B))) return rc;
     }
     {
         Timed t(d, LUTLDPC_K_LAYOUT);
@@ -152,7 +142,7 @@ static int histogram_tiles(lutldpc_decoder *d, int B, int level, int mode, int n
     }
     if (rc) return rc;
     std::vector<unsigned long long> h(n_hist);
-    HIP_TRY(hipMemcpyAsync(h.data(), d->d_hist.p, n_hist * sizeof(unsigned long long), hipMemcpyDeviceToHost, d->stream));
+    if ((rc = copy_to_host(d, h.data(), d->d_hist.p, n_hist * sizeof(unsigned long long)))) return rc;
     HIP_TRY(hipStreamSynchronize(d->stream));
     for (size_t i = 0; i < n_hist; i++) hist[i] += (int64_t)h[i];
     return LUTLDPC_OK;
@@ -184,21 +174,11 @@ int lutldpc_decoder_histogram_batch(lutldpc_decoder *d, const uint8_t *cha, cons
     int nd = 0, rc;
     if ((rc = hist_check_args(d, B, level, mode, n_labels, hist, hist_cap, &nd))) return rc;
     if (!cha || !msg0) return fail(LUTLDPC_ERR_ARG, "NULL argument");
-    HIP_TRY(hipSetDevice(d->device));
-    const size_t n = (size_t)B * (size_t)d->nvar;
-    HIP_TRY(d->d_in_cha.alloc(n)); HIP_TRY(d->d_in_msg.alloc(n));
-    HIP_TRY(hipMemcpyAsync(d->d_in_cha.p, cha, n, hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(d->d_in_msg.p, msg0, n, hipMemcpyHostToDevice, d->stream));
-    if ((rc = ensure_batch(d, B))) return rc;
-    const int G = d->bpad(B) / d->tile();
-    auto fill = [&]() -> int {
-        Timed t(d, LUTLDPC_K_LAYOUT);
-        if (int r = launch_transpose_in(d, d->d_in_cha.p, d->d_cha_t.p, B, G, d->Nq_Cha)) return r;
-        return launch_transpose_in(d, d->d_in_msg.p, d->d_msg0_t.p, B, G, d->Nq_Msg[0]);
-    };
-    if ((rc = fill())) return rc;
-    if (sent && (rc = sent_rows_from_host(d, sent, B))) return rc;
-    if ((rc = histogram_tiles(d, B, level, mode, n_labels, sent ? d->d_sent.p : nullptr, fill, out_bits, out_iters, hist, nd))) return rc;
+    if ((rc = tiles_from_host(d, cha, msg0, B))) return rc;
+    const uint8_t *sent_rows = nullptr;
+    if ((rc = sent_rows_from_host(d, sent, B, &sent_rows))) return rc;
+    auto refill = [&]() -> int { return tiles_from_device(d, d->d_in_cha.p, d->d_in_msg.p, B); };       // (the uploaded labels are still there)
+    if ((rc = histogram_tiles(d, B, level, mode, n_labels, sent_rows, refill, out_bits, out_iters, hist, nd))) return rc;
     if (n_dumps) *n_dumps = nd;
     return LUTLDPC_OK;
 }
@@ -211,13 +191,9 @@ int lutldpc_decoder_sim_batch_histogram(lutldpc_decoder *d, const lutldpc_channe
     if (device_codewords && !d->gen_set) return fail(LUTLDPC_ERR_STATE, "sim_batch_histogram: no generator set (lutldpc_decoder_set_generator)");
     ChannelCells C;
     if ((rc = fill_cells(cells, d, C))) return rc;
-    HIP_TRY(hipSetDevice(d->device));
-    if ((rc = ensure_batch(d, B))) return rc;
-    // the sent bits always as sent-bit rows: from the encoder, or converted once from the caller's codewords
     const uint8_t *sent_rows = nullptr;
-    if (device_codewords) { if ((rc = encode_tiles(d, seed, stream, frame0, B))) return rc; sent_rows = d->d_sent.p; }
-    else if (codewords) { if ((rc = sent_rows_from_host(d, codewords, B))) return rc; sent_rows = d->d_sent.p; }
-    auto fill = [&]() -> int { return sample_tiles(d, C, seed, stream, frame0, B, nullptr, sent_rows); };   // (a pure function of seed, stream, frame)
+    if ((rc = sent_rows_of(d, codewords, device_codewords != 0, seed, stream, frame0, B, &sent_rows))) return rc;
+    auto fill = [&]() -> int { return sample_tiles(d, C, seed, stream, frame0, B, sent_rows); };   // (a pure function of seed, stream, frame)
     if ((rc = fill())) return rc;
     if ((rc = histogram_tiles(d, B, level, mode, n_labels, sent_rows, fill, nullptr, nullptr, hist, nd))) return rc;
     if (n_dumps) *n_dumps = nd;

@@ -473,22 +473,13 @@ int decode_tiles(lutldpc_decoder *d, int B) {
     return LUTLDPC_OK;
 }
 
-// The batched lut_decode (src/LDPC_Code_LUT.cpp:259-353) on device-resident frame-major labels.
+// The batched lut_decode (src/LDPC_Code_LUT.cpp:259-353) on device-resident frame-major labels (after the entry's batch_entry).
 int decode_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d_msg0, int B, uint8_t *d_out_bits, int32_t *d_out_iters) {
-    if (d->device < 0) return fail(LUTLDPC_ERR_STATE, "decoder was created without a device (host-only handle)");
-    if (B <= 0) return fail(LUTLDPC_ERR_ARG, "B must be positive");
-    HIP_TRY(hipSetDevice(d->device));
-    int rc = ensure_batch(d, B);
-    if (rc) return rc;
-    const int Bpad = d->bpad(B), G = Bpad / d->tile();
     // the LDS-resident decoder reads the frame-major labels and writes the frame-major bits itself
     const bool direct = resident_active(d) && d->opt.resident_fm && d->trace.level <= 1;
-    if (!direct) {
-        Timed t(d, LUTLDPC_K_LAYOUT);
-        if ((rc = launch_transpose_in(d, d_cha, d->d_cha_t.p, B, G, d->Nq_Cha))) return rc;
-        if ((rc = launch_transpose_in(d, d_msg0, d->d_msg0_t.p, B, G, d->Nq_Msg[0]))) return rc;
-        LAUNCH_CHECK();
-    }
+    int rc = direct ? ensure_batch(d, B) : tiles_from_device(d, d_cha, d_msg0, B);
+    if (rc) return rc;
+    const int G = d->bpad(B) / d->tile();
     if (direct) { d->fm_cha = d_cha; d->fm_msg0 = d_msg0; d->fm_bits = d_out_bits; }
     rc = decode_tiles(d, B);
     d->fm_cha = d->fm_msg0 = nullptr; d->fm_bits = nullptr;

@@ -91,11 +91,11 @@ __device__ __forceinline__ uint32_t sent_bits_of_lane(const uint8_t *__restrict_
 
 // Writes cha_t / msg0_t rows (row layout) for B frames starting at global frame index frame0 and
 // adds the slicer errors of each frame to stats[f][3].  One thread = 4*PACK frames x a run of
-// code-bit pairs.  codewords (frame-major [B][N], may be null = all-zero codeword): the sent bits;
-// SENT_ROWS: codewords points to sent-bit rows instead (never null).
+// code-bit pairs.  SENT_ROWS: the sent bits are the sent-bit rows `sent` (never null); otherwise the
+// all-zero codeword was sent and `sent` is not read.
 template <int PACK, bool SENT_ROWS = false>
 __global__ __launch_bounds__(256) void sample_labels_kernel(const ChannelCells *__restrict__ Cp, uint32_t seed_lo, uint32_t seed_hi, uint32_t stream, uint64_t frame0,
-                                                            int B, int N, const uint8_t *__restrict__ codewords, uint8_t *__restrict__ cha_t,
+                                                            int B, int N, const uint8_t *__restrict__ sent, uint8_t *__restrict__ cha_t,
                                                             uint8_t *__restrict__ msg_t, int32_t *__restrict__ stats, int pairs_per_thread)
 {
     constexpr int F = 4 * PACK;                                     // frames per lane
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void sample_labels_kernel(const ChannelCells *
         if constexpr (SENT_ROWS) {
 #pragma unroll
             for (int hh = 0; hh < 2; hh++)
-                if (2 * p + hh < N) sb[hh] = sent_bits_of_lane<PACK>(codewords, (size_t)g * N + 2 * p + hh, lane);
+                if (2 * p + hh < N) sb[hh] = sent_bits_of_lane<PACK>(sent, (size_t)g * N + 2 * p + hh, lane);
         }
 #pragma unroll
         for (int j = 0; j < F; j++) {
@@ -144,9 +144,7 @@ __global__ __launch_bounds__(256) void sample_labels_kernel(const ChannelCells *
                 const int v = 2 * p + hh;
                 if (v >= N) continue;
                 const int cell = cell_from_bucket(thr_lds, first_lds, n_thr, u[hh]);
-                int bit;
-                if constexpr (SENT_ROWS) bit = (int)((sb[hh] >> j) & 1u);
-                else bit = codewords ? codewords[(size_t)fl * N + v] : 0;
+                const int bit = (int)((sb[hh] >> j) & 1u);          // (no sent rows: sb stays zero)
                 const uint32_t at = attr_lds[cell], sel = bit ? at >> 16 : at;
                 const uint32_t a = sel & 0x7Fu, m = (sel >> 8) & 0xFFu;
                 // slicer decision: neg for bit 0, its mirror for bit 1 -- wrong exactly when the cell lies on the negative side
@@ -172,9 +170,9 @@ __global__ __launch_bounds__(256) void sample_labels_kernel(const ChannelCells *
 
 // stats[f] = {iteration code, frame error, data bit errors, uncoded bit errors}: compares the decided
 // bits of the first K positions with the sent ones (BERC / BLERC of src/LDPC_BER_Sim.cpp:284-286);
-// SENT_ROWS: codewords points to sent-bit rows (see sample_labels_kernel)
+// SENT_ROWS: as in sample_labels_kernel
 template <int PACK, bool SENT_ROWS = false>
-__global__ __launch_bounds__(256) void count_errors_kernel(const uint8_t *__restrict__ hard, const uint8_t *__restrict__ codewords, int B, int N, int K,
+__global__ __launch_bounds__(256) void count_errors_kernel(const uint8_t *__restrict__ hard, const uint8_t *__restrict__ sent, int B, int N, int K,
                                                            const int32_t *__restrict__ iters, int32_t *__restrict__ stats, int rows_per_wave)
 {
     constexpr int F = 4 * PACK;
@@ -188,15 +186,11 @@ __global__ __launch_bounds__(256) void count_errors_kernel(const uint8_t *__rest
     for (int v = v0; v < v1; v++) {
         const uint32_t x = *reinterpret_cast<const uint32_t *>(hard + ((size_t)g * N + v) * kRowBytes + lane * 4);
         uint32_t sb = 0;
-        if constexpr (SENT_ROWS) sb = sent_bits_of_lane<PACK>(codewords, (size_t)g * N + v, lane);
+        if constexpr (SENT_ROWS) sb = sent_bits_of_lane<PACK>(sent, (size_t)g * N + v, lane);
 #pragma unroll
         for (int j = 0; j < F; j++) {
-            const int fl = (g * kWave + lane) * F + j;
-            int sent;
-            if constexpr (SENT_ROWS) sent = (int)((sb >> j) & 1u);          // (pad frames carry zeros)
-            else sent = (codewords && fl < B) ? codewords[(size_t)fl * N + v] : 0;
             const uint32_t hw = unpack_half<PACK>(x, j / 4);
-            err[j] += (int)((hw >> (8 * (j & 3))) & 1u) != sent;
+            err[j] += (int)(((hw >> (8 * (j & 3))) ^ (sb >> j)) & 1u);      // (pad frames and no sent rows: zeros)
         }
     }
 #pragma unroll

@@ -87,7 +87,7 @@ def test_sim_batch_on_device_codewords_equals_host_codewords(cfg, resident, monk
     B, seed, stream = 1337, 2 ** 33 + 9, 2                           # not a multiple of the frame group
     got = pcd.sim_batch(snr, seed, stream, 0, B, zero_codeword=False)
     # the same frames through lutldpc_decoder_sim_batch, fed the codewords of the HOST encoder (sample_labels keeps it)
-    _, _, cw = pcd.sample_labels(snr, seed, stream, 0, B, zero_codeword=False)
+    cha_host, msg_host, cw = pcd.sample_labels(snr, seed, stream, 0, B, zero_codeword=False)
     assert cw.any()
     cc = pcd.channel_cells(snr)
     keep = [np.ascontiguousarray(cc[k]) for k in ("thr", "cha", "msg", "neg", "cha_m", "msg_m")]
@@ -97,13 +97,65 @@ def test_sim_batch_on_device_codewords_equals_host_codewords(cfg, resident, monk
     assert dec.describe()["resident"] == int(resident)
     lib.lutldpc_decoder_sim_batch.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(C.c_uint8), C.c_int,
                                               C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
-    check(lib.lutldpc_decoder_sim_batch(dec._h, C.byref(cells), seed, stream, 0, B, _p(np.ascontiguousarray(cw), C.c_uint8), pcd.ninfo,
-                                        _p(want, C.c_int32), None, None))
+    cw = np.ascontiguousarray(cw)
+    N = pcd.nvar
+    cha_h, bits_h, cha_d, bits_d = (np.full((B, N), 0xEE, np.uint8) for _ in range(4))
+    check(lib.lutldpc_decoder_sim_batch(dec._h, C.byref(cells), seed, stream, 0, B, _p(cw, C.c_uint8), pcd.ninfo,
+                                        _p(want, C.c_int32), cha_h.ctypes.data, bits_h.ctypes.data))
     assert (got == want).all(), np.argwhere(got != want)[:5]
     assert (want[:, 3] > 0).all()
+    # the labels and decided bits of both: the host codewords reach the sampler and the counters as the same sent-bit rows
+    rnd = np.empty((B, 4), np.int32)
+    check(lib.lutldpc_decoder_sim_batch_random(dec._h, C.byref(cells), seed, stream, 0, B, pcd.ninfo, _p(rnd, C.c_int32), _p(cha_d, C.c_uint8),
+                                               _p(bits_d, C.c_uint8)))
+    assert (rnd == want).all()
+    assert (cha_h == cha_d).all() and (bits_h == bits_d).all()
+    # ... and the test entry of the sampler, fed the same host codewords: that cha again, and the msg0 of the call above
+    lib.lutldpc_decoder_sample_labels.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(C.c_uint8),
+                                                  C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
+    cha_s, msg_s = np.full((B, N), 0xEE, np.uint8), np.full((B, N), 0xEE, np.uint8)
+    check(lib.lutldpc_decoder_sample_labels(dec._h, C.byref(cells), seed, stream, 0, B, _p(cw, C.c_uint8), _p(cha_s, C.c_uint8), _p(msg_s, C.c_uint8)))
+    assert (cha_s == cha_h).all() and (cha_s == cha_host).all() and (msg_s == msg_host).all()
     # pad frames carry zero codewords and no counts: the first frames of a larger batch (no padding there) are the same frames
     big = pcd.sim_batch(snr, seed, stream, 0, 2048, zero_codeword=False)
     assert (big[:B] == got).all()
+    pcd.close()
+
+
+@pytest.mark.parametrize("pack,B", [("", 515), ("1", 259)])
+def test_host_codewords_equal_device_codewords_in_histogram_and_events(pack, B, monkeypatch):
+    """sim_batch_histogram (level 3, all frames) and sim_batch_events (select = codeword, every frame kept) on C1, once on the
+    encoder's codewords and once on the bytes encode_random returns for them, passed back as host codewords: the same sent-bit
+    rows either way, so identical histograms, frame_stats, records, lists and profiles.  Two frame groups, three frames in the
+    second: nibble rows at B = 515, byte rows (LUTLDPC_PACK = 1) at B = 259."""
+    from lut_ldpc_amd.err_events import _Request
+    if pack:
+        monkeypatch.setenv("LUTLDPC_PACK", pack)                    # read when the device handle is created
+    pcd, snr = _product_c1()
+    dec = pcd.decoder()
+    assert dec.describe()["pack"] == (1 if pack else 2) and -(-B // dec.describe()["tile_frames"]) == 2
+    seed, stream, f0 = 2 ** 33 + 11, 4, 2 ** 32 + 3
+    cw = np.ascontiguousarray(pcd.encode_random(seed, stream, f0, B))
+    assert cw.any() and cw.max() <= 1
+    cc = pcd.channel_cells(snr)
+    keep = [np.ascontiguousarray(cc[k]) for k in ("thr", "cha", "msg", "neg", "cha_m", "msg_m")]
+    cells = Cells(len(cc["cha"]), _p(keep[0], C.c_uint64), *[_p(a, C.c_uint8) for a in keep[1:]])
+    nd, groups, labels, _ = dec.histogram_shape(3)
+    res = []
+    for codewords, on_device in ((None, 1), (_p(cw, C.c_uint8), 0)):
+        hist, got = np.zeros((nd, groups, 2, labels), np.int64), C.c_int32()
+        check(lib.lutldpc_decoder_sim_batch_histogram(dec._h, C.byref(cells), seed, stream, f0, B, codewords, on_device, 3, 0, labels,
+                                                      _p(hist, C.c_int64), hist.size, C.byref(got)))
+        assert got.value == nd and hist[:, :, 1].any()
+        rq, stats = _Request(pcd.nvar, pcd.nchk, "codeword", B, 64, 64, True), np.full((B, 4), -7, np.int32)
+        check(lib.lutldpc_decoder_sim_batch_events(dec._h, C.byref(cells), seed, stream, f0, B, codewords, on_device, pcd.ninfo, _p(stats, C.c_int32),
+                                                   C.byref(rq.c)))
+        res.append((hist, stats, rq.result()))
+    (h_d, s_d, e_d), (h_h, s_h, e_h) = res
+    assert (h_d == h_h).all() and (s_d == s_h).all()
+    assert e_d.n_selected == e_h.n_selected > 0 and len(e_d.events) == len(e_h.events) > 0
+    assert (e_d.events == e_h.events).all() and (e_d.positions == e_h.positions).all() and (e_d.checks == e_h.checks).all()
+    assert (e_d.node_errors == e_h.node_errors).all() and (e_d.check_fails == e_h.check_fails).all()
     pcd.close()
 
 
