@@ -135,6 +135,11 @@ int lutldpc_decoder_decode_llr_batch(lutldpc_decoder *d, const double *llr, int 
  * for a sent 1.  Frame f of the SNR point uses the Philox4x32-10 stream
  * (key = seed, counter = (f_lo, f_hi, bit-pair index, stream)), so any split of the frame range
  * over calls / GPUs generates the same frames.
+ *   stream      0 .. LUTLDPC_STREAM_MAX = 2^31 - 1.  Bit 31 of counter word 3 separates the information-bit stream of the random
+ *               codewords (stream | 0x80000000, below) from the channel stream: a stream with that bit set would draw its noise
+ *               from the blocks that make another stream's data.  Every entry that takes a stream (sim_batch, sim_batch_random,
+ *               sample_labels, encode_random, sim_batch_histogram, sim_batch_events and the lutldpc_codec_* wrappers) answers a
+ *               larger one with LUTLDPC_ERR_ARG before anything is computed or written; lutldpc_check_stream is that check.
  *   codewords   host [B*nvar] sent bits, bytes 0 or 1 (as encode_random returns them; bit 0 of a byte is what counts: the
  *               device keeps the sent bits in one form, a bitmap per node and frame group), or NULL for the all-zero codeword
  *   K_info      number of leading bits counted as data bits (nvar - rank(H))
@@ -152,6 +157,9 @@ typedef struct {
     const uint8_t *cha_label_mirror;
     const uint8_t *msg_label_mirror;
 } lutldpc_channel_cells;
+
+#define LUTLDPC_STREAM_MAX 0x7FFFFFFFu
+int lutldpc_check_stream(uint32_t stream);   /* LUTLDPC_OK, or LUTLDPC_ERR_ARG and the reason as the last error */
 
 int lutldpc_decoder_sim_batch(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream,
                               uint64_t frame0, int B, const uint8_t *codewords, int K_info, int32_t *frame_stats,

@@ -70,6 +70,7 @@ _SIGNATURES = {
     "lutldpc_decoder_decode_batch_trace": (C.c_int, [_vp, _u8p, _u8p, C.c_int, C.c_int, _u8p, _ip, _u8p, C.c_int64, _ip]),
     "lutldpc_selftest_jit_source": (C.c_int64, [_vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int64, C.c_int]),
     "lutldpc_selftest_resident_source": (C.c_int64, [_vp, C.c_int, C.c_char_p, C.c_int64, C.c_int, C.POINTER(C.c_int32)]),
+    "lutldpc_check_stream": (C.c_int, [C.c_uint32]),
     "lutldpc_decoder_set_generator": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "lutldpc_decoder_encode_random": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p]),
     "lutldpc_decoder_sim_batch_random": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, _ip, _u8p, _u8p]),

@@ -175,11 +175,23 @@ int device_entry(lutldpc_decoder *d) {
     HIP_TRY(hipSetDevice(d->device));
     return LUTLDPC_OK;
 }
-int batch_entry(lutldpc_decoder *d, int B) {
+int batch_entry(lutldpc_decoder *d, int B, uint32_t stream) {
     if (!d) return fail(LUTLDPC_ERR_ARG, "NULL decoder");
     if (B <= 0) return fail(LUTLDPC_ERR_ARG, "B must be positive");
+    if (int rc = lutldpc_check_stream(stream)) return rc;
     return device_entry(d);
 }
+#pragma GCC visibility pop
+// The Philox counter word 3 is `stream` for the channel uniforms and `stream | 0x80000000` for the information bits
+// (kernels_frontend.hpp, kernels_encode.hpp, host/ber_sim_driver.cpp): a stream with bit 31 set would draw its channel noise from
+// the very blocks that make the data of stream & 0x7FFFFFFF, and send that stream's data.  (Exported for host_capi.cpp, whose
+// wrappers make codewords on the host before they reach an entry here.)
+extern "C" int lutldpc_check_stream(uint32_t stream) {
+    if (stream > LUTLDPC_STREAM_MAX)
+        return fail(LUTLDPC_ERR_ARG, "stream must be below 2^31: bit 31 separates the information-bit stream from the channel stream");
+    return LUTLDPC_OK;
+}
+#pragma GCC visibility push(hidden)
 
 int tiles_from_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d_msg0, int B) {
     int rc = ensure_batch(d, B);

@@ -91,7 +91,7 @@ int sent_rows_of(lutldpc_decoder *d, const uint8_t *codewords, bool device_codew
 int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
                    const uint8_t *codewords, bool device_codewords, int K_info, int32_t *frame_stats, uint8_t *cha_out, uint8_t *bits_out, lutldpc_event_request *req) {
     if (!d || !frame_stats) return fail(LUTLDPC_ERR_ARG, "NULL argument");
-    int rc = batch_entry(d, B);
+    int rc = batch_entry(d, B, stream);
     if (rc) return rc;
     if (K_info < 0 || K_info > d->nvar) return fail(LUTLDPC_ERR_ARG, "bad K_info");
     if (device_codewords && !d->gen_set) return fail(LUTLDPC_ERR_STATE, "sim_batch_random: no generator set (lutldpc_decoder_set_generator)");
@@ -157,7 +157,7 @@ int lutldpc_decoder_set_generator(lutldpc_decoder *d, int K, int R, const uint64
 }
 
 int lutldpc_decoder_encode_random(lutldpc_decoder *d, uint64_t seed, uint32_t stream, uint64_t frame0, int B, uint8_t *codewords) {
-    int rc = batch_entry(d, B);
+    int rc = batch_entry(d, B, stream);
     if (rc || (rc = encode_tiles(d, seed, stream, frame0, B))) return rc;
     if (codewords) {
         const size_t n = (size_t)B * d->nvar;
@@ -171,7 +171,7 @@ int lutldpc_decoder_encode_random(lutldpc_decoder *d, uint64_t seed, uint32_t st
 int lutldpc_decoder_sample_labels(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
                                   const uint8_t *codewords, uint8_t *cha, uint8_t *msg0) {
     if (!d || !cha || !msg0) return fail(LUTLDPC_ERR_ARG, "NULL argument");
-    int rc = batch_entry(d, B);
+    int rc = batch_entry(d, B, stream);
     if (rc) return rc;
     ChannelCells C;
     if ((rc = fill_cells(cells, d, C))) return rc;

@@ -376,8 +376,9 @@ int check_batch_buffers(const lutldpc_decoder *d, int Bpad);
 // The entry layer: what every batch entry of the C-ABI does around decode_tiles.
 // The guard, in the order of the header's error contract: NULL handle, B <= 0 (LUTLDPC_ERR_ARG), host-only handle
 // (LUTLDPC_ERR_STATE), then the handle's device made current.  device_entry: the same without a batch (set_generator).
+// stream: the Philox stream of the entries that sample or encode (lutldpc_check_stream: >= 2^31 is LUTLDPC_ERR_ARG too).
 int device_entry(lutldpc_decoder *d);
-int batch_entry(lutldpc_decoder *d, int B);
+int batch_entry(lutldpc_decoder *d, int B, uint32_t stream = 0);
 // labels in: frame-major labels of B frames -> d_cha_t / d_msg0_t.  labels_from_host uploads them to d_in_cha / d_in_msg and stops
 // there (decode_device decides whether rows are needed), tiles_from_host goes on to the rows.
 int tiles_from_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d_msg0, int B);

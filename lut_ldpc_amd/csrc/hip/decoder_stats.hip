@@ -67,7 +67,8 @@ int hist_dump(lutldpc_decoder *d) {
 }
 
 // what both entries check before anything touches the device; *n_dumps_out = dumps of `level`
-static int hist_check_args(lutldpc_decoder *d, int B, int level, int mode, int n_labels, const int64_t *hist, int64_t hist_cap, int *n_dumps_out) {
+static int hist_check_args(lutldpc_decoder *d, int B, int level, int mode, int n_labels, const int64_t *hist, int64_t hist_cap, int *n_dumps_out,
+                           uint32_t stream = 0) {
     if (!d || !hist) return fail(LUTLDPC_ERR_ARG, "NULL argument");
     if (level < 2 || level > 3) return fail(LUTLDPC_ERR_ARG, "histogram level must be 2 or 3");
     if (mode < 0 || mode > 1) return fail(LUTLDPC_ERR_ARG, "histogram mode must be 0 (all) or 1 (active)");
@@ -76,7 +77,7 @@ static int hist_check_args(lutldpc_decoder *d, int B, int level, int mode, int n
     const int64_t need = (int64_t)nd * d->hist_groups * 2 * n_labels;
     if (hist_cap < need) return fail(LUTLDPC_ERR_ARG, "hist too small: " + std::to_string(need) + " int64 needed");
     *n_dumps_out = nd;
-    return batch_entry(d, B);
+    return batch_entry(d, B, stream);
 }
 
 // Does a normal decode of G frame groups move channel rows?  Only the compaction of the skewed pipeline does (launch_compaction
@@ -187,7 +188,7 @@ int lutldpc_decoder_sim_batch_histogram(lutldpc_decoder *d, const lutldpc_channe
                                         int B, const uint8_t *codewords, int device_codewords, int level, int mode, int n_labels,
                                         int64_t *hist, int64_t hist_cap, int32_t *n_dumps) {
     int nd = 0, rc;
-    if ((rc = hist_check_args(d, B, level, mode, n_labels, hist, hist_cap, &nd))) return rc;
+    if ((rc = hist_check_args(d, B, level, mode, n_labels, hist, hist_cap, &nd, stream))) return rc;
     if (device_codewords && !d->gen_set) return fail(LUTLDPC_ERR_STATE, "sim_batch_histogram: no generator set (lutldpc_decoder_set_generator)");
     ChannelCells C;
     if ((rc = fill_cells(cells, d, C))) return rc;

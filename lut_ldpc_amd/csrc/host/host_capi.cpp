@@ -177,6 +177,7 @@ int lutldpc_codec_encode(lutldpc_codec *c, const uint8_t *info, uint8_t *codewor
 int lutldpc_codec_sim_batch(lutldpc_codec *c, double snr_db, uint64_t seed, uint32_t stream, uint64_t frame0, int B, int zero_codeword, int32_t *stats) {
     return guarded([&] {
         if (!c || !stats || B <= 0) throw std::invalid_argument("NULL / bad argument");
+        if (int rc = lutldpc_check_stream(stream)) return rc;
         const ChannelCellTable cells = channel_cells_at(*c->C, snr_db);
         const lutldpc_channel_cells view = cells.view();
         // random codewords: made on the device (generators beyond the device encoder's size: on the host, as before)
@@ -192,6 +193,7 @@ int lutldpc_codec_message_histogram(lutldpc_codec *c, double snr_db, uint64_t se
                                     int level, int mode, int n_labels, int64_t *hist, int64_t hist_cap, int32_t *n_dumps) {
     return guarded([&] {
         if (!c || !hist || B <= 0) throw std::invalid_argument("NULL / bad argument");
+        if (int rc = lutldpc_check_stream(stream)) return rc;
         const ChannelCellTable cells = channel_cells_at(*c->C, snr_db);
         const lutldpc_channel_cells view = cells.view();
         lutldpc_decoder *d = c->C->device_handle();
@@ -208,6 +210,7 @@ int lutldpc_codec_error_events(lutldpc_codec *c, double snr_db, uint64_t seed, u
                                lutldpc_event_request *req) {
     return guarded([&] {
         if (!c || !req || B <= 0) throw std::invalid_argument("NULL / bad argument");
+        if (int rc = lutldpc_check_stream(stream)) return rc;
         const ChannelCellTable cells = channel_cells_at(*c->C, snr_db);
         const lutldpc_channel_cells view = cells.view();
         // the sent codewords as lutldpc_codec_sim_batch chooses them
@@ -223,6 +226,7 @@ int lutldpc_codec_error_events(lutldpc_codec *c, double snr_db, uint64_t seed, u
 int lutldpc_codec_encode_random(lutldpc_codec *c, uint64_t seed, uint32_t stream, uint64_t frame0, int B, uint8_t *codewords) {
     return guarded([&] {
         if (!c || !codewords || B <= 0) throw std::invalid_argument("NULL / bad argument");
+        if (int rc = lutldpc_check_stream(stream)) return rc;
         if (!c->C->has_device_generator()) throw std::logic_error("encode_random: the codec has no generator on the device (with_generator, at most 8192 information bits)");
         return lutldpc_decoder_encode_random(c->C->device_handle(), seed, stream, frame0, B, codewords);
     });
@@ -232,6 +236,7 @@ int lutldpc_codec_sample_labels(lutldpc_codec *c, double snr_db, uint64_t seed, 
                                 uint8_t *cha, uint8_t *msg0, uint8_t *codewords) {
     return guarded([&] {
         if (!c || !cha || !msg0 || B <= 0) throw std::invalid_argument("NULL / bad argument");
+        if (int rc = lutldpc_check_stream(stream)) return rc;
         const ChannelCellTable cells = channel_cells_at(*c->C, snr_db);
         const lutldpc_channel_cells view = cells.view();
         std::vector<unsigned char> cw;
