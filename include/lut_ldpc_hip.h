@@ -93,6 +93,36 @@ int lutldpc_decoder_set_exit_conditions(lutldpc_decoder *d, int max_iters, int p
 int lutldpc_decoder_decode_batch(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0, int B,
                                  uint8_t *out_bits, int32_t *out_iters);
 
+/*
+ * lutldpc_decoder_decode_batch for callers whose labels cross a host link: the same decode, bit for bit, without the bytes that
+ * carry no information.  Labels may come two per byte, the initial messages may be derived from the channel labels on the device
+ * (the toolkit's QCHA mode, cha2msg_map of src/LDPC_Code_LUT.cpp:204-226), and only a window of the decided bits is returned, one
+ * bit each -- the data bits are the first nvar - rank(H).
+ *   cha        host [B][stride] labels in `in_format`: stride = nvar (LUTLDPC_IN_BYTES) or ceil(nvar/2) (LUTLDPC_IN_NIBBLES)
+ *   msg0       the initial message labels in the same format, or NULL when io->cha2msg_map is given
+ *   out_words  host [B][ceil(out_count/32)] uint32: bit j of word w = decided bit out_first + 32w + j, bits beyond out_count are 0;
+ *              NULL when only the iteration codes are wanted
+ *   out_iters  host [B] as lutldpc_decoder_decode_batch; may be NULL
+ * A channel label >= Nq_Cha is clamped to the largest label (a 6-label alphabet in a nibble can hold one), the map is applied after
+ * the clamp; a given msg0 is clamped to Nq_Msg[0] - 1.
+ * Errors: NULL handle or B <= 0 -> LUTLDPC_ERR_ARG; then the entry's own arguments, LUTLDPC_ERR_ARG too: NULL io or cha, an
+ * in_format other than the two below, LUTLDPC_IN_NIBBLES with Nq_Cha > 16 (or with Nq_Msg[0] > 16 and msg0 given), both or neither
+ * of msg0 and cha2msg_map, a map entry outside [0, Nq_Msg[0]), out_first < 0, out_count < 1, out_first + out_count > nvar; only
+ * then a handle without a device -> LUTLDPC_ERR_STATE.
+ */
+#define LUTLDPC_IN_BYTES   0   /* one label per byte, [B][nvar], as decode_batch                                   */
+#define LUTLDPC_IN_NIBBLES 1   /* two labels per byte, frame stride ceil(nvar/2) bytes, node v in byte v/2,
+                                  even v in bits 0-3, odd v in bits 4-7; the spare nibble of an odd nvar is ignored */
+typedef struct {
+    int32_t in_format;            /* applies to cha and, when given, to msg0                                  */
+    const int32_t *cha2msg_map;   /* NULL: msg0 is given.  Else Nq_Cha entries < Nq_Msg[0]: msg0[v] = map[cha[v]]
+                                     computed on the device, msg0 must be NULL                                 */
+    int32_t out_first, out_count; /* decided bits out_first .. out_first+out_count-1 of every frame            */
+} lutldpc_packed_io;
+
+int lutldpc_decoder_decode_batch_packed(lutldpc_decoder *d, const lutldpc_packed_io *io, const uint8_t *cha, const uint8_t *msg0,
+                                        int B, uint32_t *out_words, int32_t *out_iters);
+
 /* Same with device-resident buffers (same frame-major layout); asynchronous on the decoder's
  * stream unless `sync` is non-zero.  The call runs on the decoder's OWN non-blocking stream (lutldpc_decoder_stream): the input
  * buffers must be complete, and the four buffers must not be memory that another stream is still working on (a stream-ordered

@@ -39,6 +39,7 @@ int lutldpc_codec_design_luts(lutldpc_codec *c, const char *tree_method, int min
 int lutldpc_codec_design_from_cache(lutldpc_codec *c);
 int lutldpc_codec_set_exit_conditions(lutldpc_codec *c, int max_iters, int psc, int pisc);
 int lutldpc_codec_set_initial_message_mode(lutldpc_codec *c, int mode);   /* 0 CONT, 1 QCHA */
+int lutldpc_codec_initial_message_mode(lutldpc_codec *c);                 /* the mode in force; < 0: NULL codec */
 int lutldpc_codec_set_output_verbosity(lutldpc_codec *c, int level);
 
 /* getters */

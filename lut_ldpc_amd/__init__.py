@@ -8,5 +8,6 @@ from ._capi import LutLdpcError, device_count, last_error, LIB_PATH  # noqa: F40
 from .decoder import Decoder  # noqa: F401
 from .codec import Codec, de_threshold  # noqa: F401
 from .bp import BPDecoder  # noqa: F401
+from . import packing  # noqa: F401
 
-__all__ = ["Decoder", "Codec", "BPDecoder", "de_threshold", "LutLdpcError", "device_count", "last_error", "LIB_PATH"]
+__all__ = ["Decoder", "Codec", "BPDecoder", "de_threshold", "LutLdpcError", "device_count", "last_error", "LIB_PATH", "packing"]

@@ -48,6 +48,15 @@ class EventRequest(C.Structure):
 
 
 _evp = C.POINTER(EventRequest)
+IN_BYTES, IN_NIBBLES = 0, 1
+
+
+class PackedIO(C.Structure):
+    """lutldpc_packed_io (include/lut_ldpc_hip.h): input format, the optional channel-to-message map, the window of decided bits."""
+    _fields_ = [("in_format", C.c_int32), ("cha2msg_map", _ip), ("out_first", C.c_int32), ("out_count", C.c_int32)]
+
+
+_u32p = C.POINTER(C.c_uint32)
 _SIGNATURES = {
     "lutldpc_last_error": (_cp, []),
     "lutldpc_version": (_cp, []),
@@ -57,6 +66,7 @@ _SIGNATURES = {
     "lutldpc_decoder_destroy": (C.c_int, [_vp]),
     "lutldpc_decoder_set_exit_conditions": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
     "lutldpc_decoder_decode_batch": (C.c_int, [_vp, _u8p, _u8p, C.c_int, _u8p, _ip]),
+    "lutldpc_decoder_decode_batch_packed": (C.c_int, [_vp, C.POINTER(PackedIO), _u8p, _u8p, C.c_int, _u32p, _ip]),
     "lutldpc_decoder_decode_batch_device": (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, C.c_int]),
     "lutldpc_decoder_decode_llr_batch": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _ip, _u8p, _ip]),
     "lutldpc_decoder_stream": (_vp, [_vp]),
@@ -110,6 +120,7 @@ _HOST_SIGNATURES = {
     "lutldpc_codec_design_from_cache": (C.c_int, [_vp]),
     "lutldpc_codec_set_exit_conditions": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
     "lutldpc_codec_set_initial_message_mode": (C.c_int, [_vp, C.c_int]),
+    "lutldpc_codec_initial_message_mode": (C.c_int, [_vp]),
     "lutldpc_codec_set_output_verbosity": (C.c_int, [_vp, C.c_int]),
     "lutldpc_codec_dims": (C.c_int, [_vp, _ip, _ip, _ip, _ip]),
     "lutldpc_codec_graph": (C.c_int, [_vp, _ip, _ip, _ip]),

@@ -146,6 +146,15 @@ class Codec:
         check(lib.lutldpc_codec_lut_decode_batch(self._h, _p(cha, C.c_uint8), _p(msg0, C.c_uint8), B, _p(bits, C.c_uint8), _p(iters, C.c_int32)))
         return bits, iters
 
+    def decode_packed(self, cha, nibbles=False, info_only=True):
+        """Decoder.decode_packed with what the codec knows: the initial messages from its cha2msg_map on the device, and (info_only)
+        only the nvar - rank(H) data bits returned.  (words, iters).  The map stands for the initial messages only in the mode
+        from_quantized_channel_llrs (QCHA, set_initial_message_mode(1)); in any other mode this raises."""
+        if lib.lutldpc_codec_initial_message_mode(self._h) != 1:
+            raise ValueError("decode_packed derives the initial messages from the channel labels: the codec's initial-message mode must be "
+                             "QCHA (set_initial_message_mode(1)); with continuous-input messages use Decoder.decode_packed(cha, msg0=...)")
+        return self.decoder().decode_packed(cha, cha2msg_map=self.cha2msg_map, nibbles=nibbles, first=0, count=self.ninfo if info_only else self.nvar)
+
     # ---- Monte-Carlo front end ------------------------------------------------------------------------
     def sim_batch(self, snr_db, seed, stream, frame0, B, zero_codeword=True) -> np.ndarray:
         """{iters, frame error, data bit errors, uncoded errors} of frames frame0..frame0+B-1 (device sampler + decode)."""

@@ -14,6 +14,7 @@
 //   decoder_frontend.hip   channel sampler, encoder, error counters and their C-ABI entries    (kernels_frontend.hpp, kernels_encode.hpp)
 //   decoder_stats.hip      message-label histograms per dump: edge groups, the counted decode, C-ABI   (kernels_stats.hpp)
 //   decoder_events.hip     failed frames captured on the device: weights, selection, sorted error / syndrome lists, C-ABI   (kernels_events.hpp)
+//   decoder_packed.hip     packed label input and bit-packed output of the host-side batch decode, C-ABI                    (kernels_packed.hpp)
 #pragma once
 #include "../../../include/lut_ldpc_hip.h"
 #include "kernels_common.hpp"
@@ -215,6 +216,7 @@ struct lutldpc_decoder {
     DevBuf<int32_t> d_iters;
     DevBuf<uint8_t> d_in_cha, d_in_msg, d_out_bits;   // frame-major staging for the host entry points
     DevBuf<int32_t> d_out_iters;
+    DevBuf<uint32_t> d_out_words;                     // decode_batch_packed: [B][ceil(out_count/32)] decided bits, one each
     DevBuf<double> d_llr, d_qb_cha, d_qb_msg;
     DevBuf<int32_t> d_map;
     DevBuf<uint8_t> d_codewords;                      // upload staging of sent_rows_from_host; no kernel but its conversion reads it
@@ -465,5 +467,8 @@ int event_request_check(const lutldpc_event_request *req);                      
 // after decode_tiles of B frames: weights, selection and lists of the batch in d_hard / d_iters into req.  sent_rows: sent-bit
 // rows of the batch or null (all-zero codeword); stats: the front end's per-frame counters (device) or null.  Synchronises.
 int capture_events(lutldpc_decoder *d, int B, int K_info, const uint8_t *sent_rows, const int32_t *stats, lutldpc_event_request *req);
+
+// ---- decoder_packed.hip (home of the kernels of kernels_packed.hpp)
+hipError_t preload_packed_kernels();
 
 #pragma GCC visibility pop

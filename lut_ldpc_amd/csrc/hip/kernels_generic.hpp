@@ -3,6 +3,7 @@
 // All kernels are templated on PACK (1 = byte rows, 2 = nibble rows; kernels_common.hpp).
 #pragma once
 #include "kernels_common.hpp"
+#include "kernels_layout.hpp"
 #include "lut_program.hpp"
 
 namespace lutldpc {
@@ -297,27 +298,7 @@ __global__ __launch_bounds__(256) void transpose_out_kernel(const uint8_t *__res
 //                 frames 4*PACK*L + k of one quad c) hit 32 different banks;
 //   registers   : 4x4 byte transposes with v_perm_b32 turn "4 nodes of 4 frames" into "4 frames of one node",
 //                 the dword a lane owns in a row (PACK = 2: two of them merged as low / high nibbles).
-// XCD-aware block order of the transposes.  A block moves 128 nodes x one frame group; its frame-major side is one 128-byte
-// segment per frame at a stride of N bytes, so unless N is a multiple of 128 every segment straddles two 128-byte lines and
-// shares each with the block of the neighbouring node range.  Blocks are dealt round-robin to the 8 XCDs (one L2 each): with the
-// plain (x, y) order the two halves of a line are fetched (written) by two different L2s -- measured 3.72 GB read for 2.12 GB of
-// input.  Remapped, the blocks of one XCD cover a CONTIGUOUS range of (group, node block): the neighbour that shares a line runs
-// on the same XCD a few blocks later and finds it in that L2.
-__device__ __forceinline__ void xcd_block(int &bx, int &by) {
-    const int gx = (int)gridDim.x, total = gx * (int)gridDim.y, lin = (int)blockIdx.y * gx + (int)blockIdx.x;
-    const int per = total / 8;
-    int nl = lin;
-    if (lin < per * 8) nl = (lin & 7) * per + (lin >> 3);         // (the last total % 8 blocks keep their place)
-    bx = nl % gx; by = nl / gx;
-}
-
-__device__ __forceinline__ void transpose4x4(uint32_t (&d)[4]) {
-    const uint32_t a = __builtin_amdgcn_perm(d[1], d[0], 0x05010400u), b = __builtin_amdgcn_perm(d[1], d[0], 0x07030602u);
-    const uint32_t c = __builtin_amdgcn_perm(d[3], d[2], 0x05010400u), e = __builtin_amdgcn_perm(d[3], d[2], 0x07030602u);
-    d[0] = __builtin_amdgcn_perm(c, a, 0x05040100u); d[1] = __builtin_amdgcn_perm(c, a, 0x07060302u);
-    d[2] = __builtin_amdgcn_perm(e, b, 0x05040100u); d[3] = __builtin_amdgcn_perm(e, b, 0x07060302u);
-}
-
+// (xcd_block, the XCD-aware block order, and transpose4x4: kernels_layout.hpp)
 template <int PACK>
 __global__ __launch_bounds__(256) void transpose_in_vec_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int B, int N, int limit)
 {

@@ -97,6 +97,10 @@ int lutldpc_codec_set_initial_message_mode(lutldpc_codec *c, int mode) {
         return LUTLDPC_OK;
     });
 }
+int lutldpc_codec_initial_message_mode(lutldpc_codec *c) {
+    if (!c) { lutldpc_set_last_error("NULL codec"); return LUTLDPC_ERR_ARG; }
+    return c->C->get_initial_message_mode() == LDPC_Code_LUT::QCHA ? 1 : 0;
+}
 int lutldpc_codec_set_output_verbosity(lutldpc_codec *c, int level) {
     return guarded([&] { if (!c) throw std::invalid_argument("NULL codec"); c->C->set_output_verbosity(level); return LUTLDPC_OK; });
 }

@@ -67,6 +67,29 @@ class Decoder:
                                                _p(iters, C.c_int32)))
         return out, iters
 
+    def decode_packed(self, cha, msg0=None, cha2msg_map=None, nibbles=False, first=0, count=None):
+        """lut_decode_batch with less on the host link (lutldpc_decoder_decode_batch_packed): cha / msg0 are [B, nvar] labels, or with
+        nibbles=True [B, ceil(nvar/2)] bytes as packing.pack_nibbles makes them; cha2msg_map (Nq_Cha entries) in place of msg0
+        derives the initial messages from the channel labels on the device.  Returns (words uint32 [B, ceil(count/32)], iters): the
+        decided bits first .. first+count-1 of every frame, one bit each (packing.unpack_bits); count=None: up to nvar."""
+        cha = np.ascontiguousarray(cha, np.uint8)
+        stride = (self.nvar + 1) // 2 if nibbles else self.nvar
+        if cha.ndim != 2 or cha.shape[1] != stride:
+            raise ValueError("cha must be [B, ceil(nvar/2)] packed bytes" if nibbles else "cha must be [B, nvar]")
+        B = cha.shape[0]
+        if msg0 is not None:
+            msg0 = np.ascontiguousarray(msg0, np.uint8)
+            if msg0.shape != cha.shape:
+                raise ValueError("msg0 must have the shape and format of cha")
+        mp = _i32(cha2msg_map) if cha2msg_map is not None else None
+        count = self.nvar - int(first) if count is None else int(count)
+        io = _capi.PackedIO(_capi.IN_NIBBLES if nibbles else _capi.IN_BYTES, _p(mp, C.c_int32) if mp is not None else None, int(first), count)
+        words = np.empty((B, max((count + 31) // 32, 0)), np.uint32)
+        iters = np.empty(B, np.int32)
+        check(lib.lutldpc_decoder_decode_batch_packed(self._h, C.byref(io), _p(cha, C.c_uint8), _p(msg0, C.c_uint8) if msg0 is not None else None, B,
+                                                      _p(words, C.c_uint32), _p(iters, C.c_int32)))
+        return words, iters
+
     def lut_decode_batch_trace(self, cha, msg0, level, n_edges):
         """Debug path: (bits, iters, trace uint8 [n_dumps, B, E]) -- the edge messages after the initialisation, (level 3) every
         check pass and every variable pass, in the print order of output_verbosity = level (src/LDPC_Code_LUT.cpp:292-337)."""
