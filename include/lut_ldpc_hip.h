@@ -154,6 +154,56 @@ int lutldpc_decoder_decode_llr_batch(lutldpc_decoder *d, const double *llr, int 
                                      uint8_t *out_bits, int32_t *out_iters);
 
 /*
+ * lutldpc_decoder_decode_llr_batch for receivers: the same quantisation and decode, bit for bit, for soft values as a demapper
+ * holds them -- float64, float32, float16 or int8 with a scale, in host memory or already on the device -- and a window of the
+ * decided bits out at one bit each.  The values are quantised straight into both label row sets (no frame-major labels in
+ * between), the decode is that of every other batch entry.
+ *   llr        [B][frame_stride] elements of io->dtype; host memory (io->on_device = 0) or device memory (1), aligned to its element
+ *              size.  Elements nvar .. frame_stride-1 of a frame are never read.
+ *   out_words  [B][ceil(out_count/32)] uint32 as lutldpc_decoder_decode_batch_packed, or NULL
+ *   out_iters  [B] as lutldpc_decoder_decode_batch, or NULL
+ *   out_cha, out_msg0   optional [B][nvar] label bytes: what the device derived from the values
+ * Every output lives where llr lives.  With out_words and out_iters both NULL the decode is skipped and the call only quantises;
+ * at least one output must be asked for.
+ * The value of an element is x as a real number (int8: (double)q * scale); cha = number of leading qb_Cha[k] with x > qb_Cha[k],
+ * msg0 = the same over qb_Msg (mode 0, CONT) or cha2msg_map[cha] (mode 1, QCHA): quant_nonlin of src/common.cpp:120-129 on the
+ * value, so NaN gets label 0, +inf the largest label and -0.0 is 0.  No value is rounded on the way: the boundaries are rounded
+ * DOWN to the input type on the host, which leaves every comparison as it was.
+ * on_device = 1: the contract of lutldpc_decoder_decode_batch_device -- the call runs on the decoder's own stream, its buffers must
+ * be complete and not in use by another stream, and it is asynchronous unless io->sync is set.  on_device = 0: synchronous.
+ * Errors: NULL handle or B <= 0 -> LUTLDPC_ERR_ARG; then the entry's own arguments, LUTLDPC_ERR_ARG too: NULL io or llr, an
+ * unknown dtype, llr not aligned to its element size, frame_stride neither 0 nor >= nvar, n_qb_Cha != Nq_Cha - 1 (mode 0:
+ * n_qb_Msg != Nq_Msg[0] - 1), a NaN or descending boundary, a mode other than 0 / 1, mode 0 without qb_Msg or with a map, mode 1
+ * without a map, a map entry outside [0, Nq_Msg[0]), a window outside [0, nvar) when out_words is given, LUTLDPC_LLR_I8 with a
+ * scale that is not finite and positive, no output asked for; only then a handle without a device -> LUTLDPC_ERR_STATE.
+ */
+#define LUTLDPC_LLR_F64 0
+#define LUTLDPC_LLR_F32 1
+#define LUTLDPC_LLR_F16 2      /* IEEE binary16 */
+#define LUTLDPC_LLR_I8  3      /* LLR = scale * q */
+typedef struct {
+    int32_t dtype;
+    int32_t on_device;           /* 0: llr and every output are host memory; 1: all of them are device memory */
+    int64_t frame_stride;        /* elements from one frame to the next; 0 = nvar, else >= nvar */
+    double  scale;               /* LUTLDPC_LLR_I8: finite, > 0; ignored otherwise */
+    const double *qb_Cha; int32_t n_qb_Cha;          /* host, Nq_Cha - 1 */
+    const double *qb_Msg; int32_t n_qb_Msg;          /* host, Nq_Msg[0] - 1; mode 0 only */
+    int32_t initial_message_mode; const int32_t *cha2msg_map;   /* host; mode 1 only, entries in [0, Nq_Msg[0]) */
+    int32_t out_first, out_count;                    /* window of decided bits, as lutldpc_packed_io */
+    int32_t sync;                                    /* on_device = 1: synchronise the decoder's stream before returning */
+} lutldpc_llr_io;
+int lutldpc_decoder_decode_llr_packed(lutldpc_decoder *d, const lutldpc_llr_io *io, const void *llr, int B,
+                                      uint32_t *out_words, int32_t *out_iters, uint8_t *out_cha, uint8_t *out_msg0);
+
+/* The host half of that entry, without a decoder or a device (self test): the thresholds in the input type (widened to double,
+ * ascending, at most 255; none for LUTLDPC_LLR_I8, whose byte is its own cell) and the two 256-entry tables from a value's cell
+ * = #{j : x > thr[j]} to its labels.  Reads dtype, scale, the boundaries, the mode and the map of io; the same argument errors,
+ * and LUTLDPC_ERR_ARG when thr_cap is short. */
+int lutldpc_llr_cell_table(const lutldpc_llr_io *io, int Nq_Cha, int Nq_Msg0,
+                           double *thr, int32_t thr_cap, int32_t *n_thr,   /* the T values, widened to double */
+                           uint8_t lut_cha[256], uint8_t lut_msg[256]);
+
+/*
  * Monte-Carlo front end + decode + error counting for B consecutive frames of one SNR point:
  * the body of the frame loop of LDPC_BER_Sim::sim_snr_point (src/LDPC_BER_Sim.cpp:260-286)
  * without the stop rule, which stays with the caller (it needs the frames in order).

@@ -56,8 +56,21 @@ class PackedIO(C.Structure):
     _fields_ = [("in_format", C.c_int32), ("cha2msg_map", _ip), ("out_first", C.c_int32), ("out_count", C.c_int32)]
 
 
+LLR_F64, LLR_F32, LLR_F16, LLR_I8 = 0, 1, 2, 3
+
+
+class LlrIO(C.Structure):
+    """lutldpc_llr_io (include/lut_ldpc_hip.h): element type and location of the soft values, the quantiser, the window of decided bits."""
+    _fields_ = [("dtype", C.c_int32), ("on_device", C.c_int32), ("frame_stride", C.c_int64), ("scale", C.c_double),
+                ("qb_Cha", _dp), ("n_qb_Cha", C.c_int32), ("qb_Msg", _dp), ("n_qb_Msg", C.c_int32),
+                ("initial_message_mode", C.c_int32), ("cha2msg_map", _ip), ("out_first", C.c_int32), ("out_count", C.c_int32),
+                ("sync", C.c_int32)]
+
+
 _u32p = C.POINTER(C.c_uint32)
 _SIGNATURES = {
+    "lutldpc_decoder_decode_llr_packed": (C.c_int, [_vp, C.POINTER(LlrIO), _vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "lutldpc_llr_cell_table": (C.c_int, [C.POINTER(LlrIO), C.c_int, C.c_int, _dp, C.c_int32, _ip, _u8p, _u8p]),
     "lutldpc_last_error": (_cp, []),
     "lutldpc_version": (_cp, []),
     "lutldpc_device_count": (C.c_int, []),

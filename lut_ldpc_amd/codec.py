@@ -155,6 +155,16 @@ class Codec:
                              "QCHA (set_initial_message_mode(1)); with continuous-input messages use Decoder.decode_packed(cha, msg0=...)")
         return self.decoder().decode_packed(cha, cha2msg_map=self.cha2msg_map, nibbles=nibbles, first=0, count=self.ninfo if info_only else self.nvar)
 
+    def decode_llr(self, llr, scale=None, info_only=True):
+        """Decoder.decode_llr with what the codec knows: its boundaries, its initial-message mode (CONT: qb_msg, QCHA: cha2msg_map) and
+        (info_only) only the nvar - rank(H) data bits returned.  llr: [B, nvar] float64 / float32 / float16 / int8 (with scale),
+        numpy or a torch tensor on the device.  (words, iters)."""
+        mode = lib.lutldpc_codec_initial_message_mode(self._h)
+        if mode not in (0, 1):
+            raise ValueError("decode_llr needs the initial-message mode CONT (0) or QCHA (1)")
+        return self.decoder().decode_llr(llr, self.qb_cha, qb_msg=self.qb_msg if mode == 0 else None, cha2msg_map=self.cha2msg_map if mode == 1 else None,
+                                         scale=scale, first=0, count=self.ninfo if info_only else self.nvar)
+
     # ---- Monte-Carlo front end ------------------------------------------------------------------------
     def sim_batch(self, snr_db, seed, stream, frame0, B, zero_codeword=True) -> np.ndarray:
         """{iters, frame error, data bit errors, uncoded errors} of frames frame0..frame0+B-1 (device sampler + decode)."""

@@ -374,7 +374,7 @@ int lutldpc_decoder_reset_profile(lutldpc_decoder *d) {
 int64_t lutldpc_decoder_device_bytes(lutldpc_decoder *d) {
     if (!d) return 0;
     return (int64_t)(d->d_msgs.bytes() + d->d_cha_t.bytes() + d->d_msg0_t.bytes() + d->d_hard.bytes() + d->d_state.bytes() + d->d_vfail.bytes() +
-                     d->d_iters.bytes() + d->d_in_cha.bytes() + d->d_in_msg.bytes() + d->d_out_bits.bytes() + d->d_out_iters.bytes() + d->d_llr.bytes() +
+                     d->d_iters.bytes() + d->d_in_cha.bytes() + d->d_in_msg.bytes() + d->d_out_bits.bytes() + d->d_out_iters.bytes() + d->d_llr.bytes() + d->d_llr_in.bytes() +
                      d->d_ops.bytes() + d->d_tables.bytes() + d->d_cn_idx.bytes() + d->d_cn_vn.bytes());
 }
 const char *lutldpc_decoder_describe(lutldpc_decoder *d) { return d ? d->describe.c_str() : ""; }

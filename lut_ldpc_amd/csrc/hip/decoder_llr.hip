@@ -1,0 +1,124 @@
+// decoder_llr.hip -- lutldpc_decoder_decode_llr_packed: the batch decode for receivers, whose soft values are float32, float16 or
+// 8-bit fixed point (float64 for the toolkit's own callers) and sit in host memory or already on the device.  Values -> cells ->
+// both row sets in one pass (llr_cells.hpp, kernels_llr.hpp) -> decode_tiles -> packed bits (packed_bits_out_kernel); every decode
+// path decode_tiles picks.  Home of the kernel of kernels_llr.hpp; lutldpc_llr_cell_table is the host half on its own.
+#include "decoder_state.hpp"
+#include "kernels_llr.hpp"
+#include "llr_cells.hpp"
+
+#pragma GCC visibility push(hidden)
+
+// (see preload_code_objects) this unit's code object
+hipError_t preload_llr_kernels() {
+    hipFuncAttributes a;
+    return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&llr_labels_in_kernel<2, float, 1>));
+}
+
+// frame-major values of B frames (device, `stride` elements per frame) -> d_cha_t / d_msg0_t
+template <class T>
+static int launch_llr_labels_in(lutldpc_decoder *d, const void *src, size_t stride, const LlrTables *tab, int n_thr, int B, int G) {
+    const dim3 grid((unsigned)((d->nvar + 127) / 128), (unsigned)G);
+    const T *p = static_cast<const T *>(src);
+    const bool vec = stride % 4 == 0 && reinterpret_cast<uintptr_t>(src) % alignof(LlrQuad<T>) == 0;
+#define LLR_IN(VEC) PACK_DISPATCH(d, launch_k(llr_labels_in_kernel<PK, T, VEC>, grid, dim3(256), 0, d->stream, p, stride, d->d_cha_t.p, d->d_msg0_t.p, tab, n_thr, B, d->nvar))
+    if (vec) LLR_IN(1); else LLR_IN(0);
+#undef LLR_IN
+    LAUNCH_CHECK();
+    return LUTLDPC_OK;
+}
+
+// the tables of a call as the kernel of `dtype` reads them
+static LlrTables device_tables(const LlrCells &C, int dtype) {
+    LlrTables T;
+    memset(&T, 0, sizeof(T));                               // (the arena is keyed by content: no stray bytes)
+    memcpy(T.lut_cha, C.lut_cha, 256);
+    memcpy(T.lut_msg, C.lut_msg, 256);
+    for (int j = 0; j < C.n_thr; j++) {
+        if (dtype == LUTLDPC_LLR_F64) T.thr.f64[j] = C.thr[j];
+        else T.thr.f32[j] = (float)C.thr[j];                // exact: a value of float32 / float16
+    }
+    return T;
+}
+
+#pragma GCC visibility pop
+
+extern "C" int lutldpc_llr_cell_table(const lutldpc_llr_io *io, int Nq_Cha, int Nq_Msg0, double *thr, int32_t thr_cap, int32_t *n_thr,
+                                      uint8_t lut_cha[256], uint8_t lut_msg[256]) {
+    if (!io || !n_thr || !lut_cha || !lut_msg) return fail(LUTLDPC_ERR_ARG, "NULL argument");
+    LlrCells C;
+    const std::string err = llr_cell_table(*io, Nq_Cha, Nq_Msg0, C);
+    if (!err.empty()) return fail(LUTLDPC_ERR_ARG, err);
+    if (C.n_thr > thr_cap || (C.n_thr > 0 && !thr)) return fail(LUTLDPC_ERR_ARG, "thr holds fewer than " + std::to_string(C.n_thr) + " thresholds");
+    *n_thr = C.n_thr;
+    std::copy(C.thr, C.thr + C.n_thr, thr);
+    memcpy(lut_cha, C.lut_cha, 256);
+    memcpy(lut_msg, C.lut_msg, 256);
+    return LUTLDPC_OK;
+}
+
+extern "C" int lutldpc_decoder_decode_llr_packed(lutldpc_decoder *d, const lutldpc_llr_io *io, const void *llr, int B, uint32_t *out_words,
+                                                 int32_t *out_iters, uint8_t *out_cha, uint8_t *out_msg0) {
+    if (!d) return fail(LUTLDPC_ERR_ARG, "NULL decoder");
+    if (B <= 0) return fail(LUTLDPC_ERR_ARG, "B must be positive");
+    if (!io || !llr) return fail(LUTLDPC_ERR_ARG, "NULL argument: io and llr are required");
+    const size_t esize = llr_elem_size(io->dtype);
+    if (!esize) return fail(LUTLDPC_ERR_ARG, "dtype must be LUTLDPC_LLR_F64, _F32, _F16 or _I8");
+    if (reinterpret_cast<uintptr_t>(llr) % esize) return fail(LUTLDPC_ERR_ARG, "llr is not aligned to its element size");
+    const int N = d->nvar;
+    if (io->frame_stride != 0 && io->frame_stride < N) return fail(LUTLDPC_ERR_ARG, "frame_stride must be 0 or at least nvar");
+    LlrCells C;
+    const std::string err = llr_cell_table(*io, d->Nq_Cha, d->Nq_Msg[0], C);
+    if (!err.empty()) return fail(LUTLDPC_ERR_ARG, err);
+    if (out_words && (io->out_first < 0 || io->out_count < 1 || (int64_t)io->out_first + io->out_count > N)) return fail(LUTLDPC_ERR_ARG, "output window outside [0, nvar)");
+    if (!out_words && !out_iters && !out_cha && !out_msg0) return fail(LUTLDPC_ERR_ARG, "no output asked for");
+    int rc = batch_entry(d, B);
+    if (rc) return rc;
+    const bool dev = io->on_device != 0, decode = out_words || out_iters;
+    const size_t stride = io->frame_stride ? (size_t)io->frame_stride : (size_t)N;
+    const void *src = llr;
+    if (!dev) {         // the whole batch, gaps included, up to the last element read
+        const size_t bytes = ((size_t)(B - 1) * stride + (size_t)N) * esize;
+        HIP_TRY(d->d_llr_in.alloc((bytes + 7) / 8));
+        HIP_TRY(hipMemcpyAsync(d->d_llr_in.p, llr, bytes, hipMemcpyHostToDevice, d->stream));
+        src = d->d_llr_in.p;
+    }
+    if ((rc = ensure_batch(d, B))) return rc;
+    const int G = d->bpad(B) / d->tile();
+    {
+        Timed t(d, LUTLDPC_K_LAYOUT);
+        DEV_PARAM(tab, d, device_tables(C, io->dtype));
+        switch (io->dtype) {
+        case LUTLDPC_LLR_F64: rc = launch_llr_labels_in<double>(d, src, stride, tab, C.n_thr, B, G); break;
+        case LUTLDPC_LLR_F32: rc = launch_llr_labels_in<float>(d, src, stride, tab, C.n_thr, B, G); break;
+        case LUTLDPC_LLR_F16: rc = launch_llr_labels_in<_Float16>(d, src, stride, tab, C.n_thr, B, G); break;
+        default: rc = launch_llr_labels_in<int8_t>(d, src, stride, tab, C.n_thr, B, G); break;
+        }
+        if (rc) return rc;
+    }
+    // the labels the device derived, read back from the rows before the decode works on them
+    const uint8_t *rows[2] = {d->d_cha_t.p, d->d_msg0_t.p};
+    uint8_t *labels[2] = {out_cha, out_msg0};
+    for (int i = 0; i < 2; i++) {
+        if (!labels[i]) continue;
+        if (!dev) { if ((rc = rows_to_host(d, rows[i], labels[i], B))) return rc; continue; }
+        Timed t(d, LUTLDPC_K_LAYOUT);
+        if ((rc = launch_transpose_out(d, rows[i], labels[i], B, G))) return rc;
+    }
+    if (decode && (rc = decode_tiles(d, B))) return rc;
+    if (out_words) {
+        const int W = (io->out_count + 31) / 32;
+        uint32_t *dst = out_words;
+        if (!dev) { HIP_TRY(d->d_out_words.alloc((size_t)B * (size_t)W)); dst = d->d_out_words.p; }
+        {
+            Timed t(d, LUTLDPC_K_LAYOUT);
+            if ((rc = launch_bits_out(d, dst, B, G, io->out_first, io->out_count))) return rc;
+        }
+        if (!dev && (rc = copy_to_host(d, out_words, dst, sizeof(uint32_t) * (size_t)B * (size_t)W))) return rc;
+    }
+    if (out_iters) {
+        if (dev) HIP_TRY(hipMemcpyAsync(out_iters, d->d_iters.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToDevice, d->stream));
+        else if ((rc = iters_to_host(d, out_iters, B))) return rc;
+    }
+    if (!dev || io->sync) HIP_TRY(hipStreamSynchronize(d->stream));
+    return LUTLDPC_OK;
+}

@@ -27,6 +27,15 @@ static int launch_labels_in(lutldpc_decoder *d, const uint8_t *src, size_t strid
     return LUTLDPC_OK;
 }
 
+// decided bits first .. first + count - 1 of the B frames in d_hard -> dst[B][ceil(count / 32)] (device), one bit each
+int launch_bits_out(lutldpc_decoder *d, uint32_t *dst, int B, int G, int first, int count) {
+    const int W = (count + 31) / 32;
+    PACK_DISPATCH(d, launch_k(packed_bits_out_kernel<PK>, dim3((unsigned)((W + kBitsCols - 1) / kBitsCols), (unsigned)G), dim3(256), 0, d->stream,
+                              d->d_hard.p, dst, B, d->nvar, first, count, W));
+    LAUNCH_CHECK();
+    return LUTLDPC_OK;
+}
+
 #pragma GCC visibility pop
 
 extern "C" int lutldpc_decoder_decode_batch_packed(lutldpc_decoder *d, const lutldpc_packed_io *io, const uint8_t *cha, const uint8_t *msg0, int B,
@@ -74,9 +83,7 @@ extern "C" int lutldpc_decoder_decode_batch_packed(lutldpc_decoder *d, const lut
         HIP_TRY(d->d_out_words.alloc((size_t)B * (size_t)W));
         {
             Timed t(d, LUTLDPC_K_LAYOUT);
-            PACK_DISPATCH(d, launch_k(packed_bits_out_kernel<PK>, dim3((unsigned)((W + kBitsCols - 1) / kBitsCols), (unsigned)G), dim3(256), 0, d->stream,
-                                      d->d_hard.p, d->d_out_words.p, B, N, io->out_first, io->out_count, W));
-            LAUNCH_CHECK();
+            if ((rc = launch_bits_out(d, d->d_out_words.p, B, G, io->out_first, io->out_count))) return rc;
         }
         if ((rc = copy_to_host(d, out_words, d->d_out_words.p, sizeof(uint32_t) * (size_t)B * (size_t)W))) return rc;
     }

@@ -15,6 +15,7 @@
 //   decoder_stats.hip      message-label histograms per dump: edge groups, the counted decode, C-ABI   (kernels_stats.hpp)
 //   decoder_events.hip     failed frames captured on the device: weights, selection, sorted error / syndrome lists, C-ABI   (kernels_events.hpp)
 //   decoder_packed.hip     packed label input and bit-packed output of the host-side batch decode, C-ABI                    (kernels_packed.hpp)
+//   decoder_llr.hip        float64 / float32 / float16 / int8 soft values from host or device memory into both row sets, C-ABI (kernels_llr.hpp, llr_cells.hpp)
 #pragma once
 #include "../../../include/lut_ldpc_hip.h"
 #include "kernels_common.hpp"
@@ -218,6 +219,7 @@ struct lutldpc_decoder {
     DevBuf<int32_t> d_out_iters;
     DevBuf<uint32_t> d_out_words;                     // decode_batch_packed: [B][ceil(out_count/32)] decided bits, one each
     DevBuf<double> d_llr, d_qb_cha, d_qb_msg;
+    DevBuf<uint64_t> d_llr_in;                        // decode_llr_packed: host values of any element type, staged as they came
     DevBuf<int32_t> d_map;
     DevBuf<uint8_t> d_codewords;                      // upload staging of sent_rows_from_host; no kernel but its conversion reads it
     DevBuf<int32_t> d_stats;
@@ -470,5 +472,9 @@ int capture_events(lutldpc_decoder *d, int B, int K_info, const uint8_t *sent_ro
 
 // ---- decoder_packed.hip (home of the kernels of kernels_packed.hpp)
 hipError_t preload_packed_kernels();
+int launch_bits_out(lutldpc_decoder *d, uint32_t *dst, int B, int G, int first, int count);     // a window of d_hard -> dst[B][ceil(count/32)], device
+
+// ---- decoder_llr.hip (home of the kernel of kernels_llr.hpp)
+hipError_t preload_llr_kernels();
 
 #pragma GCC visibility pop

@@ -190,6 +190,70 @@ class Decoder:
                                                    _p(out, C.c_uint8), _p(iters, C.c_int32)))
         return out, iters
 
+    def decode_llr(self, llr, qb_cha, qb_msg=None, cha2msg_map=None, scale=None, first=0, count=None, want_labels=False, decode=True):
+        """decode(llr) for receivers (lutldpc_decoder_decode_llr_packed): llr is [B, nvar] float64, float32, float16 or int8 (then
+        LLR = scale * q), a numpy array or a torch tensor on the decoder's device (2-D, last dimension contiguous, row stride >=
+        nvar; read in place).  qb_cha with either qb_msg (mode CONT) or cha2msg_map (mode QCHA).  Returns (words, iters): the decided
+        bits first .. first+count-1 of every frame, one bit each (packing.unpack_bits; count=None: up to nvar), with
+        want_labels=True also (cha, msg0) as the device derived them; decode=False only quantises and returns (cha, msg0).
+        For a tensor the results are tensors on its device (words as int32: the same 32 bits), the tensor's current stream is
+        synchronised before the call and the decoder's stream before it returns."""
+        qc = np.ascontiguousarray(qb_cha, np.float64)
+        qm = np.ascontiguousarray(qb_msg, np.float64) if qb_msg is not None else None
+        mp = _i32(cha2msg_map) if cha2msg_map is not None else None
+        if (qm is None) == (mp is None):
+            raise ValueError("give either qb_msg (mode CONT) or cha2msg_map (mode QCHA)")
+        if mp is not None and len(mp) != len(qc) + 1:
+            raise ValueError("cha2msg_map must hold one entry per channel label")
+        on_device = not isinstance(llr, np.ndarray) and hasattr(llr, "data_ptr")
+        if on_device:
+            import torch
+            names = {torch.float64: _capi.LLR_F64, torch.float32: _capi.LLR_F32, torch.float16: _capi.LLR_F16, torch.int8: _capi.LLR_I8}
+            if not llr.is_cuda:
+                raise ValueError("a torch tensor must live on the device; pass host values as a numpy array")
+        else:
+            if not isinstance(llr, np.ndarray):
+                raise ValueError("llr must be a numpy array or a torch tensor on the device")
+            names = {np.dtype(np.float64): _capi.LLR_F64, np.dtype(np.float32): _capi.LLR_F32, np.dtype(np.float16): _capi.LLR_F16,
+                     np.dtype(np.int8): _capi.LLR_I8}
+        if llr.dtype not in names:
+            raise ValueError("llr must be float64, float32, float16 or int8")
+        dtype = names[llr.dtype]
+        if llr.ndim != 2 or llr.shape[1] != self.nvar or llr.shape[0] < 1:
+            raise ValueError("llr must be [B, nvar]")
+        if dtype == _capi.LLR_I8 and scale is None:
+            raise ValueError("int8 values need a scale: LLR = scale * q")
+        if not decode and not want_labels:
+            want_labels = True
+        B, N = int(llr.shape[0]), self.nvar
+        count = N - int(first) if count is None else int(count)
+        W = max((count + 31) // 32, 0)
+        if on_device:
+            if llr.stride(1) != 1 or (B > 1 and llr.stride(0) < N):
+                raise ValueError("a tensor needs a contiguous last dimension and a row stride of at least nvar")
+            stride = int(llr.stride(0)) if B > 1 else N
+            dev = llr.device
+            torch.cuda.current_stream(dev).synchronize()
+            words = torch.empty((B, W), dtype=torch.int32, device=dev) if decode else None
+            iters = torch.empty(B, dtype=torch.int32, device=dev) if decode else None
+            cha = torch.empty((B, N), dtype=torch.uint8, device=dev) if want_labels else None
+            msg = torch.empty((B, N), dtype=torch.uint8, device=dev) if want_labels else None
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        else:
+            llr = np.ascontiguousarray(llr)
+            stride = N
+            words = np.empty((B, W), np.uint32) if decode else None
+            iters = np.empty(B, np.int32) if decode else None
+            cha = np.empty((B, N), np.uint8) if want_labels else None
+            msg = np.empty((B, N), np.uint8) if want_labels else None
+            ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
+        io = _capi.LlrIO(dtype, int(on_device), stride, float(scale) if scale is not None else 0.0, _p(qc, C.c_double), len(qc),
+                         _p(qm, C.c_double) if qm is not None else None, len(qm) if qm is not None else 0, 0 if qm is not None else 1,
+                         _p(mp, C.c_int32) if mp is not None else None, int(first), count, 1)
+        check(lib.lutldpc_decoder_decode_llr_packed(self._h, C.byref(io), ptr(llr), B, ptr(words), ptr(iters), ptr(cha), ptr(msg)))
+        out = (words, iters) if decode else ()
+        return out + (cha, msg) if want_labels else out
+
     # ---- device buffers (raw pointers, e.g. torch.Tensor.data_ptr()) -------------------------
     def lut_decode_batch_device(self, d_cha: int, d_msg0: int, B: int, d_out_bits: int, d_out_iters: int, sync=False):
         check(lib.lutldpc_decoder_decode_batch_device(self._h, C.c_void_p(d_cha), C.c_void_p(d_msg0), int(B),
