@@ -262,6 +262,32 @@ int lutldpc_decoder_encode_random(lutldpc_decoder *d, uint64_t seed, uint32_t st
 int lutldpc_decoder_sim_batch_random(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream,
                                      uint64_t frame0, int B, int K_info, int32_t *frame_stats, uint8_t *cha_out, uint8_t *bits_out);
 
+/*
+ * The caller's data bits encoded on the device: the transmit-side counterpart of lutldpc_decoder_decode_batch_packed /
+ * lutldpc_decoder_decode_llr_packed, in the bit-packed format those return.  Codeword = [u | parity] in the decoder's column order,
+ * parity bit i = popcount(A_i & u) mod 2 over the rows given to lutldpc_decoder_set_generator (K information bits, R rows).
+ *   info       [B][in_stride] uint32: bit j of word w of a frame = information bit 32w + j (the layout of out_words).  Bits at
+ *              positions >= K of the last word are ignored; words ceil(K/32) .. in_stride-1 of a frame are never read by the kernel.
+ *   out_words  [B][ceil(out_count/32)] uint32: bit j of word w = codeword bit out_first + 32w + j, bits beyond out_count are 0.
+ *              (0, nvar) is the whole codeword, (K, R) the parity alone.
+ * Both buffers live in host memory (io->on_device = 0; the call is synchronous) or both in device memory (1): then the contract of
+ * lutldpc_decoder_decode_batch_device holds -- the call runs on the decoder's own stream, the buffers must be complete and not in
+ * use by another stream, and it is asynchronous unless io->sync is set.  Only 4-byte alignment is asked of either pointer.
+ * The entry reads the generator only: it needs no label rows, leaves the state of the decode entries alone, and a refused call
+ * writes nothing.
+ * Errors: NULL handle or B <= 0 -> LUTLDPC_ERR_ARG; then the entry's own arguments, LUTLDPC_ERR_ARG too: NULL io, info or out_words,
+ * a pointer not 4-byte aligned, in_stride negative or (where a generator is set, which gives K) positive and below ceil(K/32),
+ * out_first < 0, out_count < 1, out_first + out_count > nvar; then a handle without a device -> LUTLDPC_ERR_STATE; then no
+ * generator set -> LUTLDPC_ERR_STATE (lutldpc_decoder_set_generator comes first).
+ */
+typedef struct {
+    int32_t on_device;            /* 0: info and out_words are host memory; 1: both are device memory */
+    int64_t in_stride;            /* uint32 words from one frame to the next; 0 = ceil(K/32), else >= ceil(K/32) */
+    int32_t out_first, out_count; /* codeword bits out_first .. out_first+out_count-1, as lutldpc_packed_io */
+    int32_t sync;                 /* on_device = 1: synchronise the decoder's stream before returning */
+} lutldpc_encode_io;
+int lutldpc_decoder_encode_packed(lutldpc_decoder *d, const lutldpc_encode_io *io, const uint32_t *info, int B, uint32_t *out_words);
+
 /* The labels the sampler would produce for those frames (host, frame-major [B*nvar]); codewords as for sim_batch; for tests. */
 int lutldpc_decoder_sample_labels(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream,
                                   uint64_t frame0, int B, const uint8_t *codewords, uint8_t *cha, uint8_t *msg0);

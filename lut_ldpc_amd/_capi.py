@@ -67,8 +67,14 @@ class LlrIO(C.Structure):
                 ("sync", C.c_int32)]
 
 
+class EncodeIO(C.Structure):
+    """lutldpc_encode_io (include/lut_ldpc_hip.h): location and frame stride of the packed information words, the window of codeword bits."""
+    _fields_ = [("on_device", C.c_int32), ("in_stride", C.c_int64), ("out_first", C.c_int32), ("out_count", C.c_int32), ("sync", C.c_int32)]
+
+
 _u32p = C.POINTER(C.c_uint32)
 _SIGNATURES = {
+    "lutldpc_decoder_encode_packed": (C.c_int, [_vp, C.POINTER(EncodeIO), _vp, C.c_int, _vp]),
     "lutldpc_decoder_decode_llr_packed": (C.c_int, [_vp, C.POINTER(LlrIO), _vp, C.c_int, _vp, _vp, _vp, _vp]),
     "lutldpc_llr_cell_table": (C.c_int, [C.POINTER(LlrIO), C.c_int, C.c_int, _dp, C.c_int32, _ip, _u8p, _u8p]),
     "lutldpc_last_error": (_cp, []),

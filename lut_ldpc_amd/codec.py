@@ -206,6 +206,23 @@ class Codec:
         check(lib.lutldpc_codec_encode_random(self._h, int(seed), int(stream), int(frame0), int(B), _p(cw, C.c_uint8)))
         return cw
 
+    def encode_packed(self, data, parity_only=False):
+        """The caller's data encoded on the device (Decoder.encode_packed): data is [B, W >= ceil(ninfo/32)] packed words (numpy uint32 /
+        int32, or a torch int32 tensor on the device; packing.pack_bits makes them), or a 0/1 uint8 array [B, ninfo], which is packed
+        first.  Returns the codewords [u | parity] as [B, ceil(nvar/32)] words, or with parity_only the rank(H) parity bits alone,
+        [B, ceil(rank/32)]; same kind of array, same place."""
+        dec = self.decoder()
+        if "generator" not in dec.describe():
+            raise ValueError("encode_packed needs the generator on the device: make the Codec with with_generator=True on a device "
+                             "(the device encoder holds at most 8192 information bits)")
+        if isinstance(data, np.ndarray) and data.dtype == np.uint8:
+            from .packing import pack_bits
+            if data.ndim != 2 or data.shape[1] != self.ninfo:
+                raise ValueError("a uint8 array of data bits must be [B, ninfo]")
+            data = pack_bits(data)
+        first, count = (self.ninfo, self.rank) if parity_only else (0, self.nvar)
+        return dec.encode_packed(data, first=first, count=count)
+
     def channel_cells(self, snr_db):
         thr = np.zeros(72, np.uint64)
         arrs = [np.zeros(72, np.uint8) for _ in range(5)]

@@ -1,5 +1,5 @@
-// decoder_frontend.hip -- the simulation front end on the device: channel sampler, random-codeword encoder, error counters, and
-// the C-ABI entries built on them.  Home of every kernel of kernels_frontend.hpp and kernels_encode.hpp.
+// decoder_frontend.hip -- the simulation front end on the device: channel sampler, random-codeword encoder, error counters, the
+// encoder of the caller's packed data bits, and the C-ABI entries built on them.  Home of every kernel of kernels_frontend.hpp and kernels_encode.hpp.
 #include "decoder_state.hpp"
 #include "kernels_frontend.hpp"
 #include "kernels_encode.hpp"
@@ -165,6 +165,47 @@ int lutldpc_decoder_encode_random(lutldpc_decoder *d, uint64_t seed, uint32_t st
         if ((rc = launch_sent_to_bytes(d, d->d_out_bits.p, B)) || (rc = copy_to_host(d, codewords, d->d_out_bits.p, n))) return rc;
     }
     HIP_TRY(hipStreamSynchronize(d->stream));
+    return LUTLDPC_OK;
+}
+
+// The caller's information bits -> codewords, bit-packed both ways, in host or device memory (encode_bits_kernel).  Works on its
+// own staging buffers and the generator alone: no label rows, no frame-group state of a decode.
+int lutldpc_decoder_encode_packed(lutldpc_decoder *d, const lutldpc_encode_io *io, const uint32_t *info, int B, uint32_t *out_words) {
+    if (!d) return fail(LUTLDPC_ERR_ARG, "NULL decoder");
+    if (B <= 0) return fail(LUTLDPC_ERR_ARG, "B must be positive");
+    if (!io || !info || !out_words) return fail(LUTLDPC_ERR_ARG, "NULL argument: io, info and out_words are required");
+    if (reinterpret_cast<uintptr_t>(info) % 4 || reinterpret_cast<uintptr_t>(out_words) % 4) return fail(LUTLDPC_ERR_ARG, "info and out_words must be 4-byte aligned");
+    const int N = d->nvar, W32 = (d->gen_K + 31) / 32;              // (a handle without a generator: W32 = 0, and the state error below)
+    if (io->in_stride < 0 || (io->in_stride != 0 && io->in_stride < W32)) return fail(LUTLDPC_ERR_ARG, "in_stride must be 0 or at least ceil(K/32)");
+    if (io->out_first < 0 || io->out_count < 1 || (int64_t)io->out_first + io->out_count > N) return fail(LUTLDPC_ERR_ARG, "output window outside [0, nvar)");
+    int rc = batch_entry(d, B);
+    if (rc) return rc;
+    if (!d->gen_set) return fail(LUTLDPC_ERR_STATE, "encode_packed: no generator set (lutldpc_decoder_set_generator)");
+    const bool dev = io->on_device != 0;
+    const int K = d->gen_K, R = d->gen_R, Wout = (io->out_count + 31) / 32;
+    const size_t stride = io->in_stride ? (size_t)io->in_stride : (size_t)W32;
+    const uint32_t *src = info;
+    uint32_t *dst = out_words;
+    if (!dev) {         // the whole batch, gaps included, up to the last word read
+        const size_t words = (size_t)(B - 1) * stride + (size_t)W32;
+        HIP_TRY(d->d_llr_in.alloc((words + 1) / 2));
+        HIP_TRY(hipMemcpyAsync(d->d_llr_in.p, info, words * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
+        src = reinterpret_cast<const uint32_t *>(d->d_llr_in.p);
+        HIP_TRY(d->d_out_words.alloc((size_t)B * (size_t)Wout));
+        dst = d->d_out_words.p;
+    }
+    {
+        Timed t(d, LUTLDPC_K_FRONTEND);
+        // one wave per output word that holds parity rows (at least one information-only word per wave where those are fewer)
+        const int c_last = io->out_first + io->out_count - 1;
+        const int n_par = c_last < K ? 0 : Wout - std::max(0, (K - io->out_first) / 32);
+        const unsigned gx = (unsigned)((B + kEncFrames - 1) / kEncFrames), gy = (unsigned)std::max(1, (std::max(n_par, (Wout - n_par + 7) / 8) + 3) / 4);
+        launch_k(encode_bits_kernel, dim3(gx, gy), dim3(256), (size_t)((K + 127) / 128) * kEncFrames * 16, d->stream, d->d_gen.p, K, R, d->gen_W32p, src, stride, B,
+                 io->out_first, io->out_count, dst);
+        LAUNCH_CHECK();
+    }
+    if (!dev && (rc = copy_to_host(d, out_words, dst, sizeof(uint32_t) * (size_t)B * (size_t)Wout))) return rc;
+    if (!dev || io->sync) HIP_TRY(hipStreamSynchronize(d->stream));
     return LUTLDPC_OK;
 }
 

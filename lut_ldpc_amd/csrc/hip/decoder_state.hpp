@@ -217,9 +217,9 @@ struct lutldpc_decoder {
     DevBuf<int32_t> d_iters;
     DevBuf<uint8_t> d_in_cha, d_in_msg, d_out_bits;   // frame-major staging for the host entry points
     DevBuf<int32_t> d_out_iters;
-    DevBuf<uint32_t> d_out_words;                     // decode_batch_packed: [B][ceil(out_count/32)] decided bits, one each
+    DevBuf<uint32_t> d_out_words;                     // decode_batch_packed: [B][ceil(out_count/32)] decided bits, one each (encode_packed: codeword bits)
     DevBuf<double> d_llr, d_qb_cha, d_qb_msg;
-    DevBuf<uint64_t> d_llr_in;                        // decode_llr_packed: host values of any element type, staged as they came
+    DevBuf<uint64_t> d_llr_in;                        // decode_llr_packed: host values of any element type, staged as they came (encode_packed: host information words)
     DevBuf<int32_t> d_map;
     DevBuf<uint8_t> d_codewords;                      // upload staging of sent_rows_from_host; no kernel but its conversion reads it
     DevBuf<int32_t> d_stats;

@@ -1,5 +1,6 @@
 // kernels_encode.hpp -- random codewords on the device (zero_codeword = false): the information bits of
-// random_info_bits (host/ber_sim_driver.cpp) and the parity of LDPC_Generator_Systematic::encode, for a batch of frames.
+// random_info_bits (host/ber_sim_driver.cpp) and the parity of LDPC_Generator_Systematic::encode, for a batch of frames
+// (encode_random_kernel); and the same parity for information bits the caller hands in, bit-packed in and out (encode_bits_kernel).
 //
 // Information bits: Philox4x32-10, key = seed, counter = (frame lo, frame hi, k / 128, stream | 0x80000000); output word j
 // of block c holds bits 128c + 32j .. 128c + 32j + 31 (bit b = info bit 128c + 32j + b), exactly as on the host.
@@ -81,6 +82,88 @@ __global__ __launch_bounds__(256) void encode_random_kernel(const uint32_t *__re
         }
         const int i = t * kEncTileRows + lane;
         if (lane < kEncTileRows && i < R) *reinterpret_cast<uint64_t *>(sent + ((size_t)g * N + K + i) * RB + byte0) = mine;
+    }
+}
+
+// The caller's information bits -> codewords, both bit-packed and frame-major (lutldpc_decoder_encode_packed): the arithmetic of
+// encode_random_kernel (one lane = one frame, u[c][lane] in LDS, wave-uniform A words, acc ^= a & u, popcount parity) with loads in
+// place of Philox and words in place of sent-bit rows.
+//
+// info: [B][in_stride] dwords, bit j of word w = information bit 32w + j; words ceil(K/32) .. in_stride-1 are never read, bits at
+// positions >= K of the last word are masked.  A wave reads consecutive words of one frame (coalesced dwords) and writes them to
+// that frame's column of u_lds: the LDS write is the transposition.  Frames >= B load nothing (zeros in LDS) and store nothing.
+//
+// out: [B][Wout] dwords, Wout = ceil(out_count/32); bit j of word w = codeword bit out_first + 32w + j, zero beyond out_count.
+// The 32-row tiles are aligned to the OUTPUT words: the wave that owns word w (c0 = out_first + 32w) takes the information bits
+// c0 .. min(K, c0+32)-1 from LDS (a funnel shift of two words) and computes the parity rows max(0, c0-K) .. min(R, c0+32-K)-1, which land
+// at bit max(0, K-c0) upwards: K % 32 != 0 and any out_first are that one shift.  A lane owns its frame, so it assembles the word
+// from its own 32 parities and stores it once: no ballot, no atomics, no word written by two waves.  Rows past the tile's last
+// one are read from the row Rp-1 at most (the generator's pad rows keep that in bounds) and masked off; words below K need no A.
+//
+// grid (ceil(B/64), ny), 256 threads, dynamic LDS = ceil(K/128) * 64 * 16 bytes (as encode_random_kernel).  Wave w of workgroup
+// (x, y) takes the output words 4y + w, 4y + w + 4ny, ...
+__global__ __launch_bounds__(256) void encode_bits_kernel(const uint32_t *__restrict__ A, int K, int R, int W32p, const uint32_t *__restrict__ info,
+                                                          size_t in_stride, int B, int out_first, int out_count, uint32_t *__restrict__ out)
+{
+    extern __shared__ uint4 u_lds[];                                   // [c][lane]
+    uint32_t *u_words = reinterpret_cast<uint32_t *>(u_lds);           // word x of lane l: u_words[((x >> 2) * 64 + l) * 4 + (x & 3)]
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform: the A addresses below go to scalar loads)
+    const int W128 = (K + 127) >> 7, W32 = (K + 31) >> 5, Rp = (R + kEncTileRows - 1) / kEncTileRows * kEncTileRows;
+    const int Wout = (out_count + 31) >> 5;
+    const int fb = blockIdx.x * kEncFrames;                            // first frame of the workgroup
+    const int fl = fb + lane;
+    const uint32_t last_mask = (K & 31) ? (1u << (K & 31)) - 1u : 0xFFFFFFFFu;
+    // frame fb + j of the workgroup: wave j % 4 reads its words lane, lane + 64, ...; the spare words of the last block are zero
+    for (int j = wv; j < kEncFrames; j += 4) {
+        const bool live = fb + j < B;                                  // (wave-uniform)
+        const uint32_t *src = info + (size_t)(fb + j) * in_stride;
+        for (int x = lane; x < 4 * W128; x += 64) {
+            uint32_t v = 0;
+            if (live && x < W32) v = src[x] & (x == W32 - 1 ? last_mask : 0xFFFFFFFFu);
+            u_words[((x >> 2) * kEncFrames + j) * 4 + (x & 3)] = v;
+        }
+    }
+    __syncthreads();
+    const int step = (int)gridDim.y * 4, first = (int)blockIdx.y * 4 + wv;
+    for (int w = first; w < Wout; w += step) {
+        const int c0 = out_first + 32 * w;                             // codeword bit at bit 0 of this word
+        uint32_t word = 0;
+        if (c0 < K) {                                                  // information bits c0 .. : words x0, x0 + 1 shifted down by s
+            const int x0 = c0 >> 5, s = c0 & 31;
+            const uint32_t lo = u_words[((x0 >> 2) * kEncFrames + lane) * 4 + (x0 & 3)];
+            const uint32_t hi = (s && x0 + 1 < W32) ? u_words[(((x0 + 1) >> 2) * kEncFrames + lane) * 4 + ((x0 + 1) & 3)] : 0u;
+            word = s ? (lo >> s) | (hi << (32 - s)) : lo;
+        }
+        const int jlo = c0 < K ? K - c0 : 0;                           // bit of the first parity row of this word (>= 32: none)
+        const int r0 = c0 < K ? 0 : c0 - K;                            // that row
+        const int nrows = min(R - r0, 32 - jlo);                       // rows r0 .. r0 + nrows - 1 (wave-uniform)
+        if (jlo < 32 && nrows > 0) {
+            uint32_t acc[kEncTileRows];
+            uint32_t roff[kEncTileRows];                               // row i of the tile in A; past the tile: a row in bounds, masked below
+#pragma unroll
+            for (int i = 0; i < kEncTileRows; i++) { acc[i] = 0; roff[i] = (uint32_t)min(r0 + i, Rp - 1) * (uint32_t)W32p; }
+            for (int c = 0; c < W128; c++) {
+                const uint4 u = u_lds[c * kEncFrames + lane];
+#pragma unroll
+                for (int i = 0; i < kEncTileRows; i++) {
+                    const uint4 a = *reinterpret_cast<const uint4 *>(A + roff[i] + 4 * c);
+                    // acc ^ (a & u): truth table from acc = 0xF0, a = 0xCC, u = 0xAA
+                    acc[i] = __builtin_amdgcn_bitop3_b32(acc[i], a.x, u.x, 0x78);
+                    acc[i] = __builtin_amdgcn_bitop3_b32(acc[i], a.y, u.y, 0x78);
+                    acc[i] = __builtin_amdgcn_bitop3_b32(acc[i], a.z, u.z, 0x78);
+                    acc[i] = __builtin_amdgcn_bitop3_b32(acc[i], a.w, u.w, 0x78);
+                }
+            }
+            uint32_t par = 0;
+#pragma unroll
+            for (int i = 0; i < kEncTileRows; i++) par |= (uint32_t)(__builtin_popcount(acc[i]) & 1) << i;
+            if (nrows < 32) par &= (1u << nrows) - 1u;
+            word |= par << jlo;
+        }
+        const int left = out_count - 32 * w;                           // bits of the window in this word
+        if (left < 32) word &= (1u << left) - 1u;
+        if (fl < B) out[(size_t)fl * Wout + w] = word;
     }
 }
 

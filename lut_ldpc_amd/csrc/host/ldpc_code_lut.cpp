@@ -387,6 +387,13 @@ lutldpc_decoder *LDPC_Code_LUT::device_handle() {
     return dev;
 }
 
+void LDPC_Code_LUT::encode_packed(const uint32_t *info, int B, uint32_t *codewords) {
+    if (!has_device_generator()) throw std::logic_error("LDPC_Code_LUT::encode_packed(): no generator on the device (with_generator, at most 8192 information bits)");
+    lutldpc_encode_io io{};
+    io.out_first = 0; io.out_count = nvar;
+    if (lutldpc_decoder_encode_packed(dev, &io, info, B, codewords) != LUTLDPC_OK) hip_fail("LDPC_Code_LUT::encode_packed()");
+}
+
 void LDPC_Code_LUT::lut_decode_batch(const uint8_t *cha, const uint8_t *msg0, int B, uint8_t *bits, int32_t *iters) {
     if (output_verbosity > 1) { lut_decode_batch_dump(cha, msg0, B, bits, iters, output_verbosity > 2 ? 3 : 2, std::cout); return; }
     if (lutldpc_decoder_decode_batch(device_handle(), cha, msg0, B, bits, iters) != LUTLDPC_OK) hip_fail("LDPC_Code_LUT::lut_decode()");

@@ -97,6 +97,10 @@ public:
     // the device handle holds the generator: random codewords can be made on the device (false for generators of more
     // than 8192 information bits, which stay on the host encoder)
     bool has_device_generator() { device_handle(); return dev_generator; }
+    // the caller's data encoded on the device (lutldpc_decoder_encode_packed), host memory: info = [B][ceil(ninfo/32)] words, bit j of
+    // word w = information bit 32w + j; codewords = [B][ceil(nvar/32)] words in the same bit order.  Throws std::logic_error where
+    // the device handle holds no generator
+    void encode_packed(const uint32_t *info, int B, uint32_t *codewords);
 
     double get_rate() const { return 1.0 - static_cast<double>(nchk_lin_indep) / nvar; }
     int get_nvar() const { return nvar; }

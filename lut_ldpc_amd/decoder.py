@@ -254,6 +254,44 @@ class Decoder:
         out = (words, iters) if decode else ()
         return out + (cha, msg) if want_labels else out
 
+    def encode_packed(self, info_words, first=0, count=None, sync=True):
+        """The caller's data bits encoded on the device (lutldpc_decoder_encode_packed; the generator of set_generator): info_words
+        is [B, W] with W >= ceil(K/32), bit j of word w = information bit 32w + j (packing.pack_bits) -- a numpy uint32 / int32
+        array, or a torch int32 tensor on the decoder's device (2-D, last dimension contiguous; read in place).  Returns the
+        codeword bits first .. first+count-1 of every frame, one bit each, [B, ceil(count/32)] (packing.unpack_bits; count=None: up
+        to nvar): a numpy uint32 array, or an int32 tensor on the tensor's device.  For a tensor the tensor's current stream is
+        synchronised before the call and (sync=True) the decoder's stream before it returns."""
+        on_device = not isinstance(info_words, np.ndarray) and hasattr(info_words, "data_ptr")
+        if on_device:
+            import torch
+            if not info_words.is_cuda:
+                raise ValueError("a torch tensor must live on the device; pass host words as a numpy array")
+            if info_words.dtype != torch.int32:
+                raise ValueError("a tensor of information words must be int32")
+        else:
+            if not isinstance(info_words, np.ndarray) or info_words.dtype not in (np.dtype(np.uint32), np.dtype(np.int32)):
+                raise ValueError("info_words must be a numpy uint32 / int32 array or a torch int32 tensor on the device")
+        if info_words.ndim != 2 or info_words.shape[0] < 1 or info_words.shape[1] < 1:
+            raise ValueError("info_words must be [B, W]")
+        B, W = int(info_words.shape[0]), int(info_words.shape[1])
+        count = self.nvar - int(first) if count is None else int(count)
+        Wout = max((count + 31) // 32, 0)
+        if on_device:
+            if info_words.stride(1) != 1 or (B > 1 and info_words.stride(0) < W):
+                raise ValueError("a tensor needs a contiguous last dimension and a row stride of at least its width")
+            stride = int(info_words.stride(0)) if B > 1 else W
+            torch.cuda.current_stream(info_words.device).synchronize()
+            out = torch.empty((B, Wout), dtype=torch.int32, device=info_words.device)
+            src, dst = C.c_void_p(info_words.data_ptr()), C.c_void_p(out.data_ptr())
+        else:
+            info_words = np.ascontiguousarray(info_words)
+            stride = W
+            out = np.empty((B, Wout), np.uint32)
+            src, dst = C.c_void_p(info_words.ctypes.data), C.c_void_p(out.ctypes.data)
+        io = _capi.EncodeIO(int(on_device), stride, int(first), count, int(bool(sync)))
+        check(lib.lutldpc_decoder_encode_packed(self._h, C.byref(io), src, B, dst))
+        return out
+
     # ---- device buffers (raw pointers, e.g. torch.Tensor.data_ptr()) -------------------------
     def lut_decode_batch_device(self, d_cha: int, d_msg0: int, B: int, d_out_bits: int, d_out_iters: int, sync=False):
         check(lib.lutldpc_decoder_decode_batch_device(self._h, C.c_void_p(d_cha), C.c_void_p(d_msg0), int(B),

@@ -1,5 +1,6 @@
 """Host-side formats of Decoder.decode_packed (lutldpc_decoder_decode_batch_packed, include/lut_ldpc_hip.h): labels two per byte
-going in, decided bits one per bit coming out.  Plain numpy, no device.
+going in, decided bits one per bit coming out -- and of Decoder.encode_packed, which takes and returns bits in that bit format.
+Plain numpy, no device.
 
 Nibble format (LUTLDPC_IN_NIBBLES): frame stride ceil(N/2) bytes, node v in byte v // 2, even v in bits 0-3, odd v in bits 4-7;
 the spare nibble of an odd N is written as 0 here and ignored by the decoder.
@@ -44,3 +45,18 @@ def unpack_bits(words, count: int) -> np.ndarray:
     shifts = np.arange(32, dtype=np.uint32)
     bits = (words[:, :, None] >> shifts[None, None, :]) & np.uint32(1)
     return np.ascontiguousarray(bits.reshape(words.shape[0], -1)[:, :count].astype(np.uint8))
+
+
+def pack_bits(bits) -> np.ndarray:
+    """bits[B, n] of 0 / 1 -> uint32[B, ceil(n/32)], the inverse of unpack_bits: bit j of word w = bit 32w + j, the spare bits of the
+    last word are 0.  The input format of Decoder.encode_packed."""
+    bits = np.asarray(bits)
+    if bits.ndim != 2:
+        raise ValueError("bits must be [B, n]")
+    if bits.size and (bits.min() < 0 or bits.max() > 1):
+        raise ValueError("bits must be 0 or 1")
+    B, n = bits.shape
+    padded = np.zeros((B, (n + 31) // 32 * 32), np.uint32)
+    padded[:, :n] = bits
+    shifts = np.arange(32, dtype=np.uint32)
+    return np.ascontiguousarray((padded.reshape(B, -1, 32) << shifts[None, None, :]).sum(axis=2, dtype=np.uint32))
