@@ -198,8 +198,8 @@ int tiles_from_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d
     if (rc) return rc;
     const int G = d->bpad(B) / d->tile();
     Timed t(d, LUTLDPC_K_LAYOUT);
-    if ((rc = launch_transpose_in(d, d_cha, d->d_cha_t.p, B, G, d->Nq_Cha))) return rc;
-    return launch_transpose_in(d, d_msg0, d->d_msg0_t.p, B, G, d->Nq_Msg[0]);
+    if ((rc = launch_labels_in(d, d_cha, (size_t)d->nvar, false, d->d_cha_t.p, nullptr, nullptr, B, G, d->Nq_Cha - 1))) return rc;
+    return launch_labels_in(d, d_msg0, (size_t)d->nvar, false, d->d_msg0_t.p, nullptr, nullptr, B, G, d->Nq_Msg[0] - 1);
 }
 int labels_from_host(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0, int B) {
     const size_t n = (size_t)B * (size_t)d->nvar;
@@ -227,5 +227,20 @@ int rows_to_host(lutldpc_decoder *d, const uint8_t *rows, uint8_t *host_dst, int
     return copy_to_host(d, host_dst, d->d_out_bits.p, n);
 }
 int iters_to_host(lutldpc_decoder *d, int32_t *dst, int B) { return copy_to_host(d, dst, d->d_iters.p, sizeof(int32_t) * (size_t)B); }
+
+int check_out_window(const lutldpc_decoder *d, int first, int count) {
+    if (first < 0 || count < 1 || (int64_t)first + count > d->nvar) return fail(LUTLDPC_ERR_ARG, "output window outside [0, nvar)");
+    return LUTLDPC_OK;
+}
+int bits_to_caller(lutldpc_decoder *d, uint32_t *words, bool on_device, int B, int first, int count) {
+    const size_t n = (size_t)B * (size_t)((count + 31) / 32);
+    uint32_t *dst = words;
+    if (!on_device) { HIP_TRY(d->d_out_words.alloc(n)); dst = d->d_out_words.p; }
+    {
+        Timed t(d, LUTLDPC_K_LAYOUT);
+        if (int rc = launch_bits_out(d, dst, B, d->bpad(B) / d->tile(), first, count)) return rc;
+    }
+    return on_device ? LUTLDPC_OK : copy_to_host(d, words, dst, sizeof(uint32_t) * n);
+}
 
 #pragma GCC visibility pop

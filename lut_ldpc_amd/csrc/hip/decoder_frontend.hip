@@ -175,11 +175,10 @@ int lutldpc_decoder_encode_packed(lutldpc_decoder *d, const lutldpc_encode_io *i
     if (B <= 0) return fail(LUTLDPC_ERR_ARG, "B must be positive");
     if (!io || !info || !out_words) return fail(LUTLDPC_ERR_ARG, "NULL argument: io, info and out_words are required");
     if (reinterpret_cast<uintptr_t>(info) % 4 || reinterpret_cast<uintptr_t>(out_words) % 4) return fail(LUTLDPC_ERR_ARG, "info and out_words must be 4-byte aligned");
-    const int N = d->nvar, W32 = (d->gen_K + 31) / 32;              // (a handle without a generator: W32 = 0, and the state error below)
+    const int W32 = (d->gen_K + 31) / 32;             // (a handle without a generator: W32 = 0, and the state error below)
     if (io->in_stride < 0 || (io->in_stride != 0 && io->in_stride < W32)) return fail(LUTLDPC_ERR_ARG, "in_stride must be 0 or at least ceil(K/32)");
-    if (io->out_first < 0 || io->out_count < 1 || (int64_t)io->out_first + io->out_count > N) return fail(LUTLDPC_ERR_ARG, "output window outside [0, nvar)");
-    int rc = batch_entry(d, B);
-    if (rc) return rc;
+    int rc = check_out_window(d, io->out_first, io->out_count);
+    if (rc || (rc = batch_entry(d, B))) return rc;
     if (!d->gen_set) return fail(LUTLDPC_ERR_STATE, "encode_packed: no generator set (lutldpc_decoder_set_generator)");
     const bool dev = io->on_device != 0;
     const int K = d->gen_K, R = d->gen_R, Wout = (io->out_count + 31) / 32;

@@ -1,6 +1,6 @@
 // decoder_llr.hip -- lutldpc_decoder_decode_llr_packed: the batch decode for receivers, whose soft values are float32, float16 or
 // 8-bit fixed point (float64 for the toolkit's own callers) and sit in host memory or already on the device.  Values -> cells ->
-// both row sets in one pass (llr_cells.hpp, kernels_llr.hpp) -> decode_tiles -> packed bits (packed_bits_out_kernel); every decode
+// both row sets in one pass (llr_cells.hpp, kernels_llr.hpp) -> decode_tiles -> packed bits (bits_to_caller); every decode
 // path decode_tiles picks.  Home of the kernel of kernels_llr.hpp; lutldpc_llr_cell_table is the host half on its own.
 #include "decoder_state.hpp"
 #include "kernels_llr.hpp"
@@ -69,10 +69,10 @@ extern "C" int lutldpc_decoder_decode_llr_packed(lutldpc_decoder *d, const lutld
     LlrCells C;
     const std::string err = llr_cell_table(*io, d->Nq_Cha, d->Nq_Msg[0], C);
     if (!err.empty()) return fail(LUTLDPC_ERR_ARG, err);
-    if (out_words && (io->out_first < 0 || io->out_count < 1 || (int64_t)io->out_first + io->out_count > N)) return fail(LUTLDPC_ERR_ARG, "output window outside [0, nvar)");
-    if (!out_words && !out_iters && !out_cha && !out_msg0) return fail(LUTLDPC_ERR_ARG, "no output asked for");
-    int rc = batch_entry(d, B);
+    int rc = out_words ? check_out_window(d, io->out_first, io->out_count) : LUTLDPC_OK;
     if (rc) return rc;
+    if (!out_words && !out_iters && !out_cha && !out_msg0) return fail(LUTLDPC_ERR_ARG, "no output asked for");
+    if ((rc = batch_entry(d, B))) return rc;
     const bool dev = io->on_device != 0, decode = out_words || out_iters;
     const size_t stride = io->frame_stride ? (size_t)io->frame_stride : (size_t)N;
     const void *src = llr;
@@ -105,16 +105,7 @@ extern "C" int lutldpc_decoder_decode_llr_packed(lutldpc_decoder *d, const lutld
         if ((rc = launch_transpose_out(d, rows[i], labels[i], B, G))) return rc;
     }
     if (decode && (rc = decode_tiles(d, B))) return rc;
-    if (out_words) {
-        const int W = (io->out_count + 31) / 32;
-        uint32_t *dst = out_words;
-        if (!dev) { HIP_TRY(d->d_out_words.alloc((size_t)B * (size_t)W)); dst = d->d_out_words.p; }
-        {
-            Timed t(d, LUTLDPC_K_LAYOUT);
-            if ((rc = launch_bits_out(d, dst, B, G, io->out_first, io->out_count))) return rc;
-        }
-        if (!dev && (rc = copy_to_host(d, out_words, dst, sizeof(uint32_t) * (size_t)B * (size_t)W))) return rc;
-    }
+    if (out_words && (rc = bits_to_caller(d, out_words, dev, B, io->out_first, io->out_count))) return rc;
     if (out_iters) {
         if (dev) HIP_TRY(hipMemcpyAsync(out_iters, d->d_iters.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToDevice, d->stream));
         else if ((rc = iters_to_host(d, out_iters, B))) return rc;

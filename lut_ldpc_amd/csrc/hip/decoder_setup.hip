@@ -332,7 +332,7 @@ static int preload_code_objects(int device) {
     HIP_TRY(preload_compact_kernels());
     HIP_TRY(preload_stats_kernels());
     HIP_TRY(preload_events_kernels());
-    HIP_TRY(preload_packed_kernels());
+    HIP_TRY(preload_layout_kernels());
     HIP_TRY(preload_llr_kernels());
     HIP_TRY(hipDeviceSynchronize());
     done.push_back(device);

@@ -14,7 +14,8 @@
 //   decoder_frontend.hip   channel sampler, encoder, error counters and their C-ABI entries    (kernels_frontend.hpp, kernels_encode.hpp)
 //   decoder_stats.hip      message-label histograms per dump: edge groups, the counted decode, C-ABI   (kernels_stats.hpp)
 //   decoder_events.hip     failed frames captured on the device: weights, selection, sorted error / syndrome lists, C-ABI   (kernels_events.hpp)
-//   decoder_packed.hip     packed label input and bit-packed output of the host-side batch decode, C-ABI                    (kernels_packed.hpp)
+//   decoder_layout.hip     frame-major <-> rows: labels in (bytes / nibbles), labels out, decided bits out                  (kernels_layout.hpp)
+//   decoder_packed.hip     packed label input and bit-packed output of the host-side batch decode, C-ABI
 //   decoder_llr.hip        float64 / float32 / float16 / int8 soft values from host or device memory into both row sets, C-ABI (kernels_llr.hpp, llr_cells.hpp)
 #pragma once
 #include "../../../include/lut_ldpc_hip.h"
@@ -393,14 +394,17 @@ int tiles_from_host(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0,
 int copy_to_host(lutldpc_decoder *d, void *host_dst, const void *src, size_t bytes);
 int rows_to_host(lutldpc_decoder *d, const uint8_t *rows, uint8_t *host_dst, int B, int n_rows = 0);      // n_rows = 0: nvar
 int iters_to_host(lutldpc_decoder *d, int32_t *dst, int B);                                                // d_iters of the last decode_tiles
+// the packed entries: LUTLDPC_ERR_ARG unless decided / codeword bits first .. first + count - 1 lie inside [0, nvar)
+int check_out_window(const lutldpc_decoder *d, int first, int count);
+// decided bits first .. first + count - 1 of the last decode_tiles -> words[B][ceil(count/32)], one bit each: written in place
+// where `words` is device memory, else staged through d_out_words
+int bits_to_caller(lutldpc_decoder *d, uint32_t *words, bool on_device, int B, int first, int count);
 
 // ---- decoder_stream.hip (home of the kernels of kernels_generic.hpp)
 hipError_t preload_stream_kernels();
 // frames f0 .. f1-1 (both multiples of 256); default: the whole padded batch
 // `sel`: which of the two flag buffers the exit test reads and clears (always 0 outside the skewed pipeline)
 int launch_state(lutldpc_decoder *d, int B, int Bpad, int mode, int value, int f0 = 0, int f1 = -1, int sel = 0);
-int launch_transpose_in(lutldpc_decoder *d, const uint8_t *src, uint8_t *dst_rows, int B, int G, int limit);
-int launch_transpose_out(lutldpc_decoder *d, const uint8_t *src_rows, uint8_t *dst, int B, int G, int rows = 0);
 int launch_quantize_llr(lutldpc_decoder *d, size_t n, int n_qb_Cha, int n_qb_Msg, int mode);
 bool chain_active(const lutldpc_decoder *d, int set);
 // One degree class of one pass for the frame groups `groups`: complete ClassParams, the only code that assigns their fields.
@@ -470,8 +474,14 @@ int event_request_check(const lutldpc_event_request *req);                      
 // rows of the batch or null (all-zero codeword); stats: the front end's per-frame counters (device) or null.  Synchronises.
 int capture_events(lutldpc_decoder *d, int B, int K_info, const uint8_t *sent_rows, const int32_t *stats, lutldpc_event_request *req);
 
-// ---- decoder_packed.hip (home of the kernels of kernels_packed.hpp)
-hipError_t preload_packed_kernels();
+// ---- decoder_layout.hip (home of the kernels of kernels_layout.hpp)
+hipError_t preload_layout_kernels();
+// frame-major labels of B frames (device, `stride` bytes per frame, one label per byte or two with `nibbles`) -> rows_a =
+// min(label, lim_a) and, with lut_b (device, 256 entries), rows_b = lut_b[label]; rows_b = lut_b = null: one row set
+int launch_labels_in(lutldpc_decoder *d, const uint8_t *src, size_t stride, bool nibbles, uint8_t *rows_a, uint8_t *rows_b, const uint8_t *lut_b,
+                     int B, int G, int lim_a);
+// rows -> frame-major dst[B][rows] (device); rows = 0: nvar
+int launch_transpose_out(lutldpc_decoder *d, const uint8_t *src_rows, uint8_t *dst, int B, int G, int rows = 0);
 int launch_bits_out(lutldpc_decoder *d, uint32_t *dst, int B, int G, int first, int count);     // a window of d_hard -> dst[B][ceil(count/32)], device
 
 // ---- decoder_llr.hip (home of the kernel of kernels_llr.hpp)

@@ -52,26 +52,6 @@ static int launch_syndrome_of_labels(lutldpc_decoder *d, int G) {
     return LUTLDPC_OK;
 }
 
-// frame-major [B][N] <-> rows; the dword-vectorised kernels need N % 4 == 0 and a 4-byte aligned buffer
-int launch_transpose_in(lutldpc_decoder *d, const uint8_t *src, uint8_t *dst_rows, int B, int G, int limit) {
-    const int N = d->nvar;
-    if (N % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 3u) == 0)
-        PACK_DISPATCH(d, launch_k(transpose_in_vec_kernel<PK>, dim3((unsigned)((N + 127) / 128), (unsigned)G), dim3(256), 0, d->stream, src, dst_rows, B, N, limit));
-    else
-        PACK_DISPATCH(d, launch_k(transpose_in_kernel<PK>, dim3((unsigned)((N + 31) / 32), (unsigned)G), dim3(256), 0, d->stream, src, dst_rows, B, N, limit));
-    LAUNCH_CHECK();
-    return LUTLDPC_OK;
-}
-int launch_transpose_out(lutldpc_decoder *d, const uint8_t *src_rows, uint8_t *dst, int B, int G, int rows) {
-    const int N = rows > 0 ? rows : d->nvar;
-    if (N % 4 == 0 && (reinterpret_cast<uintptr_t>(dst) & 3u) == 0)
-        PACK_DISPATCH(d, launch_k(transpose_out_vec_kernel<PK>, dim3((unsigned)((N + 127) / 128), (unsigned)G), dim3(256), 0, d->stream, src_rows, dst, B, N));
-    else
-        PACK_DISPATCH(d, launch_k(transpose_out_kernel<PK>, dim3((unsigned)((N + 31) / 32), (unsigned)G), dim3(256), 0, d->stream, src_rows, dst, B, N));
-    LAUNCH_CHECK();
-    return LUTLDPC_OK;
-}
-
 // keep only the classes flagged in `keep` (the others were handled by specialised kernels)
 static PassParams filter_params(const PassParams &P, const std::vector<char> &keep) {
     PassParams Q = P;

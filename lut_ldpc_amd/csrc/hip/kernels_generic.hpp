@@ -1,9 +1,8 @@
-// kernels_generic.hpp -- generic (any tree, any degree) node-update kernels and the layout
-// kernels.  These are the correctness baseline every specialised kernel is tested against.
+// kernels_generic.hpp -- generic (any tree, any degree) node-update kernels and the row
+// initialisation.  These are the correctness baseline every specialised kernel is tested against.
 // All kernels are templated on PACK (1 = byte rows, 2 = nibble rows; kernels_common.hpp).
 #pragma once
 #include "kernels_common.hpp"
-#include "kernels_layout.hpp"
 #include "lut_program.hpp"
 
 namespace lutldpc {
@@ -229,153 +228,8 @@ __global__ __launch_bounds__(64) void cn_minsum_generic_kernel(
 }
 
 // ------------------------------------------------------------------------------------------
-// Layout kernels
+// Row initialisation (the frame-major <-> row kernels: kernels_layout.hpp)
 // ------------------------------------------------------------------------------------------
-// frame-major [B][N] -> rows [G][N][256 B]; labels are clamped to < limit, pad frames get 0.
-template <int PACK>
-__global__ __launch_bounds__(256) void transpose_in_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
-                                                           int B, int N, int limit)
-{
-    constexpr int F = kRowBytes * PACK;                     // frames per group
-    __shared__ uint8_t tile[F][32 + 4];
-    const int g = blockIdx.y, n0 = blockIdx.x * 32, t = threadIdx.x;
-    const int nn = t & 31, fq = t >> 5;
-    for (int f = fq; f < F; f += 8) {
-        const int fr = g * F + f, n = n0 + nn;
-        uint8_t v = 0;
-        if (fr < B && n < N) { v = src[(size_t)fr * N + n]; if (v >= limit) v = (uint8_t)(limit - 1); }
-        tile[f][nn] = v;
-    }
-    __syncthreads();
-    const int lane = t & 63;
-    for (int r = t >> 6; r < 32; r += 4) {
-        const int n = n0 + r;
-        if (n >= N) break;
-        uint32_t w[PACK];
-#pragma unroll
-        for (int h = 0; h < PACK; h++) {
-            const int f0 = lane * 4 * PACK + 4 * h;
-            w[h] = (uint32_t)tile[f0][r] | ((uint32_t)tile[f0 + 1][r] << 8) | ((uint32_t)tile[f0 + 2][r] << 16) | ((uint32_t)tile[f0 + 3][r] << 24);
-        }
-        *reinterpret_cast<uint32_t *>(dst + ((size_t)g * N + n) * kRowBytes + lane * 4) = pack_halves<PACK>(w);
-    }
-}
-
-// rows [G][N][256 B] -> frame-major [B][N]
-template <int PACK>
-__global__ __launch_bounds__(256) void transpose_out_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int B, int N)
-{
-    constexpr int F = kRowBytes * PACK;
-    __shared__ uint8_t tile[F][32 + 4];
-    const int g = blockIdx.y, n0 = blockIdx.x * 32, t = threadIdx.x;
-    const int lane = t & 63;
-    for (int r = t >> 6; r < 32; r += 4) {
-        const int n = n0 + r;
-        uint32_t x = 0;
-        if (n < N) x = *reinterpret_cast<const uint32_t *>(src + ((size_t)g * N + n) * kRowBytes + lane * 4);
-#pragma unroll
-        for (int h = 0; h < PACK; h++) {
-            const uint32_t w = unpack_half<PACK>(x, h);
-            const int f0 = lane * 4 * PACK + 4 * h;
-            tile[f0][r] = (uint8_t)w; tile[f0 + 1][r] = (uint8_t)(w >> 8);
-            tile[f0 + 2][r] = (uint8_t)(w >> 16); tile[f0 + 3][r] = (uint8_t)(w >> 24);
-        }
-    }
-    __syncthreads();
-    const int nn = t & 31, fq = t >> 5;
-    for (int f = fq; f < F; f += 8) {
-        const int fr = g * F + f, n = n0 + nn;
-        if (fr < B && n < N) dst[(size_t)fr * N + n] = tile[f][nn];
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// Vectorised transposes (N % 4 == 0, 4-byte aligned frame-major buffer): a block moves 128 nodes x one
-// frame group through LDS as DWORDS (4 nodes of one frame each).
-//   global side : 32 lanes x 4 B = 128 contiguous bytes per frame;
-//   LDS         : tile[f][c ^ key(f)], key(f) = (f / frames-per-lane) & 31: the XOR swizzle makes both the
-//                 frame-major side (32 lanes, one frame, all quads c) and the row side (lane L reads its own
-//                 frames 4*PACK*L + k of one quad c) hit 32 different banks;
-//   registers   : 4x4 byte transposes with v_perm_b32 turn "4 nodes of 4 frames" into "4 frames of one node",
-//                 the dword a lane owns in a row (PACK = 2: two of them merged as low / high nibbles).
-// (xcd_block, the XCD-aware block order, and transpose4x4: kernels_layout.hpp)
-template <int PACK>
-__global__ __launch_bounds__(256) void transpose_in_vec_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int B, int N, int limit)
-{
-    constexpr int F = kRowBytes * PACK, FPL = 4 * PACK;     // frames per group / per lane
-    __shared__ uint32_t tile[F * 32];
-    int bx, by;
-    xcd_block(bx, by);
-    const int g = by, n0 = bx * 128, t = threadIdx.x;
-    const int c = t & 31, fq = t >> 5;
-    const uint32_t lim = (uint32_t)(limit - 1);
-    for (int f0 = fq; f0 < F; f0 += 64) {                   // eight loads in flight per thread
-        uint32_t v[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const int fr = g * F + f0 + 8 * j, n = n0 + 4 * c;
-            v[j] = (fr < B && n < N) ? *reinterpret_cast<const uint32_t *>(src + (size_t)fr * N + n) : 0u;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const int f = f0 + 8 * j;
-            const uint32_t b0 = min(v[j] & 0xFFu, lim), b1 = min((v[j] >> 8) & 0xFFu, lim), b2 = min((v[j] >> 16) & 0xFFu, lim), b3 = min(v[j] >> 24, lim);
-            tile[f * 32 + (c ^ ((f / FPL) & 31))] = b0 | (b1 << 8) | (b2 << 16) | (b3 << 24);
-        }
-    }
-    __syncthreads();
-    const int lane = t & 63;
-    for (int q = t >> 6; q < 32; q += 4) {                  // node quad q: nodes n0 + 4q .. +3
-        if (n0 + 4 * q >= N) break;
-        uint32_t out[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int h = 0; h < PACK; h++) {
-            uint32_t d[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) d[k] = tile[(FPL * lane + 4 * h + k) * 32 + (q ^ (lane & 31))];
-            transpose4x4(d);
-#pragma unroll
-            for (int k = 0; k < 4; k++) out[k] |= d[k] << (4 * h);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            *reinterpret_cast<uint32_t *>(dst + ((size_t)g * N + n0 + 4 * q + k) * kRowBytes + lane * 4) = out[k];
-    }
-}
-
-template <int PACK>
-__global__ __launch_bounds__(256) void transpose_out_vec_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int B, int N)
-{
-    constexpr int F = kRowBytes * PACK, FPL = 4 * PACK;
-    __shared__ uint32_t tile[F * 32];
-    int bx, by;
-    xcd_block(bx, by);
-    const int g = by, n0 = bx * 128, t = threadIdx.x;
-    const int lane = t & 63;
-    for (int q = t >> 6; q < 32; q += 4) {
-        uint32_t x[4] = {0, 0, 0, 0};
-        if (n0 + 4 * q < N) {
-#pragma unroll
-            for (int k = 0; k < 4; k++) x[k] = *reinterpret_cast<const uint32_t *>(src + ((size_t)g * N + n0 + 4 * q + k) * kRowBytes + lane * 4);
-        }
-#pragma unroll
-        for (int h = 0; h < PACK; h++) {
-            uint32_t d[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) d[k] = unpack_half<PACK>(x[k], h);
-            transpose4x4(d);                                 // d[k] = 4 nodes of frame FPL*lane + 4h + k
-#pragma unroll
-            for (int k = 0; k < 4; k++) tile[(FPL * lane + 4 * h + k) * 32 + (q ^ (lane & 31))] = d[k];
-        }
-    }
-    __syncthreads();
-    const int c = t & 31, fq = t >> 5;
-    for (int f = fq; f < F; f += 8) {
-        const int fr = g * F + f, n = n0 + 4 * c;
-        if (fr < B && n < N) *reinterpret_cast<uint32_t *>(dst + (size_t)fr * N + n) = tile[f * 32 + (c ^ ((f / FPL) & 31))];
-    }
-}
-
 // msgs[g][e][:] = msg0[g][v(e)][:]  (src/LDPC_Code_LUT.cpp:284-289); one wave per VN (rows are copied whole)
 __global__ __launch_bounds__(256) void init_edges_kernel(const uint8_t *__restrict__ msg0_t, uint8_t *__restrict__ msgs,
                                                          const int32_t *__restrict__ vn_ptr, int N, int E)

@@ -1,11 +1,10 @@
 // kernels_llr.hpp -- the layout kernel of lutldpc_decoder_decode_llr_packed (decoder_llr.hip): frame-major soft values quantised
-// straight into both label row sets, read once.  Block shape, LDS scheme (dword tile, XOR swizzle, 4x4 byte transposes in
-// registers) and the store side are those of packed_labels_in_kernel (kernels_packed.hpp); what goes through the tile here is
-// the CELL of a value (llr_cells.hpp), one byte, from which two wave-held tables give both labels.
+// straight into both label row sets, read once.  Block order, tile and the whole store side (rows_from_tile) are the shared ones of
+// kernels_layout.hpp; only the load side is this kernel's own.  What goes through the tile here is the CELL of a value
+// (llr_cells.hpp), one byte, from which two wave-held tables give both labels.
 #pragma once
 #include "kernels_common.hpp"
 #include "kernels_layout.hpp"
-#include "kernels_packed.hpp"
 
 namespace lutldpc {
 
@@ -31,15 +30,15 @@ struct alignas(sizeof(T) * 4 > 16 ? 16 : sizeof(T) * 4) LlrQuad { T v[4]; };
 // stores the four cell bytes of a frame as one dword into the tile.  Nodes >= N and frames >= B stage 0.
 // VEC = 1: stride % 4 == 0 and src aligned to an LlrQuad, one quad per load (32 lanes x 4 elements contiguous per frame); VEC = 0:
 // element loads with a bound each (odd strides and bases).  The last quad of a frame whose N is no multiple of 4 is loaded by
-// elements in both.  After the transpose both row sets come from the wave-held tables, both masked with `live`: pad frames
-// get label 0 in both (lut_cha[0] is not 0 for int8).  Every row store is one 256-byte row per wave.
+// elements in both.  The two maps handed to rows_from_tile are the wave-held tables, both masked with `live`: pad frames get
+// label 0 in both (lut_cha[0] is not 0 for int8).
 template <int PACK, class T, int VEC>
 __global__ __launch_bounds__(256) void llr_labels_in_kernel(const T *__restrict__ src, size_t stride, uint8_t *__restrict__ dst_cha, uint8_t *__restrict__ dst_msg,
                                                             const LlrTables *__restrict__ tab, int n_thr, int B, int N)
 {
     using TC = typename LlrCmp<T>::type;
     constexpr bool kBytes = sizeof(T) == 1;
-    constexpr int F = kRowBytes * PACK, FPL = 4 * PACK;     // frames per group / per lane
+    constexpr int F = kRowBytes * PACK;                     // frames per group
     __shared__ uint32_t tile[F * 32];
     int bx, by;
     xcd_block(bx, by);
@@ -88,43 +87,17 @@ __global__ __launch_bounds__(256) void llr_labels_in_kernel(const T *__restrict_
         for (int j = 0; j < 8; j++) {
             const int f = f0 + 8 * j;
             // a value staged as 0 (node >= N, frame >= B) may count thresholds below 0: its rows are never stored, its frames masked
-            tile[f * 32 + (c ^ ((f / FPL) & 31))] = cell[j][0] | (cell[j][1] << 8) | (cell[j][2] << 16) | (cell[j][3] << 24);
+            tile[tile_at<PACK>(f, c)] = cell[j][0] | (cell[j][1] << 8) | (cell[j][2] << 16) | (cell[j][3] << 24);
         }
     }
     __syncthreads();
     const int lane = t & 63;
     const uint32_t cha_w = reinterpret_cast<const uint32_t *>(tab->lut_cha)[lane], msg_w = reinterpret_cast<const uint32_t *>(tab->lut_msg)[lane];
-    uint32_t live[PACK];                                    // 0xFF per frame of the batch, 0x00 per pad frame
-#pragma unroll
-    for (int h = 0; h < PACK; h++) {
-        live[h] = 0u;
-#pragma unroll
-        for (int k = 0; k < 4; k++) if (g * F + FPL * lane + 4 * h + k < B) live[h] |= 0xFFu << (8 * k);
-    }
-    for (int q = t >> 6; q < 32; q += 4) {                  // dword column q: nodes n0 + 4q .. + 3
-        const int nq = n0 + 4 * q;
-        if (nq >= N) break;
-        uint32_t a[4] = {0u, 0u, 0u, 0u}, b[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int h = 0; h < PACK; h++) {
-            uint32_t d[4];                                  // after the transpose: d[i] = node nq + i of frames FPL * lane + 4h .. + 3
-#pragma unroll
-            for (int k = 0; k < 4; k++) d[k] = tile[(FPL * lane + 4 * h + k) * 32 + (q ^ (lane & 31))];
-            transpose4x4(d);
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                a[i] |= (wave_lut4(cha_w, d[i]) & live[h]) << (4 * h);
-                b[i] |= (wave_lut4(msg_w, d[i]) & live[h]) << (4 * h);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            if (nq + i >= N) break;
-            const size_t off = ((size_t)g * N + nq + i) * kRowBytes + lane * 4;
-            *reinterpret_cast<uint32_t *>(dst_cha + off) = a[i];
-            *reinterpret_cast<uint32_t *>(dst_msg + off) = b[i];
-        }
-    }
+    uint32_t live[PACK];
+    live_frames<PACK>(live, g, lane, B);
+    rows_from_tile<PACK, 0, 1>(tile, g, n0, N, dst_cha, dst_msg,
+                               [&](uint32_t x, int h) { return wave_lut4(cha_w, x) & live[h]; },
+                               [&](uint32_t x, int h) { return wave_lut4(msg_w, x) & live[h]; });
 }
 
 }  // namespace lutldpc
