@@ -48,29 +48,31 @@ void make_describe(lutldpc_decoder *d) {
       << ",\"nodes_per_wave\":" << d->opt.nodes_per_wave << ",\"nodes_per_wave_cn\":" << d->opt.nodes_per_wave_cn << ",\"tail_front\":" << d->opt.tail_front
       << ",\"fused_prio\":" << d->opt.fused_prio << ",\"chk_full_labels\":" << d->opt.chk_full_labels
       << ",\"vn_classes\":[";
-    for (size_t i = 0; i < d->vclass.size(); i++) {
-        const TreeClassPlan *t = d->tree_class(TT_VAR, 0, (int)i);      // (null: set 0 decides, a code of one iteration)
-        const bool f = t && fast_covers(d, t->fast, d->vclass[i].deg);
+    // the kernels of a class over the iterations (pass_kernel decides per iteration: a schedule that mixes power-of-two and other
+    // message alphabets runs two of them), distinct names joined with '+' in the order fast, generated, interpreter
+    const int I = d->max_iters_created;
+    auto kernels_of = [&](int kind, size_t i, const char *const (&name)[3]) {
+        bool used[3] = {false, false, false};
+        if (kind == TT_VAR)         // variable pass ii writes the alphabet of iteration ii + 1 (a code of one iteration has none: set 0 decides)
+            for (int ii = 0; ii < std::max(I - 1, 1); ii++) used[pass_kernel(d, TT_VAR, d->iter_set[(size_t)ii], (int)i, d->Nq_Msg[(size_t)std::min(ii + 1, I - 1)] / 2)] = true;
+        else
+            for (int ii = 0; ii < I; ii++) used[pass_kernel(d, TT_CHK, d->iter_set[(size_t)ii], (int)i, d->Nq_Msg[(size_t)ii] / 2)] = true;
+        std::string s;
+        for (int k = 0; k < 3; k++) if (used[k]) s += (s.empty() ? "" : "+") + std::string(name[k]);
+        return s;
+    };
+    for (size_t i = 0; i < d->vclass.size(); i++)
         o << (i ? "," : "") << "{\"deg\":" << d->vclass[i].deg << ",\"nodes\":" << d->vclass[i].nodes.size() << ",\"nodes_per_wave\":" << d->npw_vn(d->vclass[i].deg) << ",\"kernel\":\""
-          << (f ? "vn_balanced_fast_kernel" : t && t->jit ? "lutldpc_jit_pass" : "tree_pass_kernel<VAR>") << "\"}";
-    }
+          << kernels_of(TT_VAR, i, {"vn_balanced_fast_kernel", "lutldpc_jit_pass", "tree_pass_kernel<VAR>"}) << "\"}";
     o << "],\"cn_classes\":[";
     for (size_t i = 0; i < d->cclass.size(); i++) {
-        // cn_minsum_shape decides per iteration: a schedule that mixes power-of-two and other message alphabets runs both kernels
-        int n_fast = 0;
-        for (int nq : d->Nq_Msg)
-            n_fast += d->opt.use_fast && d->min_lut && cn_minsum_shape(nq / 2, d->cclass[i].deg);
-        const char *minsum = n_fast == (int)d->Nq_Msg.size() ? "cn_minsum_fast_kernel"
-                           : n_fast == 0 ? "cn_minsum_generic_kernel" : "cn_minsum_fast_kernel+cn_minsum_generic_kernel";
         // degree-2 nodes updated inside the check pass of this class: the forward links of its chain table (build_fast_index)
         int chained = 0;
         if (d->opt.use_chain && d->cclass[i].chain_off >= 0)
             for (size_t j = 0; j < d->cclass[i].nodes.size(); j++) chained += d->fast_idx[(size_t)d->cclass[i].chain_off + 2 * j + 1] != 0;
-        const TreeClassPlan *t = d->tree_class(TT_CHK, 0, (int)i);
         o << (i ? "," : "") << "{\"deg\":" << d->cclass[i].deg << ",\"nodes\":" << d->cclass[i].nodes.size() << ",\"nodes_per_wave\":" << d->npw_cn_class(i)
           << ",\"chain_nodes\":" << chained << ",\"kernel\":\""
-          << (d->min_lut ? minsum
-                         : t && t->jit ? "lutldpc_jit_pass" : "tree_pass_kernel<CHK>") << "\"}";
+          << kernels_of(TT_CHK, i, {"cn_minsum_fast_kernel", "lutldpc_jit_pass", d->min_lut ? "cn_minsum_generic_kernel" : "tree_pass_kernel<CHK>"}) << "\"}";
     }
     o << "],\"resident\":" << (resident_active(d) ? 1 : 0) << ",\"skewed_pipeline\":" << ((d->opt.skew && d->skew_ok) ? 1 : 0) << ",\"fused_bucket\":" << d->fused_bucket_id << ",\"compaction\":" << (d->opt.use_compact < 0 ? 2 : d->opt.use_compact) << ",\"compaction_min_groups\":" << compaction_min_groups(d) << ",\"chain_nodes\":" << (d->opt.use_chain ? d->n_chain_nodes : 0) << ",\"placement\":" << d->place_info;
     if (d->gen_set) o << ",\"generator\":{\"K\":" << d->gen_K << ",\"R\":" << d->gen_R << "}";
@@ -246,8 +248,8 @@ int lutldpc_decoder_create(int nvar, int nchk, const int32_t *dv, const int32_t 
     }
     if ((uint64_t)d->E * kRowBytes >= (1ull << 32) || (uint64_t)nvar * kRowBytes >= (1ull << 32))
         return fail(LUTLDPC_ERR_UNSUPPORTED, "code too large: the rows of one frame group must stay below 4 GiB");
-    build_classes(d->dv, d->vclass, d->vn_list);
-    build_classes(d->dc, d->cclass, d->cn_list);
+    build_classes(d->dv, d->vclass);
+    build_classes(d->dc, d->cclass);
     d->Nq_Cha = Nq_Cha; d->Nq_Msg.assign(Nq_Msg, Nq_Msg + max_iters);
     d->max_iters_created = d->max_iters = max_iters; d->psc = 1; d->pisc = 0; d->min_lut = min_lut ? 1 : 0;
     d->iter_set.resize((size_t)max_iters);
@@ -375,7 +377,7 @@ int64_t lutldpc_decoder_device_bytes(lutldpc_decoder *d) {
     if (!d) return 0;
     return (int64_t)(d->d_msgs.bytes() + d->d_cha_t.bytes() + d->d_msg0_t.bytes() + d->d_hard.bytes() + d->d_state.bytes() + d->d_vfail.bytes() +
                      d->d_iters.bytes() + d->d_in_cha.bytes() + d->d_in_msg.bytes() + d->d_out_bits.bytes() + d->d_out_iters.bytes() + d->d_llr.bytes() + d->d_llr_in.bytes() +
-                     d->d_ops.bytes() + d->d_tables.bytes() + d->d_cn_idx.bytes() + d->d_cn_vn.bytes());
+                     d->d_ops.bytes() + d->d_tables.bytes() + d->d_cn_vn.bytes());
 }
 const char *lutldpc_decoder_describe(lutldpc_decoder *d) { return d ? d->describe.c_str() : ""; }
 

@@ -5,52 +5,11 @@
 #pragma GCC visibility push(hidden)
 
 // ----------------------------------------------------------------------------- set-up helpers
-void build_classes(const std::vector<int> &deg, std::vector<NodeClass> &cls, std::vector<int> &list) {
+void build_classes(const std::vector<int> &deg, std::vector<NodeClass> &cls) {
     std::map<int, std::vector<int>> by;
     for (size_t i = 0; i < deg.size(); i++) by[deg[i]].push_back((int)i);
-    cls.clear(); list.clear();
+    cls.clear();
     for (auto &kv : by) { NodeClass c; c.deg = kv.first; c.nodes = kv.second; cls.push_back(std::move(c)); }
-    for (auto &c : cls) list.insert(list.end(), c.nodes.begin(), c.nodes.end());
-}
-
-// Build the launch plan of one pass from the per-class programs of a tree set (their base forms: what the interpreter
-// kernels walk) -- `set` may be null for the min-sum pass.
-static int build_plan(lutldpc_decoder *d, const std::vector<NodeClass> &cls, const TreeSetPlan *set, PassPlan &plan) {
-    if ((int)cls.size() > kMaxSeg) return fail(LUTLDPC_ERR_UNSUPPORTED, "more than 32 distinct node degrees in one pass");
-    PassParams &P = plan.P;
-    std::memset(&P, 0, sizeof(P));
-    P.n_seg = (int)cls.size();
-    P.nodes_per_block = d->opt.nodes_per_block;
-    P.E = d->E; P.N = d->nvar;
-    int blk = 0, node_off = 0, max_slots = 0, max_tab = 0, max_out = 1;
-    for (size_t i = 0; i < cls.size(); i++) {
-        PassSeg &S = P.seg[i];
-        S.block_begin = blk;
-        S.n_nodes = (int)cls[i].nodes.size();
-        S.node_off = node_off;
-        S.deg = cls[i].deg;
-        if (set) {
-            const TreeClassPlan &c = set->cls[i];
-            const Program &pr = c.base.prog;
-            S.op_off = c.op_off; S.n_ops = (int)pr.ops.size();
-            S.tab_off = c.base.tab.off; S.tab_bytes = c.base.tab.bytes;
-            S.n_in = pr.n_in; S.n_out = pr.n_out; S.n_slots = pr.n_slots;
-            max_slots = std::max(max_slots, pr.n_slots);
-            max_tab = std::max(max_tab, c.base.tab.bytes);
-            max_out = std::max(max_out, pr.n_out);
-        }
-        blk += (S.n_nodes + P.nodes_per_block - 1) / P.nodes_per_block;
-        node_off += S.n_nodes;
-    }
-    P.blocks_per_group = blk;
-    P.slots_lds = max_slots;
-    plan.out_slots = max_out;
-    int slots_bytes = (max_slots + max_out) * kWave * 4;
-    if (slots_bytes > 60 * 1024) return fail(LUTLDPC_ERR_UNSUPPORTED, "node program needs more than 60 KiB of LDS slots");
-    plan.lds_tab = (slots_bytes + max_tab) <= 64 * 1024;
-    plan.lds_bytes = slots_bytes + (plan.lds_tab ? max_tab : 0);
-    plan.valid = true;
-    return LUTLDPC_OK;
 }
 
 static void build_fast_index(lutldpc_decoder *d) {
@@ -201,7 +160,7 @@ static void append_tables(lutldpc_decoder *d, ProgramForm &f, bool align16) {
 }
 
 // Compile the trees of one kind of tree set s into one form of every degree class, then the checks' full-label form of it.
-// Base forms: the trees as they are, with their look-ups (all_ops), the interpreter's launch plan and the balanced-tree plans.
+// Base forms: the trees as they are, with their look-ups (all_ops) and the balanced-tree plans.
 // Composed forms: after exact table composition (compose_tree), for the generated LDS-resident kernel.  Off by default
 // (LUTLDPC_COMPOSE=1), measured on MI355X (tools/resident_probe.py): a 4 KB table spreads its 1024 dwords over 32 banks 32 deep --
 // the three-input look-ups run into 3-4-way bank conflicts where a 256-byte table has at most two dwords per bank -- and the halved
@@ -222,6 +181,7 @@ static int add_forms(lutldpc_decoder *d, int kind, int s, bool composed) {
             return fail(LUTLDPC_ERR_UNSUPPORTED, (composed ? "composed tree, degree " : "degree ") + std::to_string(cls[i].deg) + ": " + e);
         append_tables(d, f, false);
         if (composed) { f.prog.node_tabs.clear(); continue; }      // (they point into the temporary tree)
+        if (interp_slot_bytes(f.prog) > 60 * 1024) return fail(LUTLDPC_ERR_UNSUPPORTED, "node program needs more than 60 KiB of LDS slots");     // (the interpreter's)
         c.op_off = (int)d->all_ops.size();
         d->all_ops.insert(d->all_ops.end(), f.prog.ops.begin(), f.prog.ops.end());
         if (kind != TT_CHK) {
@@ -230,10 +190,7 @@ static int add_forms(lutldpc_decoder *d, int kind, int s, bool composed) {
             c.fast = plan_fast_vn(t, kind, cls[i].deg, tab_of);
         }
     }
-    if (!composed) {
-        if (int rc = build_plan(d, cls, &S, S.pass)) return rc;
-        S.valid = true;
-    }
+    if (!composed) S.valid = true;
     for (size_t i = 0; i < cls.size() && kind == TT_CHK && d->opt.chk_full_labels; i++) {
         ProgramForm f;
         if (!chk_full_label_program((composed ? S.cls[i].composed : S.cls[i].base).prog, f.prog) || f.prog.tables.empty()) continue;
@@ -278,7 +235,6 @@ int compile_all(lutldpc_decoder *d) {
         if ((rc = add_forms(d, vkind, s, true))) return rc;
         if (!d->min_lut && (rc = add_forms(d, TT_CHK, s, true))) return rc;
     }
-    if (d->min_lut) { int rc = build_plan(d, d->cclass, nullptr, d->cn_minsum_plan); if (rc) return rc; }
     return LUTLDPC_OK;
 }
 
@@ -365,7 +321,6 @@ int upload_static(lutldpc_decoder *d) {
     HIP_TRY(hipStreamCreateWithFlags(&d->stream.s, hipStreamNonBlocking));
     HIP_TRY(d->d_vn_ptr.upload(d->vn_ptr));
     HIP_TRY(d->d_cn_ptr.upload(d->cn_ptr));
-    HIP_TRY(d->d_cn_idx.upload(d->cn_msg_idx));
     {   // syndrome kernel: node of every check-edge, bit 31 = last edge of its check, 8 entries of padding
         std::vector<int32_t> f((size_t)d->E + 8, 0);
         for (int c = 0; c < d->nchk; c++)
@@ -373,8 +328,6 @@ int upload_static(lutldpc_decoder *d) {
                 f[(size_t)k] = (int32_t)((uint32_t)d->cn_vn[(size_t)k] | (k + 1 == d->cn_ptr[(size_t)c + 1] ? 0x80000000u : 0u));
         HIP_TRY(d->d_cn_vn.upload(f));
     }
-    HIP_TRY(d->d_vn_list.upload(d->vn_list));
-    HIP_TRY(d->d_cn_list.upload(d->cn_list));
     HIP_TRY(d->d_fast_idx.upload(d->fast_idx));
     HIP_TRY(d->d_chain_internal.upload(d->chain_internal));
     HIP_TRY(d->d_edge_vn.upload(d->edge_vn));

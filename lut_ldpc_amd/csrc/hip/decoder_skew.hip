@@ -17,9 +17,13 @@ bool skew_eligible(const lutldpc_decoder *d) {
     for (auto &c : d->cclass) max_cn = std::max(max_cn, c.deg);
     for (auto &c : d->vclass) max_vn = std::max(max_vn, c.deg);
     if (fused_bucket(max_vn, max_cn) < 0) return false;
-    for (int nq : d->Nq_Msg) for (auto &c : d->cclass) if (!cn_minsum_shape(nq / 2, c.deg)) return false;
-    for (int s = 0; d->tree_set(TT_VAR, s); s++)              // (a decision-only set has no variable classes)
-        for (auto &c : d->tree_set(TT_VAR, s)->cls) if (!c.fast.ok) return false;       // (a balanced tree of a degree the bucket holds fits its table slots in LDS)
+    // every class on its compile-time kernel in every iteration (a balanced tree of a degree the bucket holds fits its table slots in LDS)
+    for (int ii = 0; ii < d->max_iters_created; ii++) {
+        const int set = d->iter_set[(size_t)ii];
+        for (size_t i = 0; i < d->cclass.size(); i++) if (pass_kernel(d, TT_CHK, set, (int)i, d->Nq_Msg[(size_t)ii] / 2) != KERNEL_FAST) return false;
+        if (ii + 1 == d->max_iters_created || !d->tree_set(TT_VAR, set)->valid) continue;      // (a decision-only set has no variable classes)
+        for (size_t i = 0; i < d->vclass.size(); i++) if (pass_kernel(d, TT_VAR, set, (int)i, d->Nq_Msg[(size_t)ii + 1] / 2) != KERNEL_FAST) return false;
+    }
     return true;
 }
 

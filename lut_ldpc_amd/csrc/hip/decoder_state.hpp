@@ -7,8 +7,9 @@
 //                          (NodeClass: where each sits), chain fusion, JIT registry, static uploads
 //   decoder_batch.hip      batch buffers, parameter arena, placement search; the entry layer of the batch entries: one guard
 //                          (batch_entry), labels in (tiles_from_host / _device), results out (rows_to_host, iters_to_host)
-//   decoder_stream.hip     streaming decode: class parameters (the one builder and validator of ClassParams), per-class launches,
-//                          decision pass, graph replay, message trace   (kernels_generic.hpp)
+//   decoder_stream.hip     streaming decode: the kernel of every class (pass_kernel), class parameters (the one builder and validator
+//                          of ClassParams), one launch per pass and class -- compile-time, generated or interpreter --, decision
+//                          pass, graph replay, message trace   (kernels_generic.hpp)
 //   decoder_skew.hip       skewed two-half pipeline through pass_fused_kernel, compaction                     (kernels_compact.hpp)
 //   decoder_resident.hip   LDS-resident decoder (jit_resident.hpp)
 //   decoder_frontend.hip   channel sampler, encoder, error counters and their C-ABI entries    (kernels_frontend.hpp, kernels_encode.hpp)
@@ -108,14 +109,6 @@ struct NodeClass {
     int red_off = -1, red_n = 0;
 };
 
-struct PassPlan {               // one launch: all degree classes of one pass of one tree set
-    PassParams P{};
-    int lds_bytes = 0;
-    int out_slots = 0;
-    bool lds_tab = true;
-    bool valid = false;
-};
-
 // One (tree kind, tree set, degree class): every compiled form of its tree (lut_program.hpp: ProgramForm) and the kernels planned
 // for it.  A new program form or kernel plan is one more field here.
 struct TreeClassPlan {
@@ -128,9 +121,8 @@ struct TreeClassPlan {
     FastClassPlan fast;             // variable / decision classes: balanced-tree plan of the compile-time kernel
     const JitKernel *jit = nullptr; // generated streaming kernel (jit.hpp, build_jit), null = none
 };
-struct TreeSetPlan {                // valid: the set has trees of this kind (cls is empty otherwise); pass: the interpreter's launch
+struct TreeSetPlan {                // valid: the set has trees of this kind (cls is empty otherwise)
     bool valid = false;
-    PassPlan pass;
     std::vector<TreeClassPlan> cls; // parallel to vclass / cclass
 };
 
@@ -168,7 +160,6 @@ struct lutldpc_decoder {
     int nvar = 0, nchk = 0, E = 0;
     std::vector<int> dv, dc, cn_msg_idx, vn_ptr, cn_ptr, cn_vn;
     std::vector<NodeClass> vclass, cclass;
-    std::vector<int> vn_list, cn_list;         // nodes sorted by class
     // ---- decoder parameters
     int Nq_Cha = 0, max_iters_created = 0, max_iters = 0, psc = 1, pisc = 0, min_lut = 1;
     std::vector<int> Nq_Msg, iter_set;         // iter_set = cumsum(reuse == 0) - 1
@@ -194,8 +185,7 @@ struct lutldpc_decoder {
     TreeClassPlan *tree_class(int kind, int set, int cls) { return const_cast<TreeClassPlan *>(const_cast<const lutldpc_decoder *>(this)->tree_class(kind, set, cls)); }
     std::vector<Op> all_ops;
     std::vector<uint8_t> all_tables;
-    PassPlan cn_minsum_plan;
-    // dense per-class index tables of the specialised kernels (no pointer chasing, scalar loads); NodeClass says where each sits
+    // dense per-class index tables of the pass kernels (no pointer chasing, scalar loads); NodeClass says where each sits
     std::vector<int32_t> fast_idx;
     int chain_vclass = -1, n_chain_nodes = 0;   // chain fusion (build_fast_index): the degree-2 class, nodes updated inside the check pass
     std::vector<uint8_t> chain_internal;    // 1 = variable node updated inside the check pass (build_fast_index)
@@ -207,7 +197,7 @@ struct lutldpc_decoder {
     // ---- device.  The stream comes first: members are destroyed in reverse order, every buffer below goes before it.
     int device = -1;
     StreamHolder stream;
-    DevBuf<int32_t> d_vn_ptr, d_cn_ptr, d_cn_idx, d_cn_vn, d_vn_list, d_cn_list, d_fast_idx;
+    DevBuf<int32_t> d_vn_ptr, d_cn_ptr, d_cn_vn, d_fast_idx;
     DevBuf<Op> d_ops;
     DevBuf<uint8_t> d_tables;
     DevBuf<uint8_t> d_chain_internal;
@@ -365,7 +355,7 @@ struct Timed {
 void make_describe(lutldpc_decoder *d);
 
 // ---- decoder_setup.hip
-void build_classes(const std::vector<int> &deg, std::vector<NodeClass> &cls, std::vector<int> &list);
+void build_classes(const std::vector<int> &deg, std::vector<NodeClass> &cls);
 int compile_all(lutldpc_decoder *d);
 int upload_static(lutldpc_decoder *d);
 // Process-wide registry of the run-time generated kernels, keyed by device + source text (decoder_setup.hip: jit_registry)
@@ -407,18 +397,25 @@ hipError_t preload_stream_kernels();
 int launch_state(lutldpc_decoder *d, int B, int Bpad, int mode, int value, int f0 = 0, int f1 = -1, int sel = 0);
 int launch_quantize_llr(lutldpc_decoder *d, size_t n, int n_qb_Cha, int n_qb_Msg, int mode);
 bool chain_active(const lutldpc_decoder *d, int set);
+// The kernel that runs degree class `cls` of a pass of `kind` (TT_VAR, TT_CHK, TT_DEC) with tree set `set` and sign threshold nz
+// (ClassParams::nz): the only place that chooses.  Launches, class parameters, describe() and skew_eligible ask here.
+enum PassKernel { KERNEL_FAST, KERNEL_GENERATED, KERNEL_INTERPRETER };      // compile-time (kernels_fast.hpp), jit.hpp, kernels_generic.hpp
+PassKernel pass_kernel(const lutldpc_decoder *d, int kind, int set, int cls, int nz);
 // One degree class of one pass for the frame groups `groups`: complete ClassParams, the only code that assigns their fields.
 // skew_ii: the iteration of a role of the skewed pipeline (its flag buffers, chain block, first pass), or kPerClassLaunch for
 // a launch of the streaming decode (flag buffer 0, no chain, inputs from the edge rows).
 struct HalfRange { int g0, G; };
 constexpr int kPerClassLaunch = -1;
 ClassParams cn_class_params(const lutldpc_decoder *d, size_t ci, HalfRange groups, int nz, int check, int skew_ii = kPerClassLaunch);
-ClassParams lut_cn_class_params(const lutldpc_decoder *d, int set, size_t ci, HalfRange groups, int nz, int check);      // LUT checks: a generated kernel
+ClassParams lut_cn_class_params(const lutldpc_decoder *d, int set, size_t ci, HalfRange groups, int nz, int check);      // LUT checks: generated kernel or interpreter
 ClassParams vn_class_params(const lutldpc_decoder *d, int kind, int set, size_t ci, HalfRange groups, int nz, int check, int write_hard, int skew_ii = kPerClassLaunch);
-inline bool fast_covers(const lutldpc_decoder *d, const FastClassPlan &f, int deg) { return d->opt.use_fast && f.ok && deg <= kFastMaxDeg; }   // the compile-time balanced-tree kernel takes the class
-// the kernel a ClassParams is meant for: its pass, compile-time (min-sum, balanced tables of <= 256 bytes) or generated (one
-// class blob), the degrees it has cases for and what the error message calls that limit
+inline bool fast_covers(const lutldpc_decoder *d, const FastClassPlan &f, int deg) { return d->opt.use_fast && f.ok && deg <= kFastMaxDeg; }   // the balanced-tree kernel has a case for the class (pass_kernel decides)
+// the kernel a ClassParams is meant for: its pass, compile-time (min-sum, balanced tables of <= 256 bytes) or one class blob
+// (`generated`: the generated kernels and the interpreter), the degrees it has cases for and what the error message calls that limit
 struct KernelCases { int tree_kind; bool generated; int max_vn_deg, max_cn_deg; const char *limit; };
+// LDS of an interpreter launch (tree_pass_kernel): value slots and staged outputs, one dword per lane each; the class's tables
+// follow where the sum stays within 64 KiB
+inline int interp_slot_bytes(const Program &p) { return (p.n_slots + p.n_out) * kWave * 4; }
 // a ClassParams against the decoder's allocations and the cases of its kernel; `where` opens the error message
 int validate_class(const lutldpc_decoder *d, const ClassParams &P, const std::string &where, const KernelCases &k);
 inline PassBufs pass_bufs(const lutldpc_decoder *d) {

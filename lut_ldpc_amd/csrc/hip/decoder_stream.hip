@@ -1,4 +1,4 @@
-// decoder_stream.hip -- the streaming decode: one launch per pass and degree class, exit tests, decision pass, message trace,
+// decoder_stream.hip -- the streaming decode: one launch per pass and degree class (launch_pass), exit tests, decision pass, message trace,
 // graph replay.  Replaces LDPC_Code_LUT::lut_decode and everything below it (src/LDPC_Code_LUT.cpp:259-469,
 // src/LUT_Tree.cpp:402-445,774-820) for a BATCH of frames: the frame loop of LDPC_BER_Sim::sim_snr_point
 // (src/LDPC_BER_Sim.cpp:260-291) becomes the innermost, coalesced memory dimension.  See kernels_common.hpp for the HBM layout.
@@ -52,25 +52,23 @@ static int launch_syndrome_of_labels(lutldpc_decoder *d, int G) {
     return LUTLDPC_OK;
 }
 
-// keep only the classes flagged in `keep` (the others were handled by specialised kernels)
-static PassParams filter_params(const PassParams &P, const std::vector<char> &keep) {
-    PassParams Q = P;
-    Q.n_seg = 0;
-    int blk = 0;
-    for (int i = 0; i < P.n_seg; i++) {
-        if (!keep[(size_t)i]) continue;
-        PassSeg S = P.seg[i];
-        S.block_begin = blk;
-        blk += (S.n_nodes + P.nodes_per_block - 1) / P.nodes_per_block;
-        Q.seg[Q.n_seg++] = S;
-    }
-    Q.blocks_per_group = blk;
-    return Q;
+// ----------------------------------------------------------------------------- the kernel of a class
+PassKernel pass_kernel(const lutldpc_decoder *d, int kind, int set, int cls, int nz) {
+    // min-sum checks: the compile-time kernel where it has the shape, else the any-degree, any-alphabet one
+    if (kind == TT_CHK && d->min_lut) return d->opt.use_fast && cn_minsum_shape(nz, d->cclass[(size_t)cls].deg) ? KERNEL_FAST : KERNEL_INTERPRETER;
+    const TreeClassPlan *t = d->tree_class(kind, set, cls);
+    // The compile-time and generated variable kernels read the sign of an outgoing label as bit sbit = log2(nz) (exit test and
+    // decided bits); that holds only where nz is a power of two.  A variable pass that writes any other alphabet (Nq_Msg = 12:
+    // nz = 6) runs in the interpreter, which compares the label with nz.
+    if (!t || (kind == TT_VAR && !is_pow2(nz))) return KERNEL_INTERPRETER;
+    if (kind != TT_CHK && fast_covers(d, t->fast, d->vclass[(size_t)cls].deg)) return KERNEL_FAST;
+    return t->jit ? KERNEL_GENERATED : KERNEL_INTERPRETER;      // (build_jit: a kernel for every class without a compile-time one)
 }
 
 // ----------------------------------------------------------------------------- class parameters
 // The only code that fills a ClassParams.  skew_ii = kPerClassLaunch: a launch of the streaming decode (flag buffer 0, no chain,
-// inputs from the edge rows); otherwise: a role of the skewed pipeline in that iteration (decoder_skew.hip).
+// inputs from the edge rows) through the kernel pass_kernel names -- an interpreter block takes opt.nodes_per_block nodes, and the
+// tables are those of that kernel; otherwise: a role of the skewed pipeline in that iteration (decoder_skew.hip: compile-time kernels).
 static ClassParams class_params(const lutldpc_decoder *d, int kind, const NodeClass &c, int n_nodes, int idx_off, int npw, HalfRange g, int nz, int check) {
     ClassParams P{};
     P.kind = kind; P.deg = c.deg; P.g0 = g.g0; P.G = g.G;
@@ -80,7 +78,8 @@ static ClassParams class_params(const lutldpc_decoder *d, int kind, const NodeCl
 }
 ClassParams cn_class_params(const lutldpc_decoder *d, size_t ci, HalfRange groups, int nz, int check, int skew_ii) {
     const NodeClass &c = d->cclass[ci];
-    ClassParams P = class_params(d, 0, c, (int)c.nodes.size(), c.idx_off, skew_ii == kPerClassLaunch ? d->npw_cn(c.deg) : d->npw_cn_class(ci), groups, nz, check);
+    const int npw = skew_ii != kPerClassLaunch ? d->npw_cn_class(ci) : pass_kernel(d, TT_CHK, 0, (int)ci, nz) == KERNEL_INTERPRETER ? d->opt.nodes_per_block : d->npw_cn(c.deg);
+    ClassParams P = class_params(d, 0, c, (int)c.nodes.size(), c.idx_off, npw, groups, nz, check);
     if (skew_ii == kPerClassLaunch) return P;
     const int ii = skew_ii, buf_w = kVfailSlots * d->Bcap / 4;        // words per flag buffer
     P.vfail_off_w = (ii & 1) * buf_w;                                 // parity flags: this iteration's exit test
@@ -104,8 +103,11 @@ ClassParams cn_class_params(const lutldpc_decoder *d, size_t ci, HalfRange group
     return P;
 }
 ClassParams lut_cn_class_params(const lutldpc_decoder *d, int set, size_t ci, HalfRange groups, int nz, int check) {
-    ClassParams P = cn_class_params(d, ci, groups, nz, check);
-    const TabRef tab = d->chk_form(set, (int)ci, false)->tab;        // the class blob the kernel was generated for
+    const NodeClass &c = d->cclass[ci];
+    const bool interp = pass_kernel(d, TT_CHK, set, (int)ci, nz) == KERNEL_INTERPRETER;
+    ClassParams P = class_params(d, 0, c, (int)c.nodes.size(), c.idx_off, interp ? d->opt.nodes_per_block : d->npw_cn(c.deg), groups, nz, check);
+    // the class blob: of the form the kernel was generated for, or the tree as the reference walks it
+    const TabRef tab = interp ? d->tree_class(TT_CHK, set, (int)ci)->base.tab : d->chk_form(set, (int)ci, false)->tab;
     P.tab_off[0] = tab.off; P.tab_len[0] = tab.bytes;
     return P;
 }
@@ -113,15 +115,16 @@ ClassParams vn_class_params(const lutldpc_decoder *d, int kind, int set, size_t 
     const NodeClass &c = d->vclass[ci];
     int n_nodes = (int)c.nodes.size(), idx_off = c.idx_off;
     if (skew_ii != kPerClassLaunch && chain_active(d, set) && (int)ci == d->chain_vclass) { n_nodes = c.red_n; idx_off = c.red_off; }   // the others are updated by the check pass
-    ClassParams P = class_params(d, 1, c, n_nodes, idx_off, d->npw_vn(c.deg), groups, nz, check);
+    const PassKernel k = pass_kernel(d, kind, set, (int)ci, nz);
+    ClassParams P = class_params(d, 1, c, n_nodes, idx_off, k == KERNEL_INTERPRETER ? d->opt.nodes_per_block : d->npw_vn(c.deg), groups, nz, check);
     P.write_hard = write_hard;
     if (skew_ii != kPerClassLaunch) P.vfail_off_w = ((skew_ii + 1) & 1) * (kVfailSlots * d->Bcap / 4);      // unanimity flags: the exit test after the NEXT check pass
     const TreeClassPlan &t = *d->tree_class(kind, set, (int)ci);
     const FastClassPlan &f = t.fast;
-    if (fast_covers(d, f, c.deg)) {                                   // balanced tree: its tables in canonical order
+    if (k == KERNEL_FAST) {                                           // balanced tree: its tables in canonical order
         P.shift_msg = f.shift_msg;
         for (int t = 0; t < f.n_tables; t++) { P.tab_off[t] = f.tab_off[t]; P.tab_len[t] = f.tab_len[t]; P.tab_shift[t] = f.tab_shift[t]; }
-    } else {                                                          // generated kernel: the class blob
+    } else {                                                          // generated kernel, interpreter: the class blob
         P.tab_off[0] = t.base.tab.off; P.tab_len[0] = t.base.tab.bytes;
     }
     return P;
@@ -163,92 +166,54 @@ int validate_class(const lutldpc_decoder *d, const ClassParams &R, const std::st
     return LUTLDPC_OK;
 }
 // LUTLDPC_VALIDATE=1: the parameters of a per-class launch against the allocations, before it is issued
-static int check_class_launch(const lutldpc_decoder *d, const ClassParams &P, int i, int tree_kind, bool generated) {
+static int check_class_launch(const lutldpc_decoder *d, const ClassParams &P, size_t i, int tree_kind, PassKernel kernel) {
     if (!d->opt.validate) return LUTLDPC_OK;
-    const KernelCases k = generated ? KernelCases{tree_kind, true, INT32_MAX, INT32_MAX, "the generated kernel"} : KernelCases{tree_kind, false, kFastMaxDeg, kFastMaxCnDeg, "the compile-time kernels"};
+    const KernelCases k = kernel == KERNEL_FAST        ? KernelCases{tree_kind, false, kFastMaxDeg, kFastMaxCnDeg, "the compile-time kernels"}
+                        : kernel == KERNEL_GENERATED   ? KernelCases{tree_kind, true, INT32_MAX, INT32_MAX, "the generated kernel"}
+                                                       : KernelCases{tree_kind, true, 255, 255, "the interpreter"};
     return validate_class(d, P, "class launch check failed, class " + std::to_string(i), k);
 }
 
+// One pass of the streaming decode: every degree class through the kernel pass_kernel names, one launch each (the classes of a
+// pass own disjoint rows).  KIND = TT_CHK covers both check updates, min-sum and CHKTREE.
 template <int KIND>
-static int launch_tree_pass(lutldpc_decoder *d, int set, int G, int nz, int check, int write_hard, int kind_id) {
-    const TreeSetPlan *S = d->tree_set(KIND, set);
-    if (!S || !S->valid) return fail(LUTLDPC_ERR_STATE, "pass plan missing for this tree set");
-    const PassPlan &plan = S->pass;
+static int launch_pass(lutldpc_decoder *d, int set, int G, int nz, int check, int write_hard, int kind_id) {
+    const bool minsum = KIND == TT_CHK && d->min_lut;
+    const TreeSetPlan *S = minsum ? nullptr : d->tree_set(KIND, set);
+    if (!minsum && (!S || !S->valid)) return fail(LUTLDPC_ERR_STATE, "no trees of this pass in this tree set");
     Timed t(d, kind_id);
-    PassParams P = plan.P;
-    P.G = G; P.nz = nz; P.check = check; P.write_hard = write_hard; P.vfail_stride_w = d->Bcap / 4;
-    std::vector<char> keep((size_t)P.n_seg, 1);
-    bool any = false;
     const PassBufs bufs = pass_bufs(d);
-    auto class_of = [&](int i) { return KIND == TT_CHK ? lut_cn_class_params(d, set, (size_t)i, {0, G}, nz, check) : vn_class_params(d, KIND, set, (size_t)i, {0, G}, nz, check, write_hard); };
-    // The compile-time and generated variable kernels read the sign of an outgoing label as bit sbit = log2(nz) (exit test and
-    // decided bits); that holds only where nz is a power of two.  A variable pass that writes any other alphabet (Nq_Msg = 12:
-    // nz = 6) runs in the interpreter below, which compares the label with nz.
-    const bool sign_bit = KIND != TT_VAR || is_pow2(nz);
-    // specialised kernels take the classes they know, one launch per degree class
-    if constexpr (KIND != TT_CHK)
-        for (int i = 0; i < P.n_seg && sign_bit; i++) {
-            if (!fast_covers(d, S->cls[(size_t)i].fast, P.seg[i].deg)) continue;
-            bool ok = false;
-            const ClassParams FP = class_of(i);
-            if (int rc = check_class_launch(d, FP, i, KIND, false)) return rc;
-            DEV_PARAM(dFP, d, FP);
-            PACK_DISPATCH(d, ok = launch_vn_fast<KIND, PK>(d->stream, FP, dFP, bufs));
-            if (ok) keep[(size_t)i] = 0;
-        }
-    // run-time generated kernels (jit.hpp) for the classes without a compile-time one
-    if (sign_bit)
-        for (int i = 0; i < P.n_seg; i++) {
-            const JitKernel *k = S->cls[(size_t)i].jit;
-            if (!keep[(size_t)i] || !k) continue;
-            const ClassParams F = class_of(i);
-            if (int rc = check_class_launch(d, F, i, KIND, true)) return rc;
-            DEV_PARAM(dF, d, F);
-            void *args[] = {&dF, (void *)&bufs.msgs, (void *)&bufs.cha, (void *)&bufs.hard, (void *)&bufs.state_w, (void *)&bufs.vfail_w, (void *)&bufs.tables, (void *)&bufs.fast_idx};
-            HIP_TRY(hipModuleLaunchKernel(k->fn, class_blocks(F), 1, 1, 256, 1, 1, 0, d->stream, args, nullptr));
-            keep[(size_t)i] = 0;
-        }
-    for (char k : keep) any = any || k;
-    if (any) {
-        P = filter_params(P, keep);
+    for (size_t i = 0; i < (KIND == TT_CHK ? d->cclass : d->vclass).size(); i++) {
+        const PassKernel k = pass_kernel(d, KIND, set, (int)i, nz);
+        const ClassParams P = KIND != TT_CHK ? vn_class_params(d, KIND, set, i, {0, G}, nz, check, write_hard)
+                              : minsum       ? cn_class_params(d, i, {0, G}, nz, check)
+                                             : lut_cn_class_params(d, set, i, {0, G}, nz, check);
+        if (int rc = check_class_launch(d, P, i, KIND, k)) return rc;
         DEV_PARAM(dP, d, P);
-        dim3 grid((unsigned)(P.blocks_per_group * G)), block(64);
-        const int32_t *list = KIND == TT_CHK ? d->d_cn_list.p : d->d_vn_list.p;
-        const int32_t *ptr = KIND == TT_CHK ? d->d_cn_ptr.p : d->d_vn_ptr.p;
-        if (plan.lds_tab)
-            PACK_DISPATCH(d, launch_k(tree_pass_kernel<KIND, true, PK>, grid, block, (size_t)plan.lds_bytes, d->stream, dP, bufs.msgs, bufs.cha, bufs.hard, bufs.state_w,
-                               bufs.vfail_w, d->d_ops.p, bufs.tables, list, ptr, d->d_cn_idx.p, plan.out_slots));
-        else
-            PACK_DISPATCH(d, launch_k(tree_pass_kernel<KIND, false, PK>, grid, block, (size_t)plan.lds_bytes, d->stream, dP, bufs.msgs, bufs.cha, bufs.hard, bufs.state_w,
-                               bufs.vfail_w, d->d_ops.p, bufs.tables, list, ptr, d->d_cn_idx.p, plan.out_slots));
-    }
-    LAUNCH_CHECK();
-    return LUTLDPC_OK;
-}
-
-static int launch_cn_minsum(lutldpc_decoder *d, int G, int nz, int check) {
-    Timed t(d, LUTLDPC_K_CN_PASS);
-    PassParams P = d->cn_minsum_plan.P;
-    P.G = G; P.nz = nz; P.check = check; P.vfail_stride_w = d->Bcap / 4;
-    std::vector<char> keep((size_t)P.n_seg, 1);
-    bool any = false;
-    const PassBufs bufs = pass_bufs(d);
-    if (d->opt.use_fast)
-        for (int i = 0; i < P.n_seg; i++) {
-            if (!cn_minsum_shape(nz, P.seg[i].deg)) continue;
+        if (k == KERNEL_FAST) {
             bool ok = false;
-            const ClassParams FP = cn_class_params(d, (size_t)i, {0, G}, nz, check);
-            if (int rc = check_class_launch(d, FP, i, TT_CHK, false)) return rc;
-            DEV_PARAM(dFP, d, FP);
-            PACK_DISPATCH(d, ok = launch_cn_fast<PK>(d->stream, FP, dFP, bufs));
-            if (ok) keep[(size_t)i] = 0;
+            if constexpr (KIND == TT_CHK) PACK_DISPATCH(d, ok = launch_cn_fast<PK>(d->stream, P, dP, bufs));
+            else PACK_DISPATCH(d, ok = launch_vn_fast<KIND, PK>(d->stream, P, dP, bufs));
+            if (!ok) return fail(LUTLDPC_ERR_STATE, "no compile-time kernel for degree " + std::to_string(P.deg));
+        } else if (k == KERNEL_GENERATED) {
+            void *args[] = {&dP, (void *)&bufs.msgs, (void *)&bufs.cha, (void *)&bufs.hard, (void *)&bufs.state_w, (void *)&bufs.vfail_w, (void *)&bufs.tables, (void *)&bufs.fast_idx};
+            HIP_TRY(hipModuleLaunchKernel(S->cls[i].jit->fn, class_blocks(P), 1, 1, 256, 1, 1, 0, d->stream, args, nullptr));
+        } else {                                                      // a block is one wave
+            const dim3 grid((unsigned)(P.waves_per_group * P.G)), block(64);
+            if (minsum) {
+                PACK_DISPATCH(d, launch_k(cn_minsum_generic_kernel<PK>, grid, block, 0, d->stream, dP, bufs.msgs, bufs.state_w, bufs.vfail_w, bufs.fast_idx));
+                continue;
+            }
+            const Program &pr = S->cls[i].base.prog;
+            const int slot_bytes = interp_slot_bytes(pr);
+            const bool lds_tab = slot_bytes + P.tab_len[0] <= 64 * 1024;
+            const size_t lds = (size_t)(slot_bytes + (lds_tab ? P.tab_len[0] : 0));
+            const Op *prog = d->d_ops.p + S->cls[i].op_off;
+#define TREE_PASS(LDS_TAB) PACK_DISPATCH(d, launch_k(tree_pass_kernel<KIND, LDS_TAB, PK>, grid, block, lds, d->stream, dP, bufs.msgs, bufs.cha, bufs.hard, bufs.state_w, bufs.vfail_w, \
+                                                  prog, bufs.tables, bufs.fast_idx, (int)pr.ops.size(), pr.n_slots, pr.n_out))
+            if (lds_tab) TREE_PASS(true); else TREE_PASS(false);
+#undef TREE_PASS
         }
-    for (char k : keep) any = any || k;
-    if (any) {
-        P = filter_params(P, keep);
-        DEV_PARAM(dP, d, P);
-        PACK_DISPATCH(d, launch_k(cn_minsum_generic_kernel<PK>, dim3((unsigned)(P.blocks_per_group * G)), dim3(64), 0, d->stream, dP, bufs.msgs, bufs.state_w, bufs.vfail_w,
-                           d->d_cn_list.p, d->d_cn_ptr.p, d->d_cn_idx.p));
     }
     LAUNCH_CHECK();
     return LUTLDPC_OK;
@@ -374,15 +339,12 @@ static int decode_tiles_launch(lutldpc_decoder *d, int B) {
         const int set = d->iter_set[(size_t)ii];
         const int nz_in = d->Nq_Msg[(size_t)ii] / 2;
         const int chk_check = (d->psc && ii > 0) ? 1 : 0;    // finishes the test started by VN pass ii-1
-        if (d->min_lut) rc = launch_cn_minsum(d, G, nz_in, chk_check);
-        else rc = launch_tree_pass<TT_CHK>(d, set, G, nz_in, chk_check, 0, LUTLDPC_K_CN_PASS);
-        if (rc) return rc;
+        if ((rc = launch_pass<TT_CHK>(d, set, G, nz_in, chk_check, 0, LUTLDPC_K_CN_PASS))) return rc;
         if (chk_check && (rc = launch_state(d, B, Bpad, 2, ii))) return rc;   // :327-329 returns (ii-1)+1
         if (d->trace.level > 2 && (rc = trace_dump(d))) return rc;             // :311-317
         if (ii != I - 1) {
             const int nz_out = d->Nq_Msg[(size_t)(ii + 1)] / 2;
-            rc = launch_tree_pass<TT_VAR>(d, set, G, nz_out, d->psc ? 1 : 0,
-                                          (d->psc && !late_hard_active(d, false, nullptr)) ? 1 : 0, LUTLDPC_K_VN_PASS);
+            rc = launch_pass<TT_VAR>(d, set, G, nz_out, d->psc ? 1 : 0, (d->psc && !late_hard_active(d, false, nullptr)) ? 1 : 0, LUTLDPC_K_VN_PASS);
             if (rc) return rc;
         }
         if (tracing && (rc = trace_dump(d))) return rc;                         // :331-337 (printed after the last iteration too)
@@ -403,7 +365,7 @@ static int decode_tiles_launch(lutldpc_decoder *d, int B) {
         }
     }
     // :340-349
-    if ((rc = launch_tree_pass<TT_DEC>(d, last_set, G, 0, 0, 0, LUTLDPC_K_DECISION))) return rc;
+    if ((rc = launch_pass<TT_DEC>(d, last_set, G, 0, 0, 0, LUTLDPC_K_DECISION))) return rc;
     const int fsel = skewed ? (I & 1) : 0;            // the flag buffer no pass of the skewed pipeline has written since its last test
     if ((rc = launch_syndrome(d, G, fsel))) return rc;
     if ((rc = launch_state(d, B, Bpad, 3, I, 0, -1, fsel))) return rc;

@@ -17,7 +17,8 @@
 // indices are wave-uniform (scalar registers, scalar loads).
 // Per-frame state lives in byte arrays indexed by frame; a lane's frames are PACK dwords of them.
 // Also here, because hiprtc compiles this header too: ClassParams, the description of one degree class of one pass that
-// every specialised kernel -- compile-time (kernels_fast.hpp) or generated (jit.hpp) -- reads from device memory.
+// every pass kernel -- compile-time (kernels_fast.hpp), generated (jit.hpp) or interpreter (kernels_generic.hpp) -- reads from
+// device memory.
 #pragma once
 #ifndef __HIPCC_RTC__      // hiprtc (jit.hpp compiles this header at run time) has the HIP runtime and the fixed-width types built in
 #include <hip/hip_runtime.h>
@@ -37,39 +38,10 @@ namespace lutldpc {
 constexpr int kRowBytes = 256;       // bytes per row (= 64 lanes x one dword)
 constexpr int kTileFrames = kRowBytes;   // frames per group when PACK = 1 (kept for the host code)
 constexpr int kWave = 64;
-constexpr int kMaxSeg = 32;          // degree classes handled by one pass launch
 
 // frame states
 constexpr uint32_t ST_ACTIVE = 0, ST_DONE_PSC = 1, ST_DONE_PISC = 2, ST_PAD = 3;
 constexpr uint32_t ST_DONE_SAVED = 4;   // left through the exit test, decided bits already recovered into the hard rows (compaction)
-
-struct PassSeg {
-    int32_t block_begin;   // first block (within one frame group) of this degree class
-    int32_t n_nodes;       // nodes in the class
-    int32_t node_off;      // offset of the class in the node list
-    int32_t deg;           // node degree
-    int32_t op_off;        // first op of the class program (generic kernels)
-    int32_t n_ops;
-    int32_t tab_off;       // byte offset of the class tables in the table blob
-    int32_t tab_bytes;
-    int32_t n_in, n_out, n_slots;
-    int32_t fast;          // specialised kernel id (0 = generic)
-};
-
-struct PassParams {
-    int32_t n_seg;
-    int32_t blocks_per_group;
-    int32_t nodes_per_block;
-    int32_t G;
-    int32_t E;             // edges  (rows of msgs per group)
-    int32_t N;             // variable nodes (rows of cha/hard per group)
-    int32_t nz;            // sign threshold of the messages this pass WRITES (VN) / READS (CN)
-    int32_t check;         // 1: accumulate the early-termination test into vfail
-    int32_t write_hard;    // VN pass: store the sign of the new messages as hard decisions
-    int32_t slots_lds;     // dwords per lane reserved for program slots
-    int32_t vfail_stride_w;   // words between two copies of the early-termination flags (see flag_frames)
-    PassSeg seg[kMaxSeg];
-};
 
 // ---- packing ------------------------------------------------------------------------------------
 // half h of a row dword as four frames, one per byte
@@ -210,9 +182,9 @@ struct ClassParams {
     int32_t n_nodes, nodes_per_wave, waves_per_group;
     int32_t idx_off;       // offset of the class in the dense index blob (decoder_setup.hip: build_fast_index)
     int32_t E, N;
-    int32_t nz;            // sign threshold (see PassParams)
+    int32_t nz;            // sign threshold of the messages this pass WRITES (VN) / READS (CN)
     int32_t shift_msg;     // log2 of the message alphabet feeding the tables (label = a | b << shift)
-    int32_t check, write_hard;
+    int32_t check, write_hard;          // 1: accumulate the early-termination test into vfail; VN pass: store the sign of the new messages as hard decisions
     int32_t vfail_stride_w;             // words between two copies of the early-termination flags (see flag_frames)
     int32_t vfail_off_w;                // word offset of the flag buffer this pass reports to (skewed pipeline: two buffers)
     int32_t first, nidx_off;            // check pass of iteration 0 in the skewed pipeline: inputs from the initial-message rows, through the node table at nidx_off
@@ -251,13 +223,5 @@ inline void launch_k(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t shm
     hipLaunchKernelGGL(kernel, grid, block, shmem, stream, static_cast<KArgs>(args)...);
 }
 #endif
-
-// locate the degree class of a block: linear scan over <= kMaxSeg scalar entries
-__device__ __forceinline__ int find_seg(const PassParams &P, int b) {
-    int s = 0;
-#pragma unroll 1
-    for (int i = 1; i < P.n_seg; i++) if (b >= P.seg[i].block_begin) s = i;
-    return s;
-}
 
 }  // namespace lutldpc

@@ -10,79 +10,82 @@ namespace lutldpc {
 // ------------------------------------------------------------------------------------------
 // Node-program interpreter.  KIND: TT_VAR (variable-node pass, src/LDPC_Code_LUT.cpp:404-414),
 // TT_CHK (CHKTREE check pass, :416-426), TT_DEC (decision pass, :428-434,340-344).
-// One wave per block; the program's value slots live in LDS as [slot][lane] dwords (four
-// frames per dword), so a slot access is a conflict-free ds_read/write_b32.  With nibble rows the
-// program runs once per half and the first half's outputs wait in LDS.  Tables of the class are
-// staged into LDS when they fit (LDS_TAB), else read through L1/L2.
-// LDS: [slots_lds][64] value slots | [n_out_max][64] staged outputs (PACK = 2) | tables
+// One degree class per launch, described by a ClassParams like every other pass kernel; a block is one wave and owns
+// P.nodes_per_wave nodes of frame group P.g0 + wave / P.waves_per_group (the arithmetic of vn_balanced_body).  What only the
+// interpreter needs comes as plain arguments: the class's look-ups `prog` (n_ops of them) and the LDS it was given room for.
+// The program's value slots live in LDS as [slot][lane] dwords (four frames per dword), so a slot access is a conflict-free
+// ds_read/write_b32.  With nibble rows the program runs once per half and the first half's outputs wait in LDS.  The class's
+// table blob (P.tab_off[0], P.tab_len[0]) is staged into LDS when it fits (LDS_TAB), else read through L1/L2.
+// LDS: [n_slots][64] value slots | [n_out][64] staged outputs | tables
 // ------------------------------------------------------------------------------------------
 template <int KIND, bool LDS_TAB, int PACK>
 __global__ __launch_bounds__(64) void tree_pass_kernel(
-    const PassParams *__restrict__ Pp, uint8_t *__restrict__ msgs, const uint8_t *__restrict__ cha, uint8_t *__restrict__ hard,
-    const uint32_t *__restrict__ state_w, uint32_t *__restrict__ vfail_w, const Op *__restrict__ ops,
-    const uint8_t *__restrict__ tables, const int32_t *__restrict__ node_list,
-    const int32_t *__restrict__ node_ptr,   // VAR/DEC: first edge of each VN ; CHK: offset of each CN in cn_idx
-    const int32_t *__restrict__ cn_idx, int out_slots)
+    const ClassParams *__restrict__ Pp, uint8_t *__restrict__ msgs, const uint8_t *__restrict__ cha, uint8_t *__restrict__ hard,
+    const uint32_t *__restrict__ state_w, uint32_t *__restrict__ vfail_w, const Op *__restrict__ prog,
+    const uint8_t *__restrict__ tables, const int32_t *__restrict__ fast_idx, int n_ops, int n_slots, int n_out)
 {
     extern __shared__ uint32_t lds[];
-    const PassParams &P = *Pp;           // (pass parameters in device memory: the argument segment stays a handful of pointers)
+    const ClassParams &P = *Pp;
     const int lane = threadIdx.x;
-    const int g = blockIdx.x / P.blocks_per_group;
-    const int b = blockIdx.x - g * P.blocks_per_group;
-    const int si = find_seg(P, b);
-    const PassSeg S = P.seg[si];
+    const int wave = blockIdx.x;
+    const int gl = wave / P.waves_per_group;
+    if (gl >= P.G) return;
+    const int chunk = wave - gl * P.waves_per_group;
+    const int g = gl + P.g0;
 
     uint32_t amask[PACK];
     if (load_active<PACK>(state_w, g, lane, amask)) return;
     const uint32_t smask = pack_masks<PACK>(amask);
 
-    uint32_t *slot = lds;                                    // [slots_lds][64]
-    uint32_t *ostage = lds + P.slots_lds * kWave;            // [out_slots][64]
+    uint32_t *slot = lds;                                    // [n_slots][64]
+    uint32_t *ostage = lds + n_slots * kWave;                // [n_out][64]
     const uint8_t *tab;
     if (LDS_TAB) {
-        uint32_t *lt = ostage + out_slots * kWave;
-        const uint32_t *gt = reinterpret_cast<const uint32_t *>(tables + S.tab_off);
-        for (int i = lane; i < S.tab_bytes / 4; i += kWave) lt[i] = gt[i];
+        uint32_t *lt = ostage + n_out * kWave;
+        const uint32_t *gt = reinterpret_cast<const uint32_t *>(tables + P.tab_off[0]);
+        for (int i = lane; i < P.tab_len[0] / 4; i += kWave) lt[i] = gt[i];
         __syncthreads();
         tab = reinterpret_cast<const uint8_t *>(lt);
     } else {
-        tab = tables + S.tab_off;
+        tab = tables + P.tab_off[0];
     }
 
     const size_t gE = (size_t)g * (size_t)P.E, gN = (size_t)g * (size_t)P.N;
-    const int first = (b - S.block_begin) * P.nodes_per_block;
-    int last = first + P.nodes_per_block;
-    if (last > S.n_nodes) last = S.n_nodes;
-    const Op *prog = ops + S.op_off;
+    const int first = chunk * P.nodes_per_wave;
+    int last = first + P.nodes_per_wave;
+    if (last > P.n_nodes) last = P.n_nodes;
+    // the class's dense table: VAR / DEC {node, first edge} per node; CHK the P.deg edge ids of each check.  The check tables are
+    // reordered by chain fusion only under min-sum, which is symmetric in its inputs (cn_minsum_generic_kernel): a CHKTREE
+    // class keeps the canonical edge order (ascending variable node) its program consumes
+    const int32_t *itab = fast_idx + P.idx_off;
     uint32_t fail[PACK];
 #pragma unroll
     for (int h = 0; h < PACK; h++) fail[h] = 0;
 
     for (int i = first; i < last; i++) {
-        const int node = node_list[S.node_off + i];
-        const int p0 = node_ptr[node];
+        const int32_t *edges = itab + (size_t)i * (KIND == TT_CHK ? P.deg : 2);
+        const int node = KIND == TT_CHK ? 0 : edges[0], p0 = KIND == TT_CHK ? 0 : edges[1];
         uint32_t neg_ref[PACK], dec_bit[PACK];
 #pragma unroll
         for (int h = 0; h < PACK; h++) {
             // ---- gather inputs of this half into slots 0..n_in-1
             if (KIND == TT_CHK) {
                 uint32_t par = 0;
-                for (int k = 0; k < S.deg; k++) {
-                    const int e = cn_idx[p0 + k];
-                    const uint32_t x = unpack_half<PACK>(*reinterpret_cast<const uint32_t *>(msgs + (gE + (size_t)e) * kRowBytes + lane * 4), h);
+                for (int k = 0; k < P.deg; k++) {
+                    const uint32_t x = unpack_half<PACK>(*reinterpret_cast<const uint32_t *>(msgs + (gE + (size_t)edges[k]) * kRowBytes + lane * 4), h);
                     slot[k * kWave + lane] = x;
                     par ^= swar_lt(x, (uint32_t)P.nz);
                 }
                 if (P.check) fail[h] |= par;
             } else {
-                for (int k = 0; k < S.deg; k++)
+                for (int k = 0; k < P.deg; k++)
                     slot[k * kWave + lane] = unpack_half<PACK>(*reinterpret_cast<const uint32_t *>(msgs + (gE + (size_t)(p0 + k)) * kRowBytes + lane * 4), h);
-                slot[S.deg * kWave + lane] = unpack_half<PACK>(*reinterpret_cast<const uint32_t *>(cha + (gN + (size_t)node) * kRowBytes + lane * 4), h);
+                slot[P.deg * kWave + lane] = unpack_half<PACK>(*reinterpret_cast<const uint32_t *>(cha + (gN + (size_t)node) * kRowBytes + lane * 4), h);
             }
             // ---- run the program
             uint32_t have_ref = 0;
             neg_ref[h] = 0; dec_bit[h] = 0;
-            for (int o = 0; o < S.n_ops; o++) {
+            for (int o = 0; o < n_ops; o++) {
                 const Op &op = prog[o];
                 uint32_t lab[4] = {0, 0, 0, 0}, par[4] = {0, 0, 0, 0};
                 for (int c = 0; c < op.nchild; c++) {
@@ -128,10 +131,8 @@ __global__ __launch_bounds__(64) void tree_pass_kernel(
         if (KIND == TT_DEC) {
             store_row_masked<PACK>(reinterpret_cast<uint32_t *>(hard + (gN + (size_t)node) * kRowBytes + lane * 4), pack_halves<PACK>(dec_bit), smask);
         } else {
-            for (int k = 0; k < S.n_out; k++) {
-                size_t row;
-                if (KIND == TT_CHK) row = gE + (size_t)cn_idx[p0 + k];
-                else row = gE + (size_t)(p0 + k);
+            for (int k = 0; k < n_out; k++) {
+                const size_t row = gE + (size_t)(KIND == TT_CHK ? edges[k] : p0 + k);
                 uint32_t *p = reinterpret_cast<uint32_t *>(msgs + row * kRowBytes + lane * 4);
                 store_row_masked<PACK>(p, ostage[k * kWave + lane], smask);
             }
@@ -139,11 +140,12 @@ __global__ __launch_bounds__(64) void tree_pass_kernel(
                 store_row_masked<PACK>(reinterpret_cast<uint32_t *>(hard + (gN + (size_t)node) * kRowBytes + lane * 4), pack_halves<PACK>(neg_ref), smask);
         }
     }
-    if (KIND != TT_DEC && P.check) flag_frames<PACK>(vfail_w, P.vfail_stride_w, g, lane, fail, amask);
+    if (KIND != TT_DEC && P.check) flag_frames<PACK>(vfail_w + P.vfail_off_w, P.vfail_stride_w, g, lane, fail, amask);
 }
 
 // ------------------------------------------------------------------------------------------
-// Min-sum check pass, any degree (src/LDPC_Code_LUT.cpp:355-402).  Two sweeps over the
+// Min-sum check pass, any degree (src/LDPC_Code_LUT.cpp:355-402); one degree class per launch,
+// blocks as in tree_pass_kernel.  Two sweeps over the
 // check's rows: the first accumulates min1/min2/sign product, the second re-reads each row
 // (L1/L2 hit) and writes the extrinsic message.  Byte-serial arithmetic; the specialised
 // kernel in kernels_fast.hpp keeps the rows in registers and works on packed bytes.
@@ -152,28 +154,29 @@ __global__ __launch_bounds__(64) void tree_pass_kernel(
 // ------------------------------------------------------------------------------------------
 template <int PACK>
 __global__ __launch_bounds__(64) void cn_minsum_generic_kernel(
-    const PassParams *__restrict__ Pp, uint8_t *__restrict__ msgs, const uint32_t *__restrict__ state_w, uint32_t *__restrict__ vfail_w,
-    const int32_t *__restrict__ node_list, const int32_t *__restrict__ cn_ptr, const int32_t *__restrict__ cn_idx)
+    const ClassParams *__restrict__ Pp, uint8_t *__restrict__ msgs, const uint32_t *__restrict__ state_w, uint32_t *__restrict__ vfail_w,
+    const int32_t *__restrict__ fast_idx)
 {
-    const PassParams &P = *Pp;
+    const ClassParams &P = *Pp;
     const int lane = threadIdx.x;
-    const int g = blockIdx.x / P.blocks_per_group;
-    const int b = blockIdx.x - g * P.blocks_per_group;
-    const PassSeg S = P.seg[find_seg(P, b)];
+    const int wave = blockIdx.x;
+    const int gl = wave / P.waves_per_group;
+    if (gl >= P.G) return;
+    const int chunk = wave - gl * P.waves_per_group;
+    const int g = gl + P.g0;
     uint32_t amask[PACK];
     if (load_active<PACK>(state_w, g, lane, amask)) return;
     const uint32_t smask = pack_masks<PACK>(amask);
     const size_t gE = (size_t)g * (size_t)P.E;
-    const int first = (b - S.block_begin) * P.nodes_per_block;
-    int last = first + P.nodes_per_block;
-    if (last > S.n_nodes) last = S.n_nodes;
+    const int first = chunk * P.nodes_per_wave;
+    int last = first + P.nodes_per_wave;
+    if (last > P.n_nodes) last = P.n_nodes;
     const int nz = P.nz;
     uint32_t fail[PACK];
 #pragma unroll
     for (int h = 0; h < PACK; h++) fail[h] = 0;
     for (int i = first; i < last; i++) {
-        const int c = node_list[S.node_off + i];
-        const int p0 = cn_ptr[c];
+        const int32_t *edges = fast_idx + P.idx_off + (size_t)i * P.deg;       // (any order: min-sum is symmetric in its inputs)
         int min1[PACK][4], min2[PACK][4];
         uint32_t sp[PACK];
 #pragma unroll
@@ -182,8 +185,8 @@ __global__ __launch_bounds__(64) void cn_minsum_generic_kernel(
 #pragma unroll
             for (int j = 0; j < 4; j++) { min1[h][j] = nz; min2[h][j] = nz; }
         }
-        for (int k = 0; k < S.deg; k++) {
-            const uint32_t xr = *reinterpret_cast<const uint32_t *>(msgs + (gE + (size_t)cn_idx[p0 + k]) * kRowBytes + lane * 4);
+        for (int k = 0; k < P.deg; k++) {
+            const uint32_t xr = *reinterpret_cast<const uint32_t *>(msgs + (gE + (size_t)edges[k]) * kRowBytes + lane * 4);
 #pragma unroll
             for (int h = 0; h < PACK; h++) {
                 const uint32_t x = unpack_half<PACK>(xr, h);
@@ -201,8 +204,8 @@ __global__ __launch_bounds__(64) void cn_minsum_generic_kernel(
 #pragma unroll
             for (int h = 0; h < PACK; h++) fail[h] |= sp[h];
         }
-        for (int k = 0; k < S.deg; k++) {
-            uint32_t *row = reinterpret_cast<uint32_t *>(msgs + (gE + (size_t)cn_idx[p0 + k]) * kRowBytes + lane * 4);
+        for (int k = 0; k < P.deg; k++) {
+            uint32_t *row = reinterpret_cast<uint32_t *>(msgs + (gE + (size_t)edges[k]) * kRowBytes + lane * 4);
             const uint32_t xr = *row;
             uint32_t rr[PACK];
 #pragma unroll
@@ -224,7 +227,7 @@ __global__ __launch_bounds__(64) void cn_minsum_generic_kernel(
             *row = bfi(smask, pack_halves<PACK>(rr), xr);
         }
     }
-    if (P.check) flag_frames<PACK>(vfail_w, P.vfail_stride_w, g, lane, fail, amask);
+    if (P.check) flag_frames<PACK>(vfail_w + P.vfail_off_w, P.vfail_stride_w, g, lane, fail, amask);
 }
 
 // ------------------------------------------------------------------------------------------

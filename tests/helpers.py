@@ -31,6 +31,9 @@ CONFIGS = {
     "reg36_n1000_q3_chklut": ("rate0.50_dv03_dc06_N1000", dict(sigma2=0.80 ** 2, max_iters=10, nq_cha=16, nq_msg=8, min_lut=False)),
     "reg36_n1000_rootonly": ("rate0.50_dv03_dc06_N1000", dict(sigma2=0.85 ** 2, max_iters=6, nq_cha=8, nq_msg=8, tree_method="root_only")),
     "reg36_n1000_high": ("rate0.50_dv03_dc06_N1000", dict(sigma2=0.85 ** 2, max_iters=6, nq_cha=16, nq_msg=16, tree_method="auto_bin_high")),
+    # three kernels inside one variable pass: degree 3 on the compile-time kernel, degrees 2, 9 and 17 (unbalanced trees) on the generated
+    # one or, with LUTLDPC_JIT=0, in the interpreter
+    "n500_high": ("rate0.50_dv02-17_dc08-09_lut_q4_N500", dict(sigma2=0.80 ** 2, max_iters=6, nq_cha=16, nq_msg=16, tree_method="auto_bin_high")),
     # C5 of BASELINE.json: params/ber.ini.regular.example (design_SNRdB 3.9, R = 1 - 325/2048)
     "c5_minlut": ("rate0.84_reg_v6c32_N2048", dict(sigma2=None, design_snr_db=3.9, max_iters=8, nq_cha=16, nq_msg=8,
                                                    tree_method="filename=" + str(TREES / "6_32_wide.ini"), rank=325)),

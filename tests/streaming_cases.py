@@ -95,6 +95,13 @@ COMPACT_KNOBS = [("compact_share0", dict(COMPACT, LUTLDPC_COMPACT_MIN_SHARE="0")
 # generated check kernels on (sign, magnitude) tables: (configuration of helpers.CONFIGS, frames, SNR in dB)
 CHK_FULL0 = [("reg36_n1000_q3_chklut", 251, 2.5), ("c5_chklut", 205, 4.0)]
 
+# ---- section E: more degree classes on one side than one launch of the interpreter once held (32): check degrees 2..34, three
+#      checks each, under 594 degree-3 variables.  Degrees 33 and 34 are beyond cn_minsum_fast_kernel, so a default check pass runs
+#      31 classes on it and two on cn_minsum_generic_kernel; the code has no case in the fused kernel and does not fit the LDS.
+MANY_VDEG, MANY_CDEG, MANY_SIGMA, MANY_B, MANY_LABEL_SEED = {3: 594}, {d: 3 for d in range(2, 35)}, 0.45, 600, 4
+#      the oracle's iteration codes on the batch with both exit tests on (test_streaming_cases_cpu.py): code -> frames
+MANY_CODES = {-5: 32, 0: 2, 1: 20, 2: 166, 3: 180, 4: 114, 5: 86}
+
 _tmp = None
 
 
@@ -117,6 +124,33 @@ def codec(name):
     cd.rate = 1.0 - M / N
     cd.design_luts(sigma2=sig ** 2, max_iters=ITERS, nq_msg=np.full(ITERS, nqm, np.int32), nq_cha=nqc, allow_deg1=deg1)
     return cd
+
+
+@functools.lru_cache(maxsize=None)
+def many_codec():
+    """Section E: the code of 33 check classes, designed with the oracle."""
+    global _tmp
+    _tmp = _tmp or tempfile.TemporaryDirectory(prefix="streaming_cases_")
+    path = Path(_tmp.name) / "many.alist"
+    write_degree_alist(path, MANY_VDEG, MANY_CDEG, seed=GRAPH_SEED)
+    N, M = sum(MANY_VDEG.values()), sum(MANY_CDEG.values())
+    cd = orc.Codec(orc.Code(path), skip_rank=True)
+    cd.set_rank(M)
+    cd.rate = 1.0 - M / N
+    cd.design_luts(sigma2=MANY_SIGMA ** 2, max_iters=ITERS, nq_msg=np.full(ITERS, 16, np.int32), nq_cha=16)
+    return cd
+
+
+@functools.lru_cache(maxsize=None)
+def many_labels():
+    """Section E: MANY_B frames at the design SNR (4.717 dB), frame 0 noise-free.  Shared read-only."""
+    cd = many_codec()
+    cha, msg, _ = awgn_labels(cd, MANY_B, -10 * np.log10(2 * cd.rate * MANY_SIGMA ** 2), seed=MANY_LABEL_SEED)
+    cha[0] = cd.nq_cha - 1
+    msg[0] = cd.nq_msg[0] - 1
+    cha.setflags(write=False)
+    msg.setflags(write=False)
+    return cha, msg
 
 
 def snr(name):

@@ -59,3 +59,22 @@ def test_generated_check_kernels_on_sign_magnitude_tables(name, n, snr, monkeypa
     it = _decode(dec, cd, cha, msg, None)
     assert len(set(it.tolist())) >= 3
     dec.close()
+
+
+def test_more_degree_classes_than_one_interpreter_launch_once_held(monkeypatch):
+    """Section E of streaming_cases.py: 33 check classes.  With no knob the check pass is 31 launches of cn_minsum_fast_kernel and two
+    of cn_minsum_generic_kernel (degrees 33, 34); with LUTLDPC_USE_FAST=0 every class of both passes runs the interpreter."""
+    import numpy as np
+    cd = sc.many_codec()
+    cha, msg = sc.many_labels()
+    cache = {}
+    for kn in ({}, {"LUTLDPC_USE_FAST": "0"}):
+        dec, desc = sc.describe(None, kn, monkeypatch, device=0, cd=cd)
+        assert desc["resident"] == 0 and desc["skewed_pipeline"] == 0 and len(desc["cn_classes"]) == 33, desc
+        generic = ["cn_minsum_generic_kernel"] * 33 if kn else ["cn_minsum_fast_kernel"] * 31 + ["cn_minsum_generic_kernel"] * 2
+        assert [c["kernel"] for c in desc["cn_classes"]] == generic, desc
+        assert desc["vn_classes"][0]["kernel"] == ("tree_pass_kernel<VAR>" if kn else "vn_balanced_fast_kernel"), desc
+        it = _decode(dec, cd, cha, msg, cache)
+        codes, counts = np.unique(it, return_counts=True)
+        assert dict(zip(codes.tolist(), counts.tolist())) == sc.MANY_CODES
+        dec.close()

@@ -63,9 +63,11 @@ def test_skewed_pipeline(name, B, snr, env, monkeypatch):
     dec.close()
 
 
-@pytest.mark.parametrize("name", ["c5_minlut", "reg36_n1000_rootonly", "reg36_n1000_high", "reg36_n1000_q5", "c5_chklut", "reg36_n1000_q3_chklut"])
+@pytest.mark.parametrize("name", ["c5_minlut", "reg36_n1000_rootonly", "reg36_n1000_high", "reg36_n1000_q5", "c5_chklut", "reg36_n1000_q3_chklut", "n500_high"])
 def test_generated_kernels_are_used_and_match(name, monkeypatch):
-    """jit.hpp: the kernel generated from the node program vs the oracle, and vs the interpreter (LUTLDPC_JIT=0)."""
+    """jit.hpp: the kernel generated from the node program vs the oracle, and vs the interpreter (LUTLDPC_JIT=0).
+    n500_high mixes kernels inside one variable pass: degree 3 (balanced) on the compile-time kernel, degrees 2, 9 and 17 on the
+    generated kernel, then in the interpreter; the checks on cn_minsum_fast_kernel throughout."""
     monkeypatch.setenv("LUTLDPC_RESIDENT", "0")           # the per-class pass kernels of the streaming path are what is tested here
     cd = oracle_codec(name)
     dec = product_decoder(cd)
@@ -75,8 +77,17 @@ def test_generated_kernels_are_used_and_match(name, monkeypatch):
     if name.endswith("chklut"):
         assert dec.describe()["cn_classes"][0]["kernel"] == "lutldpc_jit_pass", dec.describe()
     mode = 1 if name.startswith("c5") else 0
-    cha, msg, _ = awgn_labels(cd, 700, 4.0 if name.startswith("c5") else 2.2, seed=31, mode=mode)
-    _compare(cd, dec, cha, msg, True, True)
+    mixed = ["lutldpc_jit_pass", "vn_balanced_fast_kernel", "lutldpc_jit_pass", "lutldpc_jit_pass"]      # n500_high: degrees 2, 3, 9, 17
+    if name == "n500_high":
+        assert [c["kernel"] for c in dec.describe()["vn_classes"]] == mixed, dec.describe()
+        assert all(c["kernel"] == "cn_minsum_fast_kernel" for c in dec.describe()["cn_classes"]), dec.describe()
+        cha, msg, _ = awgn_labels(cd, 600, 3.5, seed=3)
+        cha[0] = cd.nq_cha - 1; msg[0] = cd.nq_msg[0] - 1                # noise-free: passes the test on the channel decisions
+    else:
+        cha, msg, _ = awgn_labels(cd, 700, 4.0 if name.startswith("c5") else 2.2, seed=31, mode=mode)
+    it = _compare(cd, dec, cha, msg, True, True)
+    if name == "n500_high":
+        assert set(it.tolist()) == {-6, 0, 3, 4, 5, 6}
     _compare(cd, dec, cha, msg, False, False)
     got = dec.lut_decode_batch(cha, msg)
     dec.close()
@@ -85,6 +96,8 @@ def test_generated_kernels_are_used_and_match(name, monkeypatch):
     assert ref.describe()["vn_classes"][0]["kernel"] == ("tree_pass_kernel<VAR>" if jit_expected else "vn_balanced_fast_kernel")
     if name.endswith("chklut"):
         assert ref.describe()["cn_classes"][0]["kernel"] == "tree_pass_kernel<CHK>"
+    if name == "n500_high":
+        assert [c["kernel"] for c in ref.describe()["vn_classes"]] == [k.replace("lutldpc_jit_pass", "tree_pass_kernel<VAR>") for k in mixed], ref.describe()
     ref.set_exit_conditions(cd.max_iters, False, False)
     want = ref.lut_decode_batch(cha, msg)
     assert (got[0] == want[0]).all() and (got[1] == want[1]).all()

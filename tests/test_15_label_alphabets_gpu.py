@@ -73,6 +73,27 @@ def _widest(cd):
     return max([cd.nq_cha] + [int(q) for q in cd.nq_msg])
 
 
+def _pow2(n):
+    return n & (n - 1) == 0
+
+
+def _expected_vn(cd, env):
+    """The kernel string of a variable class: per variable pass (ii writes the alphabet of iteration ii + 1 from that of ii) the
+    interpreter where the new alphabet's half is no power of two (no sign bit) or the fast kernels are off; else the compile-time
+    kernel where every alphabet feeding the tables is a power of two of at most 16 labels (balanced tables of <= 256 entries), else
+    the generated one.  Distinct names joined in the order fast, generated, interpreter."""
+    nq = [int(q) for q in cd.nq_msg]
+    used = set()
+    for ii in range(len(nq) - 1):
+        if env.get("LUTLDPC_USE_FAST") == "0" or not _pow2_half(nq[ii + 1]):
+            used.add("tree_pass_kernel<VAR>")
+        elif _pow2(nq[ii]) and _pow2(cd.nq_cha) and max(nq[ii], cd.nq_cha) <= 16:
+            used.add("vn_balanced_fast_kernel")
+        else:
+            used.add("lutldpc_jit_pass")
+    return "+".join(k for k in ("vn_balanced_fast_kernel", "lutldpc_jit_pass", "tree_pass_kernel<VAR>") if k in used)
+
+
 def _expected_kinds(cd, env):
     """(resident, skewed, check kernel) for alphabets of up to 16 labels; above, the variable tables leave the compile-time
     kernels and neither the resident decoder nor the skewed pipeline is promised (None: not asserted)."""
@@ -112,6 +133,7 @@ def test_decode_at_every_alphabet_matches_oracle(name, snr, modes, path, monkeyp
         assert desc["skewed_pipeline"] == int(skewed), desc
     if cn is not None:
         assert all(c["kernel"] == cn for c in desc["cn_classes"]), desc
+        assert all(c["kernel"] == _expected_vn(cd, env) for c in desc["vn_classes"]), (desc, _expected_vn(cd, env))
     assert desc["pack"] == (1 if path == "pack1" or _widest(cd) > 16 else 2), desc
     print(name, path, {k: desc[k] for k in ("resident", "skewed_pipeline", "pack")}, desc["cn_classes"][0]["kernel"], desc["vn_classes"][0]["kernel"])
     for mode in modes:

@@ -161,3 +161,32 @@ def test_compaction_batch_empties_a_group_by_the_first_check_point(name):
     _, it = cd.lut_decode_batch_flat(cha, msg)
     active = (it < 0) | (it > 1)
     assert 0 < active[:1024].sum() <= 512 and 0 < active[1024:].sum() <= 512, (active[:1024].sum(), active[1024:].sum())
+
+
+def test_a_code_may_have_any_number_of_degree_classes(monkeypatch):
+    """Section E: 33 check classes on a host-only handle.  Degrees 2..32 run cn_minsum_fast_kernel, 33 and 34 the any-degree
+    kernel; neither the fused pipeline nor the LDS-resident decoder takes the code, so every pass is per-class launches.  And the
+    batch of the GPU test holds every iteration code from -5 to 5."""
+    import numpy as np
+    cd = sc.many_codec()
+    dec, desc = sc.describe(None, {}, monkeypatch, cd=cd)
+    dec.close()
+    assert [c["deg"] for c in desc["cn_classes"]] == list(range(2, 35)) and [c["nodes"] for c in desc["cn_classes"]] == [3] * 33
+    assert [c["kernel"] for c in desc["cn_classes"]] == ["cn_minsum_fast_kernel"] * 31 + ["cn_minsum_generic_kernel"] * 2, desc
+    assert desc["resident"] == 0 and desc["skewed_pipeline"] == 0, desc
+    cha, msg = sc.many_labels()
+    cd.set_exit_conditions(cd.max_iters, True, True)
+    _, it = cd.lut_decode_batch_flat(cha, msg)
+    codes, counts = np.unique(it, return_counts=True)
+    assert dict(zip(codes.tolist(), counts.tolist())) == sc.MANY_CODES
+
+
+def test_describe_names_every_kernel_of_a_mixed_schedule(monkeypatch):
+    """reg36_n1000_m16_12_8: the variable passes that write 12-label messages run the interpreter (no sign bit in a label of a
+    12-label alphabet), the others the compile-time kernel; the check passes that read them likewise.  describe() names both,
+    fast first."""
+    from helpers import oracle_codec
+    dec, desc = sc.describe(None, {}, monkeypatch, cd=oracle_codec("reg36_n1000_m16_12_8"))
+    dec.close()
+    assert [c["kernel"] for c in desc["vn_classes"]] == ["vn_balanced_fast_kernel+tree_pass_kernel<VAR>"], desc
+    assert [c["kernel"] for c in desc["cn_classes"]] == ["cn_minsum_fast_kernel+cn_minsum_generic_kernel"], desc

@@ -54,10 +54,11 @@ def test_kernel_paths_agree_at_full_iteration_count(name, snr, monkeypatch):
 
 
 @pytest.mark.parametrize("name,B,snr", [("n500_q4", 300, 1.8), ("reg36_n1000_mixed", 64, 2.2), ("c5_chklut", 20, 4.2), ("reg36_n1000_high", 33, 2.0)])
-@pytest.mark.parametrize("env", [{"LUTLDPC_PACK": "1"}, {"LUTLDPC_USE_FAST": "0"}, {"LUTLDPC_PACK": "1", "LUTLDPC_USE_FAST": "0"}, {"LUTLDPC_VALIDATE": "1"}])
+@pytest.mark.parametrize("env", [{"LUTLDPC_PACK": "1"}, {"LUTLDPC_USE_FAST": "0"}, {"LUTLDPC_PACK": "1", "LUTLDPC_USE_FAST": "0"}, {"LUTLDPC_VALIDATE": "1"},
+                                 {"LUTLDPC_VALIDATE": "1", "LUTLDPC_USE_FAST": "0"}])
 def test_kernel_variants(name, B, snr, env, monkeypatch):
     """Byte rows vs nibble rows, specialised vs generic kernels, the validating debug mode (every class's parameters checked
-    against the allocation sizes before its launch): every combination is bit-exact."""
+    against the allocation sizes before its launch, interpreter launches included): every combination is bit-exact."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     cd = oracle_codec(name)
