@@ -100,6 +100,9 @@ int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint6
     const uint8_t *sent_rows = nullptr;
     if ((rc = sent_rows_of(d, codewords, device_codewords, seed, stream, frame0, B, &sent_rows))) return rc;
     if ((rc = sample_tiles(d, C, seed, stream, frame0, B, sent_rows))) return rc;
+    // the sampled labels, read back from the rows before the decode works on them: a decode that compacts leaves the channel rows
+    // in slot order (launch_uncompaction brings back the decided bits and the iteration codes only)
+    if (cha_out && (rc = rows_to_host(d, d->d_cha_t.p, cha_out, B))) return rc;
     if ((rc = decode_tiles(d, B))) return rc;
     {
         Timed t(d, LUTLDPC_K_FRONTEND);
@@ -113,7 +116,6 @@ int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint6
         LAUNCH_CHECK();
     }
     if ((rc = copy_to_host(d, frame_stats, d->d_stats.p, sizeof(int32_t) * (size_t)B * 4))) return rc;
-    if (cha_out && (rc = rows_to_host(d, d->d_cha_t.p, cha_out, B))) return rc;
     if (bits_out && (rc = rows_to_host(d, d->d_hard.p, bits_out, B))) return rc;
     if (req && (rc = capture_events(d, B, K_info, sent_rows, d->d_stats.p, req))) return rc;
     HIP_TRY(hipStreamSynchronize(d->stream));
