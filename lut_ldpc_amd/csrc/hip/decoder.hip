@@ -61,9 +61,15 @@ void make_describe(lutldpc_decoder *d) {
         for (int k = 0; k < 3; k++) if (used[k]) s += (s.empty() ? "" : "+") + std::string(name[k]);
         return s;
     };
+    // the compile-time variable kernel of the class reads the root table as packed 64-bit rows (ClassParams::root_rows) in some iteration
+    auto root_rows_of = [&](size_t i) {
+        for (int ii = 0; ii < std::max(I - 1, 1); ii++)
+            if (vn_root_rows(TT_VAR, d->pack, d->vclass[i].deg) && pass_kernel(d, TT_VAR, d->iter_set[(size_t)ii], (int)i, d->Nq_Msg[(size_t)std::min(ii + 1, I - 1)] / 2) == KERNEL_FAST) return true;
+        return false;
+    };
     for (size_t i = 0; i < d->vclass.size(); i++)
         o << (i ? "," : "") << "{\"deg\":" << d->vclass[i].deg << ",\"nodes\":" << d->vclass[i].nodes.size() << ",\"nodes_per_wave\":" << d->npw_vn(d->vclass[i].deg) << ",\"kernel\":\""
-          << kernels_of(TT_VAR, i, {"vn_balanced_fast_kernel", "lutldpc_jit_pass", "tree_pass_kernel<VAR>"}) << "\"}";
+          << kernels_of(TT_VAR, i, {"vn_balanced_fast_kernel", "lutldpc_jit_pass", "tree_pass_kernel<VAR>"}) << "\",\"root_rows\":" << (root_rows_of(i) ? 1 : 0) << "}";
     o << "],\"cn_classes\":[";
     for (size_t i = 0; i < d->cclass.size(); i++) {
         // degree-2 nodes updated inside the check pass of this class: the forward links of its chain table (build_fast_index)
@@ -102,7 +108,7 @@ static const Knob kKnobs[] = {
     // ---- kernel choice
     KNOB_F("LUTLDPC_USE_FAST", use_fast, "1: compile-time specialised kernels (and with them the fused pipeline, the generated kernels, the resident decoder); 0: interpreter kernels only"),
     KNOB_F("LUTLDPC_JIT", use_jit, "1: run-time generated kernels for shapes the compile-time path does not cover (jit.hpp)"),
-    KNOB_I("LUTLDPC_PACK", pack, 1, 1, "1: byte rows even where every alphabet has <= 16 labels (unset: nibble rows there)"),
+    KNOB_I("LUTLDPC_PACK", pack, 1, 1, "1: byte rows even where every alphabet has <= 16 labels (unset: nibble rows there; on them the compile-time variable kernels of degree >= 3 read the root table as packed 64-bit rows, describe(): root_rows)"),
     KNOB_F("LUTLDPC_CHK_FULL", chk_full_labels, "1: generated check kernels on full-label tables; 0: on (sign, magnitude) tables as the reference walks them"),
     KNOB_F("LUTLDPC_COMPOSE", use_compose, "1: exact table composition for the resident kernel's trees (measured slower: LDS bank conflicts, see compile_all)"),
     KNOB_I("LUTLDPC_COMPOSE_SPACE", compose_space, 0, 65536, "largest composed table, entries"),

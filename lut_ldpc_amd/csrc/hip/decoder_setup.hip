@@ -159,6 +159,25 @@ static void append_tables(lutldpc_decoder *d, ProgramForm &f, bool align16) {
     d->all_tables.insert(d->all_tables.end(), f.prog.tables.begin(), f.prog.tables.end());
 }
 
+// the packed root rows of a balanced variable tree and the scaled table of its top inner node join the blob (pack_root_rows);
+// a tree whose tables do not fit the form keeps rows_off = -1 (fast_covers: nibble rows then take the generated kernel)
+static void add_root_rows(lutldpc_decoder *d, FastClassPlan &f, int deg) {
+    if (!f.ok || deg < 3) return;
+    const int root = f.n_tables - 1, top = root - 1;
+    std::vector<uint8_t> rows, top4;
+    if (!pack_root_rows(d->all_tables.data() + f.tab_off[root], (size_t)f.tab_len[root], f.tab_shift[root],
+                        d->all_tables.data() + f.tab_off[top], (size_t)f.tab_len[top], rows, top4)) return;
+    auto append = [&](const std::vector<uint8_t> &t) {
+        while (d->all_tables.size() & 3) d->all_tables.push_back(0);
+        const int32_t off = (int32_t)d->all_tables.size();
+        d->all_tables.insert(d->all_tables.end(), t.begin(), t.end());
+        return off;
+    };
+    f.rows_off = append(rows);
+    f.top4_off = append(top4);
+    while (d->all_tables.size() & 3) d->all_tables.push_back(0);
+}
+
 // Compile the trees of one kind of tree set s into one form of every degree class, then the checks' full-label form of it.
 // Base forms: the trees as they are, with their look-ups (all_ops) and the balanced-tree plans.
 // Composed forms: after exact table composition (compose_tree), for the generated LDS-resident kernel.  Off by default
@@ -188,6 +207,7 @@ static int add_forms(lutldpc_decoder *d, int kind, int s, bool composed) {
             std::map<const TreeNode *, std::pair<uint32_t, uint32_t>> tab_of;
             for (auto &nt : f.prog.node_tabs) tab_of[nt.first] = {(uint32_t)f.tab.off + nt.second[0], nt.second[1]};
             c.fast = plan_fast_vn(t, kind, cls[i].deg, tab_of);
+            if (kind == TT_VAR) add_root_rows(d, c.fast, cls[i].deg);
         }
     }
     if (!composed) S.valid = true;
@@ -303,7 +323,7 @@ static void build_jit(lutldpc_decoder *d) {
             TreeSetPlan &S = *d->tree_set(kind, (int)s);
             const auto &cls = kind == TT_CHK ? d->cclass : d->vclass;
             for (size_t i = 0; i < S.cls.size(); i++) {
-                if (kind != TT_CHK && fast_covers(d, S.cls[i].fast, cls[i].deg)) continue;
+                if (kind != TT_CHK && fast_covers(d, S.cls[i].fast, kind, cls[i].deg)) continue;
                 std::string src, log;
                 const bool full = kind == TT_CHK && d->chk_form((int)s, (int)i, false) == &S.cls[i].full;
                 if (!jit_class_source(d, full ? TT_CHK + 32 : kind, s, i, src, log)) { d->jit_log = log; continue; }

@@ -409,7 +409,10 @@ constexpr int kPerClassLaunch = -1;
 ClassParams cn_class_params(const lutldpc_decoder *d, size_t ci, HalfRange groups, int nz, int check, int skew_ii = kPerClassLaunch);
 ClassParams lut_cn_class_params(const lutldpc_decoder *d, int set, size_t ci, HalfRange groups, int nz, int check);      // LUT checks: generated kernel or interpreter
 ClassParams vn_class_params(const lutldpc_decoder *d, int kind, int set, size_t ci, HalfRange groups, int nz, int check, int write_hard, int skew_ii = kPerClassLaunch);
-inline bool fast_covers(const lutldpc_decoder *d, const FastClassPlan &f, int deg) { return d->opt.use_fast && f.ok && deg <= kFastMaxDeg; }   // the balanced-tree kernel has a case for the class (pass_kernel decides)
+// the balanced-tree kernel has a case for the class (pass_kernel decides); where it reads the root as packed rows, the plan has them
+inline bool fast_covers(const lutldpc_decoder *d, const FastClassPlan &f, int kind, int deg) {
+    return d->opt.use_fast && f.ok && deg <= kFastMaxDeg && (!vn_root_rows(kind, d->pack, deg) || f.rows_off >= 0);
+}
 // the kernel a ClassParams is meant for: its pass, compile-time (min-sum, balanced tables of <= 256 bytes) or one class blob
 // (`generated`: the generated kernels and the interpreter), the degrees it has cases for and what the error message calls that limit
 struct KernelCases { int tree_kind; bool generated; int max_vn_deg, max_cn_deg; const char *limit; };

@@ -61,7 +61,7 @@ PassKernel pass_kernel(const lutldpc_decoder *d, int kind, int set, int cls, int
     // decided bits); that holds only where nz is a power of two.  A variable pass that writes any other alphabet (Nq_Msg = 12:
     // nz = 6) runs in the interpreter, which compares the label with nz.
     if (!t || (kind == TT_VAR && !is_pow2(nz))) return KERNEL_INTERPRETER;
-    if (kind != TT_CHK && fast_covers(d, t->fast, d->vclass[(size_t)cls].deg)) return KERNEL_FAST;
+    if (kind != TT_CHK && fast_covers(d, t->fast, kind, d->vclass[(size_t)cls].deg)) return KERNEL_FAST;
     return t->jit ? KERNEL_GENERATED : KERNEL_INTERPRETER;      // (build_jit: a kernel for every class without a compile-time one)
 }
 
@@ -124,6 +124,11 @@ ClassParams vn_class_params(const lutldpc_decoder *d, int kind, int set, size_t 
     if (k == KERNEL_FAST) {                                           // balanced tree: its tables in canonical order
         P.shift_msg = f.shift_msg;
         for (int t = 0; t < f.n_tables; t++) { P.tab_off[t] = f.tab_off[t]; P.tab_len[t] = f.tab_len[t]; P.tab_shift[t] = f.tab_shift[t]; }
+        if (vn_root_rows(kind, d->pack, c.deg)) {                     // the root as packed rows, the top inner node's table times 4 (fast_covers: the plan has them)
+            P.root_rows = 1;
+            P.tab_off[f.n_tables - 1] = f.rows_off; P.tab_len[f.n_tables - 1] = kRootRowsBytes;
+            P.tab_off[f.n_tables - 2] = f.top4_off;
+        }
     } else {                                                          // generated kernel, interpreter: the class blob
         P.tab_off[0] = t.base.tab.off; P.tab_len[0] = t.base.tab.bytes;
     }
@@ -162,6 +167,9 @@ int validate_class(const lutldpc_decoder *d, const ClassParams &R, const std::st
         const int leaves = k.tree_kind == TT_DEC ? R.deg : R.deg - 1, nt = leaves > 1 ? leaves : 1;       // LUT nodes of the balanced tree, root included
         for (int t = 0; t < nt; t++)
             if (!table_ok(R.tab_off[t], R.tab_len[t], 1, kFastTableStride)) return bad("table " + std::to_string(t));
+        // the kernel of this (kind, rows, degree) reads the root as packed rows or as bytes: the parameters must say the same
+        if ((R.root_rows != 0) != vn_root_rows(k.tree_kind, d->pack, R.deg)) return bad("root rows");
+        if (R.root_rows && R.tab_len[nt - 1] != kRootRowsBytes) return bad("packed root rows");
     }
     return LUTLDPC_OK;
 }

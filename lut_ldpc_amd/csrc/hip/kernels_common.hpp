@@ -192,6 +192,10 @@ struct ClassParams {
     int32_t tab_off[kFastMaxTables];    // byte offsets into the table blob, canonical node order
     int32_t tab_len[kFastMaxTables];
     int32_t tab_shift[kFastMaxTables];  // log2 alphabet of each table's first child
+    // variable classes of degree >= 3 on nibble rows (vn_balanced_body): 1 = the root's entry (the last table) is the 128 bytes of
+    // packed rows -- row ch = one 64-bit word, nibble t = ROOT[t | ch << shift] -- and the entry before it, the tree's top inner
+    // node, the copy of its table with every entry times 4 (lut_program.hpp: pack_root_rows)
+    int32_t root_rows;
 };
 
 // (x << s) | y in one instruction, s wave-uniform

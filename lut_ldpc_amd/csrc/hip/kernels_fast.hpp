@@ -446,6 +446,11 @@ __device__ __forceinline__ void vn_balanced_body(
     constexpr int N = (KIND == TT_DEC) ? DV : DV - 1;          // message leaves
     constexpr int NI = N > 1 ? N - 1 : 0;
     constexpr int NB = N > 1 ? N : 2;                          // shape used for array sizes when N <= 1
+    // Nibble rows, at least two message leaves: all DV outputs of a frame end in ROOT[top_o | ch << shr] with ONE channel label, and
+    // ROOT[ch][.] is 16 four-bit labels.  The root slot holds the table as 16 packed rows (P.root_rows; 128 bytes = 32 dwords on 32
+    // banks: ds_read_b64 is conflict-free), the top inner node's slot its table times 4: one 64-bit read per frame, issued before the
+    // tree look-ups, then one 64-bit shift and one funnel shift per output instead of an index, a byte read and a merge.
+    constexpr bool ROWS = KIND == TT_VAR && PACK == 2 && N >= 2;
     // stage the class tables (canonical order, fixed 256-byte slots)
     // (table offsets and lengths are multiples of 4: lut_program.hpp pads every table)
     {
@@ -492,7 +497,9 @@ __device__ __forceinline__ void vn_balanced_body(
     };
     auto eval = [&](const uint32_t (&raw)[DV + 1], int v, int e0) {
         constexpr int F = 4 * PACK, BITS = 8 / PACK;             // frames per dword, bits per label
-        constexpr int U = DV <= 8 ? 2 : 1;                       // frames evaluated per trip (independent: ILP for the LDS latency)
+        // frames evaluated per trip (independent: ILP for the LDS latency).  (A degree-8 node with the exit test on and two 64-bit root
+        // rows in flight would take the fused kernel of buckets 0 and 3 from 64 to 69 registers: one frame per trip there.)
+        constexpr int U = (DV <= 8 && !(ROWS && CHECK && DV == 8)) ? 2 : 1;
         constexpr BalShape<NB> SH = make_bal_shape<NB>();
         constexpr int top_off = SH.off[SH.top - NB];
         uint32_t out[DV], hardw = 0;
@@ -509,6 +516,9 @@ __device__ __forceinline__ void vn_balanced_body(
 #pragma unroll
                 for (int k = 0; k <= DV; k++) in[k] = __builtin_amdgcn_ubfe(raw[k], (uint32_t)s, (uint32_t)BITS);
                 const uint32_t ch = in[DV];
+                [[maybe_unused]] uint64_t row = 0;
+                const uint64_t *rows = reinterpret_cast<const uint64_t *>(__builtin_assume_aligned(lds_tab + NI * kFastTableStride, 8));
+                if constexpr (ROWS) row = rows[ch];
                 uint32_t val[(N > 1 ? SH.total : 1)];
                 if constexpr (N > 1) bal_all_nodes<N, KIND == TT_VAR>(in, val, lds_tab, sh, std::make_integer_sequence<int, NI>{});
                 if constexpr (KIND == TT_DEC) {
@@ -519,6 +529,13 @@ __device__ __forceinline__ void vn_balanced_body(
                 } else {
 #pragma unroll
                     for (int o = 0; o < DV; o++) {
+                        if constexpr (ROWS) {
+                            // val[top] is 4 * top: the label sits in the low nibble of the shifted row, and the funnel shift moves exactly
+                            // those four bits into the top nibble -- after the eight frames of the dword, in ascending bit position, every
+                            // frame is where lshl_or(r, s, out[o]) puts it
+                            out[o] = __builtin_amdgcn_alignbit((uint32_t)(row >> val[top_off + o]), out[o], 4);
+                            continue;
+                        }
                         uint32_t r;
                         if constexpr (N == 0) {
                             // degree 1: the only leaf is the channel label (a one-input table: label = ch)
@@ -722,7 +739,12 @@ struct FastClassPlan {
     bool ok = false;
     int n_tables = 0, shift_msg = 0;
     int32_t tab_off[kFastMaxTables] = {}, tab_len[kFastMaxTables] = {}, tab_shift[kFastMaxTables] = {};
+    // variable trees with at least two message leaves whose tables fit it: the packed root rows and the top inner node's table
+    // times 4 (lut_program.hpp: pack_root_rows; decoder_setup.hip: add_root_rows).  -1: none
+    int32_t rows_off = -1, top4_off = -1;
 };
+// nibble rows: the variable pass of a class of degree >= 3 reads the root table as packed rows (vn_balanced_body)
+inline bool vn_root_rows(int kind, int pack, int deg) { return kind == TT_VAR && pack == 2 && deg >= 3; }
 
 // tab_of: LUT node -> (offset in the global blob, length)
 inline FastClassPlan plan_fast_vn(const Tree &t, int kind, int d, const std::map<const TreeNode *, std::pair<uint32_t, uint32_t>> &tab_of) {

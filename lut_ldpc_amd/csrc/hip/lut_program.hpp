@@ -502,4 +502,27 @@ inline bool chk_full_label_program(const Program &prog, Program &out, uint64_t m
     return true;
 }
 
+// ---- packed root rows of a balanced variable tree (kernels_fast.hpp: vn_balanced_body on nibble rows) -----------------------
+// All outputs of a variable node end in ROOT[top_o | ch << shr] with ONE channel label ch.  With alphabets of at most 16 labels the
+// row ROOT[ch][.] is 16 four-bit labels = one 64-bit word: rows[ch] nibble t = ROOT[t | ch << shr], 16 rows = 128 bytes, labels the
+// table does not hold read 0.  The kernel fetches the row once per frame and shifts it by 4 * top_o, so the table of the tree's top
+// inner node -- whose variants feed only the root -- gets a copy with every entry multiplied by 4: `top` arrives as the shift amount.
+// false: the tables do not fit the form (an input alphabet above 16 labels, a root label above 15).
+constexpr int kRootRows = 16, kRootRowsBytes = kRootRows * 8;
+inline bool pack_root_rows(const uint8_t *root, size_t root_len, int shr, const uint8_t *top, size_t top_len, std::vector<uint8_t> &rows, std::vector<uint8_t> &top4) {
+    rows.assign((size_t)kRootRowsBytes, 0);
+    top4.assign(top_len, 0);
+    if (shr < 0 || shr > 4 || root_len > ((size_t)kRootRows << shr)) return false;
+    for (size_t i = 0; i < root_len; i++) {
+        const size_t t = i & ((1u << shr) - 1u), ch = i >> shr;
+        if (root[i] > 15) return false;
+        rows[ch * 8 + t / 2] |= (uint8_t)(root[i] << (4 * (t & 1)));      // (little-endian word: nibble t = bits 4 t .. 4 t + 3)
+    }
+    for (size_t i = 0; i < top_len; i++) {
+        if (top[i] >= (1u << shr)) return false;                          // a label the root table has no column for
+        top4[i] = (uint8_t)(4 * top[i]);
+    }
+    return true;
+}
+
 }  // namespace lutldpc
