@@ -9,6 +9,8 @@ import ctypes as C
 import os
 from pathlib import Path
 
+import numpy as np
+
 _PKG = Path(__file__).resolve().parent
 LIB_PATH = _PKG / "lib" / "liblut_ldpc_amd.so"
 if os.environ.get("LUTLDPC_LIB"):          # A/B runs of two builds of the same library (tools/)
@@ -37,7 +39,7 @@ def _load() -> C.CDLL:
 lib = _load()
 
 _vp, _ip, _u8p, _dp, _cp = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_double), C.c_char_p
-_i64p = C.POINTER(C.c_int64)
+_i64p, _u32p, _u64p = C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
 
 
 class EventRequest(C.Structure):
@@ -72,7 +74,35 @@ class EncodeIO(C.Structure):
     _fields_ = [("on_device", C.c_int32), ("in_stride", C.c_int64), ("out_first", C.c_int32), ("out_count", C.c_int32), ("sync", C.c_int32)]
 
 
-_u32p = C.POINTER(C.c_uint32)
+class ChannelCells(C.Structure):
+    """lutldpc_channel_cells (include/lut_ldpc_hip.h): the cell table of the Philox sampler."""
+    _fields_ = [("n_cells", C.c_int32), ("thr", _u64p), ("cha_label", _u8p), ("msg_label", _u8p), ("slicer_neg", _u8p),
+                ("cha_label_mirror", _u8p), ("msg_label_mirror", _u8p)]
+
+    @classmethod
+    def from_table(cls, t):
+        """From the dict Codec.channel_cells returns (thr uint64; cha, msg, neg, cha_m, msg_m uint8, one entry per cell).  The
+        arrays stay alive on the instance."""
+        keep = [np.ascontiguousarray(t["thr"], np.uint64)] + [np.ascontiguousarray(t[k], np.uint8) for k in ("cha", "msg", "neg", "cha_m", "msg_m")]
+        cells = cls(len(keep[1]), keep[0].ctypes.data_as(_u64p), *[a.ctypes.data_as(_u8p) for a in keep[1:]])
+        cells._keep = keep
+        return cells
+
+
+class _ccp(C.POINTER(ChannelCells)):
+    """POINTER(ChannelCells) that also takes byref() of a caller's own Structure with the same field types.  Callers written before
+    ChannelCells existed declared the struct themselves -- the tests of the commit before this class among them, which every change
+    here is held against -- and must keep running against this package."""
+
+    @classmethod
+    def from_param(cls, obj):
+        s = getattr(obj, "_obj", None)
+        if isinstance(s, C.Structure) and not isinstance(s, ChannelCells) and [t for _, t in s._fields_] == [t for _, t in ChannelCells._fields_]:
+            return C.byref(ChannelCells.from_buffer(s))
+        return C.POINTER(ChannelCells).from_param(obj)
+
+
+# every function include/*.h declares -> (result, arguments)
 _SIGNATURES = {
     "lutldpc_decoder_encode_packed": (C.c_int, [_vp, C.POINTER(EncodeIO), _vp, C.c_int, _vp]),
     "lutldpc_decoder_decode_llr_packed": (C.c_int, [_vp, C.POINTER(LlrIO), _vp, C.c_int, _vp, _vp, _vp, _vp]),
@@ -100,37 +130,19 @@ _SIGNATURES = {
     "lutldpc_selftest_jit_source": (C.c_int64, [_vp, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int64, C.c_int]),
     "lutldpc_selftest_resident_source": (C.c_int64, [_vp, C.c_int, C.c_char_p, C.c_int64, C.c_int, C.POINTER(C.c_int32)]),
     "lutldpc_check_stream": (C.c_int, [C.c_uint32]),
-    "lutldpc_decoder_set_generator": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
+    "lutldpc_decoder_set_generator": (C.c_int, [_vp, C.c_int, C.c_int, _u64p]),
     "lutldpc_decoder_encode_random": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p]),
-    "lutldpc_decoder_sim_batch_random": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, _ip, _u8p, _u8p]),
+    "lutldpc_decoder_sim_batch": (C.c_int, [_vp, _ccp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p, C.c_int, _ip, _u8p, _u8p]),
+    "lutldpc_decoder_sample_labels": (C.c_int, [_vp, _ccp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p, _u8p, _u8p]),
+    "lutldpc_decoder_sim_batch_random": (C.c_int, [_vp, _ccp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, _ip, _u8p, _u8p]),
     "lutldpc_decoder_set_edge_groups": (C.c_int, [_vp, _ip, C.c_int]),
     "lutldpc_decoder_histogram_shape": (C.c_int, [_vp, C.c_int, _ip]),
     "lutldpc_decoder_histogram_batch": (C.c_int, [_vp, _u8p, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, _ip, _i64p, C.c_int64, _ip]),
-    "lutldpc_decoder_sim_batch_histogram": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p, C.c_int, C.c_int, C.c_int, C.c_int,
+    "lutldpc_decoder_sim_batch_histogram": (C.c_int, [_vp, _ccp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                       _i64p, C.c_int64, _ip]),
     "lutldpc_decoder_events_batch": (C.c_int, [_vp, _u8p, _u8p, _u8p, C.c_int, C.c_int, _u8p, _ip, _evp]),
-    "lutldpc_decoder_sim_batch_events": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p, C.c_int, C.c_int, _ip, _evp]),
-}
-for _name, (_res, _args) in _SIGNATURES.items():
-    if hasattr(lib, _name):
-        _fn = getattr(lib, _name)
-        _fn.restype, _fn.argtypes = _res, _args
-
-
-def last_error() -> str:
-    return lib.lutldpc_last_error().decode()
-
-
-def check(rc: int) -> None:
-    if rc != OK:
-        raise LutLdpcError(rc, last_error())
-
-
-def device_count() -> int:
-    return lib.lutldpc_device_count()
-
-# ---- host mirror (include/lut_ldpc_host.h) ---------------------------------------------------
-_HOST_SIGNATURES = {
+    "lutldpc_decoder_sim_batch_events": (C.c_int, [_vp, _ccp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p, C.c_int, C.c_int, _ip, _evp]),
+    # ---- host mirror (include/lut_ldpc_host.h)
     "lutldpc_codec_create": (C.c_int, [_cp, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "lutldpc_codec_load": (C.c_int, [_cp, C.c_int, C.POINTER(_vp)]),
     "lutldpc_codec_save": (C.c_int, [_vp, _cp]),
@@ -155,14 +167,6 @@ _HOST_SIGNATURES = {
     "lutldpc_codec_encode": (C.c_int, [_vp, _u8p, _u8p]),
     "lutldpc_de_threshold": (C.c_int, [_ip, _dp, C.c_int, _ip, _dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _cp, _cp, C.c_double,
                                        C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int, _dp]),
-}
-for _name, (_res, _args) in _HOST_SIGNATURES.items():
-    if hasattr(lib, _name):
-        _fn = getattr(lib, _name)
-        _fn.restype, _fn.argtypes = _res, _args
-
-_u64p, _i64p = C.POINTER(C.c_uint64), C.POINTER(C.c_int64)
-_SIM_SIGNATURES = {
     "lutldpc_codec_sim_batch": (C.c_int, [_vp, C.c_double, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, _ip]),
     "lutldpc_codec_sample_labels": (C.c_int, [_vp, C.c_double, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, _u8p, _u8p, _u8p]),
     "lutldpc_codec_encode_random": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p]),
@@ -184,8 +188,29 @@ _SIM_SIGNATURES = {
     "lutldpc_bersim_error_events": (C.c_int, [_vp, C.c_int, C.c_int64, C.c_int, _evp]),
     "lutldpc_bersim_decoder": (_vp, [_vp]),
     "lutldpc_bersim_code": (C.c_int, [_vp, _ip, _ip, _ip, _ip, _ip]),
+    # ---- [BP] comparison decoder (include/lut_ldpc_bp.h)
+    "lutldpc_bp_create": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "lutldpc_bp_destroy": (C.c_int, [_vp]),
+    "lutldpc_bp_set_exit_conditions": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
+    "lutldpc_bp_logexp_table": (C.c_int, [_vp, _ip, C.c_int]),
+    "lutldpc_bp_decode_llr_batch": (C.c_int, [_vp, _dp, C.c_int, _u8p, _ip, _ip]),
+    "lutldpc_bp_decode_qllr_batch": (C.c_int, [_vp, _ip, C.c_int, _u8p, _ip, _ip]),
+    "lutldpc_awgn_llr": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_double, _u8p, _dp, _ip]),
 }
-for _name, (_res, _args) in _SIM_SIGNATURES.items():
-    if hasattr(lib, _name):
+for _name, (_res, _args) in _SIGNATURES.items():
+    if hasattr(lib, _name):          # (a library selected with LUTLDPC_LIB may be an older build that lacks an entry)
         _fn = getattr(lib, _name)
         _fn.restype, _fn.argtypes = _res, _args
+
+
+def last_error() -> str:
+    return lib.lutldpc_last_error().decode()
+
+
+def check(rc: int) -> None:
+    if rc != OK:
+        raise LutLdpcError(rc, last_error())
+
+
+def device_count() -> int:
+    return lib.lutldpc_device_count()

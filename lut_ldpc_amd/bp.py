@@ -8,18 +8,7 @@ import numpy as np
 
 from ._capi import lib, check
 
-_vp, _ip, _u8p, _dp = C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint8), C.POINTER(C.c_double)
-for _name, (_res, _args) in {
-    "lutldpc_bp_create": (C.c_int, [C.c_int, C.c_int, _ip, _ip, _ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
-    "lutldpc_bp_destroy": (C.c_int, [_vp]),
-    "lutldpc_bp_set_exit_conditions": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int]),
-    "lutldpc_bp_logexp_table": (C.c_int, [_vp, _ip, C.c_int]),
-    "lutldpc_bp_decode_llr_batch": (C.c_int, [_vp, _dp, C.c_int, _u8p, _ip, _ip]),
-    "lutldpc_bp_decode_qllr_batch": (C.c_int, [_vp, _ip, C.c_int, _u8p, _ip, _ip]),
-    "lutldpc_awgn_llr": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_double, _u8p, _dp, _ip]),
-}.items():
-    _fn = getattr(lib, _name)
-    _fn.restype, _fn.argtypes = _res, _args
+_vp = C.c_void_p
 
 
 def _p(a, t):

@@ -23,6 +23,57 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
+def _opt(a, t):
+    return _p(a, t) if a is not None else None
+
+
+def _out(a, rows, width, dtype, what):
+    """An output [rows, width] of a batch entry: a new array for None, or the caller's own (C-contiguous, `rows` rows or more)."""
+    if a is None:
+        return np.empty((rows, width), dtype)
+    if not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous or a.ndim != 2 or a.shape[0] < rows or a.shape[1] != width:
+        raise ValueError(f"{what} must be a C-contiguous {np.dtype(dtype).name} array of at least {(rows, width)}")
+    return a
+
+
+def _cells(cells):
+    return cells if isinstance(cells, _capi.ChannelCells) else _capi.ChannelCells.from_table(cells)
+
+
+class _Side:
+    """Where the [B, width] input of a packed entry lives -- a numpy array in host memory or a torch tensor on the device -- with its
+    row stride and pointer, and the outputs allocated on the same side."""
+
+    def __init__(self, x):
+        self.on_device = not isinstance(x, np.ndarray) and hasattr(x, "data_ptr")
+
+    def place(self, x, width, at_least):
+        """Row stride of x (a tensor is read in place, its current stream synchronised first; an array is made contiguous)."""
+        B = int(x.shape[0])
+        if self.on_device:
+            import torch
+            if x.stride(1) != 1 or (B > 1 and x.stride(0) < width):
+                raise ValueError("a tensor needs a contiguous last dimension and a row stride of at least " + at_least)
+            self.src, self.stride, self.dev = x, int(x.stride(0)) if B > 1 else width, x.device
+            torch.cuda.current_stream(self.dev).synchronize()
+        else:
+            self.src, self.stride = np.ascontiguousarray(x), width
+
+    def empty(self, shape, dtype, want=True):
+        """uint8 / int32 / uint32 (a tensor of words is int32: the same 32 bits)"""
+        if not want:
+            return None
+        if self.on_device:
+            import torch
+            return torch.empty(shape, dtype=torch.uint8 if dtype == np.uint8 else torch.int32, device=self.dev)
+        return np.empty(shape, dtype)
+
+    def ptr(self, a):
+        if a is None:
+            return None
+        return C.c_void_p(a.data_ptr() if self.on_device else a.ctypes.data)
+
+
 MODES = {"all": 0, "active": 1}      # counting modes of the message histograms (include/lut_ldpc_hip.h)
 
 
@@ -55,12 +106,21 @@ class Decoder:
         self.max_iters = int(max_iters)
 
     # ---- host buffers ---------------------------------------------------------------------
-    def lut_decode_batch(self, cha: np.ndarray, msg0: np.ndarray):
+    def _label_rows(self, cha, msg0, sent=None):
+        """cha, msg0 and the optional sent bits as C-contiguous uint8 [B, nvar]: (cha, msg0, sent, B, nvar)."""
         cha = np.ascontiguousarray(cha, np.uint8)
         msg0 = np.ascontiguousarray(msg0, np.uint8)
         B, N = cha.shape
         if N != self.nvar or msg0.shape != cha.shape:
             raise ValueError("cha/msg0 must be [B, nvar]")
+        if sent is not None:
+            sent = np.ascontiguousarray(sent, np.uint8)
+            if sent.shape != cha.shape:
+                raise ValueError("sent must be [B, nvar]")
+        return cha, msg0, sent, B, N
+
+    def lut_decode_batch(self, cha: np.ndarray, msg0: np.ndarray):
+        cha, msg0, _, B, N = self._label_rows(cha, msg0)
         out = np.empty((B, N), np.uint8)
         iters = np.empty(B, np.int32)
         check(lib.lutldpc_decoder_decode_batch(self._h, _p(cha, C.c_uint8), _p(msg0, C.c_uint8), B, _p(out, C.c_uint8),
@@ -125,29 +185,25 @@ class Decoder:
         n_dumps, n_groups, nq, _ = self.histogram_shape(level)
         return np.zeros((n_dumps, n_groups, 2, int(n_labels or nq)), np.int64)
 
+    def _hist(self, hist, level, n_labels):
+        hist = self.new_histogram(level, n_labels) if hist is None else hist
+        if hist.dtype != np.int64 or not hist.flags.c_contiguous or hist.ndim != 4:
+            raise ValueError("hist must be a C-contiguous int64 array [dump, group, 2, label]")
+        return hist
+
     def message_histogram(self, cha, msg0, sent=None, level=3, mode="all", n_labels=None, hist=None, decode=True):
         """Counts the edge-message labels of every dump of output_verbosity = level on the device: hist[dump, group, sent bit, label]
         (int64), ADDED into `hist` when given.  mode "all": every frame at every dump (exit tests off); "active": the dumps the
         reference would have printed under the decoder's exit conditions.  sent: [B, nvar] sent bits or None (all-zero codeword).
         Returns (hist, bits, iters) with decode=True (the decode of the same call), else hist alone."""
-        cha = np.ascontiguousarray(cha, np.uint8); msg0 = np.ascontiguousarray(msg0, np.uint8)
-        B, N = cha.shape
-        if N != self.nvar or msg0.shape != cha.shape:
-            raise ValueError("cha/msg0 must be [B, nvar]")
-        if sent is not None:
-            sent = np.ascontiguousarray(sent, np.uint8)
-            if sent.shape != cha.shape:
-                raise ValueError("sent must be [B, nvar]")
-        hist = self.new_histogram(level, n_labels) if hist is None else hist
-        if hist.dtype != np.int64 or not hist.flags.c_contiguous or hist.ndim != 4:
-            raise ValueError("hist must be a C-contiguous int64 array [dump, group, 2, label]")
+        cha, msg0, sent, B, N = self._label_rows(cha, msg0, sent)
+        hist = self._hist(hist, level, n_labels)
         bits = np.empty((B, N), np.uint8) if decode else None
         iters = np.empty(B, np.int32) if decode else None
         got = C.c_int32()
-        check(lib.lutldpc_decoder_histogram_batch(self._h, _p(cha, C.c_uint8), _p(msg0, C.c_uint8), _p(sent, C.c_uint8) if sent is not None else None, B,
+        check(lib.lutldpc_decoder_histogram_batch(self._h, _p(cha, C.c_uint8), _p(msg0, C.c_uint8), _opt(sent, C.c_uint8), B,
                                                   int(level), MODES[mode] if isinstance(mode, str) else int(mode), hist.shape[3],
-                                                  _p(bits, C.c_uint8) if decode else None, _p(iters, C.c_int32) if decode else None,
-                                                  _p(hist, C.c_int64), hist.size, C.byref(got)))
+                                                  _opt(bits, C.c_uint8), _opt(iters, C.c_int32), _p(hist, C.c_int64), hist.size, C.byref(got)))
         assert got.value == hist.shape[0]
         return (hist, bits, iters) if decode else hist
 
@@ -160,21 +216,89 @@ class Decoder:
         (iteration code < 0), "undetected" (wrong, but code >= 0).  profiles: None, True (new arrays) or (node_errors int64 [nvar],
         check_fails int64 [nchk]) to add into.  decode=True returns (events, bits, iters)."""
         from .err_events import _Request
-        cha = np.ascontiguousarray(cha, np.uint8); msg0 = np.ascontiguousarray(msg0, np.uint8)
-        B, N = cha.shape
-        if N != self.nvar or msg0.shape != cha.shape:
-            raise ValueError("cha/msg0 must be [B, nvar]")
-        if sent is not None:
-            sent = np.ascontiguousarray(sent, np.uint8)
-            if sent.shape != cha.shape:
-                raise ValueError("sent must be [B, nvar]")
+        cha, msg0, sent, B, N = self._label_rows(cha, msg0, sent)
         rq = _Request(self.nvar, self.nchk, select, max_frames, max_pos, max_chk, profiles)
         bits = np.empty((B, N), np.uint8) if decode else None
         iters = np.empty(B, np.int32) if decode else None
-        check(lib.lutldpc_decoder_events_batch(self._h, _p(cha, C.c_uint8), _p(msg0, C.c_uint8), _p(sent, C.c_uint8) if sent is not None else None, B,
-                                               int(self.nvar - self.nchk if k_info is None else k_info), _p(bits, C.c_uint8) if decode else None,
-                                               _p(iters, C.c_int32) if decode else None, C.byref(rq.c)))
+        check(lib.lutldpc_decoder_events_batch(self._h, _p(cha, C.c_uint8), _p(msg0, C.c_uint8), _opt(sent, C.c_uint8), B,
+                                               int(self.nvar - self.nchk if k_info is None else k_info), _opt(bits, C.c_uint8), _opt(iters, C.c_int32),
+                                               C.byref(rq.c)))
         return (rq.result(), bits, iters) if decode else rq.result()
+
+    # ---- Monte-Carlo front end on the device: cell sampler, random codewords, error counters --------------------------------
+    #      cells: a _capi.ChannelCells or the dict Codec.channel_cells returns; codewords: host [B, nvar] sent bits (bit 0 of a byte
+    #      counts) or None for the all-zero codeword; outputs: new arrays, or the caller's own with at least B rows
+    def set_generator(self, K, R, rows):
+        """The generator of the device encoder: R rows of ceil(K/64) uint64 words, K + R = nvar (replaces an earlier one)."""
+        rows = np.ascontiguousarray(rows, np.uint64)
+        if K < 1 or R < 0 or rows.size != R * ((K + 63) // 64):
+            raise ValueError("rows must hold R rows of ceil(K/64) uint64 words")
+        buf = rows if R else np.zeros(1, np.uint64)                 # (R = 0: no row is read, the pointer must not be null)
+        check(lib.lutldpc_decoder_set_generator(self._h, int(K), int(R), _p(buf, C.c_uint64)))
+
+    def encode_random(self, seed, stream, frame0, B, fetch=True, out=None):
+        """The random codewords of frames frame0 .. frame0+B-1, uint8 [B, nvar]; fetch=False keeps them on the device only."""
+        cw = _out(out, B, self.nvar, np.uint8, "out") if fetch else None
+        check(lib.lutldpc_decoder_encode_random(self._h, int(seed), int(stream), int(frame0), int(B), _opt(cw, C.c_uint8)))
+        return cw
+
+    def _codewords(self, codewords, B):
+        if codewords is None:
+            return None
+        cw = np.ascontiguousarray(codewords, np.uint8)
+        if cw.shape != (B, self.nvar):
+            raise ValueError("codewords must be [B, nvar]")
+        return cw
+
+    def sample_labels(self, cells, seed, stream, frame0, B, codewords=None, cha=None, msg=None):
+        """(cha, msg0) as the sampler makes them for those frames."""
+        cells, cw = _cells(cells), self._codewords(codewords, B)
+        cha, msg = _out(cha, B, self.nvar, np.uint8, "cha"), _out(msg, B, self.nvar, np.uint8, "msg")
+        check(lib.lutldpc_decoder_sample_labels(self._h, C.byref(cells), int(seed), int(stream), int(frame0), int(B), _opt(cw, C.c_uint8),
+                                                _p(cha, C.c_uint8), _p(msg, C.c_uint8)))
+        return cha, msg
+
+    def sim_batch(self, cells, seed, stream, frame0, B, k_info, codewords=None, random=False, frame_stats=None, cha_out=None, bits_out=None):
+        """Sampler + decode + counters: frame_stats int32 [B, 4] = {iteration code, frame error, data bit errors among the first k_info
+        bits, uncoded errors}.  random=True: over the codewords of the device encoder (lutldpc_decoder_sim_batch_random).  Returns
+        (frame_stats, cha_out, bits_out); the sampled channel labels and the decided bits only where cha_out / bits_out is True (a new
+        array) or an array to fill, else None."""
+        cells, cw = _cells(cells), self._codewords(codewords, B)
+        stats = _out(frame_stats, B, 4, np.int32, "frame_stats")
+        cha = None if cha_out is None else _out(None if cha_out is True else cha_out, B, self.nvar, np.uint8, "cha_out")
+        bits = None if bits_out is None else _out(None if bits_out is True else bits_out, B, self.nvar, np.uint8, "bits_out")
+        head = (self._h, C.byref(cells), int(seed), int(stream), int(frame0), int(B))
+        tail = (int(k_info), _p(stats, C.c_int32), _opt(cha, C.c_uint8), _opt(bits, C.c_uint8))
+        if random:
+            if cw is not None:
+                raise ValueError("random=True takes the codewords of the device encoder, not the caller's")
+            check(lib.lutldpc_decoder_sim_batch_random(*head, *tail))
+        else:
+            check(lib.lutldpc_decoder_sim_batch(*head, _opt(cw, C.c_uint8), *tail))
+        return stats, cha, bits
+
+    def sim_batch_histogram(self, cells, seed, stream, frame0, B, codewords=None, device_codewords=False, level=3, mode="all", n_labels=None, hist=None):
+        """message_histogram of the frames sim_batch sends (device_codewords=True: sim_batch with random=True), added into `hist`."""
+        cells, cw = _cells(cells), self._codewords(codewords, B)
+        hist = self._hist(hist, level, n_labels)
+        got = C.c_int32()
+        check(lib.lutldpc_decoder_sim_batch_histogram(self._h, C.byref(cells), int(seed), int(stream), int(frame0), int(B), _opt(cw, C.c_uint8),
+                                                      int(device_codewords), int(level), MODES[mode] if isinstance(mode, str) else int(mode),
+                                                      hist.shape[3], _p(hist, C.c_int64), hist.size, C.byref(got)))
+        assert got.value == hist.shape[0]
+        return hist
+
+    def sim_batch_events(self, cells, seed, stream, frame0, B, k_info=None, codewords=None, device_codewords=False, select="codeword", max_frames=1024,
+                         max_pos=64, max_chk=64, profiles=None, frame_stats=None):
+        """error_events of the frames sim_batch sends: (ErrorEvents, frame_stats)."""
+        from .err_events import _Request
+        cells, cw = _cells(cells), self._codewords(codewords, B)
+        rq = _Request(self.nvar, self.nchk, select, max_frames, max_pos, max_chk, profiles)
+        stats = _out(frame_stats, B, 4, np.int32, "frame_stats")
+        check(lib.lutldpc_decoder_sim_batch_events(self._h, C.byref(cells), int(seed), int(stream), int(frame0), int(B), _opt(cw, C.c_uint8),
+                                                   int(device_codewords), int(self.nvar - self.nchk if k_info is None else k_info),
+                                                   _p(stats, C.c_int32), C.byref(rq.c)))
+        return rq.result(), stats
 
     def decode_llr_batch(self, llr, qb_cha, qb_msg, mode=0, cha2msg_map=None):
         llr = np.ascontiguousarray(llr, np.float64)
@@ -205,8 +329,8 @@ class Decoder:
             raise ValueError("give either qb_msg (mode CONT) or cha2msg_map (mode QCHA)")
         if mp is not None and len(mp) != len(qc) + 1:
             raise ValueError("cha2msg_map must hold one entry per channel label")
-        on_device = not isinstance(llr, np.ndarray) and hasattr(llr, "data_ptr")
-        if on_device:
+        side = _Side(llr)
+        if side.on_device:
             import torch
             names = {torch.float64: _capi.LLR_F64, torch.float32: _capi.LLR_F32, torch.float16: _capi.LLR_F16, torch.int8: _capi.LLR_I8}
             if not llr.is_cuda:
@@ -227,30 +351,13 @@ class Decoder:
             want_labels = True
         B, N = int(llr.shape[0]), self.nvar
         count = N - int(first) if count is None else int(count)
-        W = max((count + 31) // 32, 0)
-        if on_device:
-            if llr.stride(1) != 1 or (B > 1 and llr.stride(0) < N):
-                raise ValueError("a tensor needs a contiguous last dimension and a row stride of at least nvar")
-            stride = int(llr.stride(0)) if B > 1 else N
-            dev = llr.device
-            torch.cuda.current_stream(dev).synchronize()
-            words = torch.empty((B, W), dtype=torch.int32, device=dev) if decode else None
-            iters = torch.empty(B, dtype=torch.int32, device=dev) if decode else None
-            cha = torch.empty((B, N), dtype=torch.uint8, device=dev) if want_labels else None
-            msg = torch.empty((B, N), dtype=torch.uint8, device=dev) if want_labels else None
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        else:
-            llr = np.ascontiguousarray(llr)
-            stride = N
-            words = np.empty((B, W), np.uint32) if decode else None
-            iters = np.empty(B, np.int32) if decode else None
-            cha = np.empty((B, N), np.uint8) if want_labels else None
-            msg = np.empty((B, N), np.uint8) if want_labels else None
-            ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None
-        io = _capi.LlrIO(dtype, int(on_device), stride, float(scale) if scale is not None else 0.0, _p(qc, C.c_double), len(qc),
-                         _p(qm, C.c_double) if qm is not None else None, len(qm) if qm is not None else 0, 0 if qm is not None else 1,
-                         _p(mp, C.c_int32) if mp is not None else None, int(first), count, 1)
-        check(lib.lutldpc_decoder_decode_llr_packed(self._h, C.byref(io), ptr(llr), B, ptr(words), ptr(iters), ptr(cha), ptr(msg)))
+        side.place(llr, N, "nvar")
+        words, iters = side.empty((B, max((count + 31) // 32, 0)), np.uint32, decode), side.empty(B, np.int32, decode)
+        cha, msg = side.empty((B, N), np.uint8, want_labels), side.empty((B, N), np.uint8, want_labels)
+        io = _capi.LlrIO(dtype, int(side.on_device), side.stride, float(scale) if scale is not None else 0.0, _p(qc, C.c_double), len(qc),
+                         _opt(qm, C.c_double), len(qm) if qm is not None else 0, 0 if qm is not None else 1, _opt(mp, C.c_int32), int(first), count, 1)
+        check(lib.lutldpc_decoder_decode_llr_packed(self._h, C.byref(io), side.ptr(side.src), B, side.ptr(words), side.ptr(iters), side.ptr(cha),
+                                                    side.ptr(msg)))
         out = (words, iters) if decode else ()
         return out + (cha, msg) if want_labels else out
 
@@ -261,8 +368,8 @@ class Decoder:
         codeword bits first .. first+count-1 of every frame, one bit each, [B, ceil(count/32)] (packing.unpack_bits; count=None: up
         to nvar): a numpy uint32 array, or an int32 tensor on the tensor's device.  For a tensor the tensor's current stream is
         synchronised before the call and (sync=True) the decoder's stream before it returns."""
-        on_device = not isinstance(info_words, np.ndarray) and hasattr(info_words, "data_ptr")
-        if on_device:
+        side = _Side(info_words)
+        if side.on_device:
             import torch
             if not info_words.is_cuda:
                 raise ValueError("a torch tensor must live on the device; pass host words as a numpy array")
@@ -275,21 +382,10 @@ class Decoder:
             raise ValueError("info_words must be [B, W]")
         B, W = int(info_words.shape[0]), int(info_words.shape[1])
         count = self.nvar - int(first) if count is None else int(count)
-        Wout = max((count + 31) // 32, 0)
-        if on_device:
-            if info_words.stride(1) != 1 or (B > 1 and info_words.stride(0) < W):
-                raise ValueError("a tensor needs a contiguous last dimension and a row stride of at least its width")
-            stride = int(info_words.stride(0)) if B > 1 else W
-            torch.cuda.current_stream(info_words.device).synchronize()
-            out = torch.empty((B, Wout), dtype=torch.int32, device=info_words.device)
-            src, dst = C.c_void_p(info_words.data_ptr()), C.c_void_p(out.data_ptr())
-        else:
-            info_words = np.ascontiguousarray(info_words)
-            stride = W
-            out = np.empty((B, Wout), np.uint32)
-            src, dst = C.c_void_p(info_words.ctypes.data), C.c_void_p(out.ctypes.data)
-        io = _capi.EncodeIO(int(on_device), stride, int(first), count, int(bool(sync)))
-        check(lib.lutldpc_decoder_encode_packed(self._h, C.byref(io), src, B, dst))
+        side.place(info_words, W, "its width")
+        out = side.empty((B, max((count + 31) // 32, 0)), np.uint32)
+        io = _capi.EncodeIO(int(side.on_device), side.stride, int(first), count, int(bool(sync)))
+        check(lib.lutldpc_decoder_encode_packed(self._h, C.byref(io), side.ptr(side.src), B, side.ptr(out)))
         return out
 
     # ---- device buffers (raw pointers, e.g. torch.Tensor.data_ptr()) -------------------------

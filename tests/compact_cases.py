@@ -7,14 +7,11 @@ the short codes of the front-end, statistics, packed and LLR tests never reach i
 from __future__ import annotations
 
 import functools
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
 import frontend_cases as fc
-from helpers import awgn_labels, oracle_codec, product_decoder, write_ira_alist
-from oracle import oracle as orc
+from helpers import designed_codec, oracle_codec, planted_labels, product_decoder, write_ira_alist
 
 # ---- the code: the dual-diagonal code of tests/test_05 and tests/test_55 (check degree 8: bucket 0 of the fused kernel, chain-rich)
 K, M, DV, ITERS, SIGMA, SNR_OFFSET = 840, 420, 3, 16, 0.62, 0.25
@@ -64,21 +61,11 @@ LABEL_SEED = {B: B for B in SIZES}
 SEED, STREAM, F0 = 2 ** 40 + 60, 6, 2 ** 32 - 9
 SOURCES = ("zero", "codewords")            # the all-zero codeword / codewords of the generator below
 
-_tmp = None
 
-
-@functools.lru_cache(maxsize=None)
 def codec():
     """The code, designed with the oracle (as _ira_codec of tests/test_05)."""
-    global _tmp
-    _tmp = _tmp or tempfile.TemporaryDirectory(prefix="compact_cases_")
-    path = Path(_tmp.name) / "ira.alist"
-    n, _ = write_ira_alist(path, K, M, DV, seed=K + ITERS)
-    assert n == N
-    cd = orc.Codec(orc.Code(path), skip_rank=True)
-    cd.set_rank(M)
-    cd.rate = 1.0 - M / N
-    cd.design_luts(sigma2=SIGMA ** 2, max_iters=ITERS, nq_msg=np.full(ITERS, 16, np.int32), nq_cha=16)
+    cd = designed_codec("compact-ira", lambda path: write_ira_alist(path, K, M, DV, seed=K + ITERS), sigma=SIGMA, max_iters=ITERS, nq_msg=16)
+    assert cd.code.nvar == N
     return cd
 
 
@@ -94,13 +81,7 @@ def planted(B):
 def labels(B):
     """Channel and initial-message labels of a batch, three noise-free frames planted (first, middle, last: they pass the test on the
     channel decisions, so the pisc exit and hard_from_labels_masked_kernel have work).  Shared read-only."""
-    cd = codec()
-    cha, msg, _ = awgn_labels(cd, B, snr(), seed=LABEL_SEED[B])
-    cha[planted(B)] = cd.nq_cha - 1
-    msg[planted(B)] = cd.nq_msg[0] - 1
-    cha.setflags(write=False)
-    msg.setflags(write=False)
-    return cha, msg
+    return planted_labels(codec(), B, snr(), LABEL_SEED[B], noise_free=planted(B))
 
 
 ORACLE = {}      # (labels id, frames, psc, pisc) -> (bits, iteration codes): the oracle decodes each batch once per exit mode
@@ -251,14 +232,8 @@ def fits_codec():
 
 @functools.lru_cache(maxsize=None)
 def fits_labels(which):
-    cd = fits_codec()
     B = FITS_B[which]
-    cha, msg, _ = awgn_labels(cd, B, FITS_SNR, seed=B)
-    cha[planted(B)] = cd.nq_cha - 1
-    msg[planted(B)] = cd.nq_msg[0] - 1
-    cha.setflags(write=False)
-    msg.setflags(write=False)
-    return cha, msg
+    return planted_labels(fits_codec(), B, FITS_SNR, B, noise_free=planted(B))
 
 
 @functools.lru_cache(maxsize=None)

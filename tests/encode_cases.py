@@ -178,12 +178,11 @@ def loop_llr_magnitude(qb_cha):
 def loop_reference():
     """The loop-back case with the oracle alone: the codewords of real_reference(LOOP_CODE) sent as LLR = +-L (float32), quantised
     and decoded by the oracle with psc on.  dict: L, the data words, the decided data words and the iteration codes."""
+    from helpers import design
     from oracle import oracle as orc
     ref = real_reference(LOOP_CODE)
     kw = REAL_CODES[LOOP_CODE][1]
-    oc =orc.Codec(orc.Code(graph=ref["graph"]), skip_rank=True)
-    oc.set_rank(ref["R"])
-    oc.design_luts(sigma2=kw["sigma2"], max_iters=kw["max_iters"], nq_msg=np.full(kw["max_iters"], 16, np.int32), nq_cha=16)
+    oc = design(orc.Code(graph=ref["graph"]), ref["R"], kw["sigma2"], kw["max_iters"], 16, nq_cha=16)
     oc.set_exit_conditions(kw["max_iters"], True, False)
     L = loop_llr_magnitude(oc.qb_cha)
     llr = (L * (1.0 - 2.0 * ref["cw"])).astype(np.float32)

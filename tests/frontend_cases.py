@@ -10,8 +10,6 @@ thresholds and every cell that should be hit is hit by construction; their label
 from __future__ import annotations
 
 import functools
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
@@ -230,27 +228,15 @@ HANDLES = {
     "n33": ("n33", {}, 512),
     "n10000": ("reg36_n10000_q4", {}, 512),                     # (only for the generator at the LDS limit)
 }
-_tmp = None
 
 
-@functools.lru_cache(maxsize=None)
 def codec(code):
     """The oracle-designed code of a handle."""
-    from helpers import oracle_codec, write_degree_alist
-    from oracle import oracle as orc
+    from helpers import designed_codec, oracle_codec, write_degree_alist
     if code not in SYNTHETIC:
         return oracle_codec(code)
-    global _tmp
-    _tmp = _tmp or tempfile.TemporaryDirectory(prefix="frontend_cases_")
     vdeg, cdeg, sig = SYNTHETIC[code]
-    path = Path(_tmp.name) / f"{code}.alist"
-    write_degree_alist(path, vdeg, cdeg, seed=GRAPH_SEED)
-    N, M = sum(vdeg.values()), sum(cdeg.values())
-    cd = orc.Codec(orc.Code(path), skip_rank=True)
-    cd.set_rank(M)
-    cd.rate = 1.0 - M / N
-    cd.design_luts(sigma2=sig ** 2, max_iters=ITERS, nq_msg=np.full(ITERS, 16, np.int32), nq_cha=16)
-    return cd
+    return designed_codec("frontend-" + code, lambda path: write_degree_alist(path, vdeg, cdeg, seed=GRAPH_SEED), sigma=sig, max_iters=ITERS, nq_msg=16)
 
 
 def batch_size(kind, T):

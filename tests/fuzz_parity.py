@@ -6,7 +6,7 @@ import os, pathlib, sys, tempfile
 import numpy as np
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT)); sys.path.insert(0, str(ROOT / "tests"))   # (this file lives in tests/: only tests may use the oracle)
-from helpers import awgn_labels, compare, product_decoder, write_degree_alist, write_random_alist     # noqa: E402
+from helpers import awgn_labels, compare, design, product_decoder, write_degree_alist, write_random_alist     # noqa: E402
 from oracle import oracle as orc                                                   # noqa: E402
 
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 20
@@ -97,7 +97,6 @@ for c in range(cases):
         bad += 0 if okc else 1
         print(f"case {c}: BP N={N} M={M} dv={sorted(set(dv.tolist()))} dc={sorted(set(dc.tolist()))} d={dpar} B={Bb} iters<={I + 8} {'ok' if okc else 'MISMATCH'}, return codes with the syndrome test {codes[:8]}", flush=True)
         continue
-    cd = orc.Codec(code, skip_rank=True); cd.set_rank(M); cd.rate = 1.0 - M / N
     # one case in four each: check-node LUT trees instead of min-sum, a message alphabet that shrinks along the iterations (halved
     # from a random iteration on, two labels in the last one), LUT stages reused over several iterations (src/LDPC_Code_LUT.cpp:120-169)
     extra = {}
@@ -113,7 +112,7 @@ for c in range(cases):
             if nq_vec[i] != nq_vec[i - 1] or (i + 1 < I and nq_vec[i + 1] != nq_vec[i]):
                 reuse[i] = 0
         extra["reuse_vec"] = reuse.tolist()
-    cd.design_luts(sigma2=sig ** 2, max_iters=I, nq_msg=nq_vec, nq_cha=nqc, **extra)
+    cd = design(code, M, sig ** 2, I, nq_vec, nq_cha=nqc, **extra)
     snr = -10 * np.log10(2 * cd.rate * sig * sig) + snr_off
     cha, msg, _ = awgn_labels(cd, B, snr, seed=c)
     if COMPACT:                                                # a few noise-free frames: they pass the test on the channel decisions

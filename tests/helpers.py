@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import functools
 import re
+import tempfile
 import zlib
 from pathlib import Path
 
@@ -62,26 +63,87 @@ CONFIGS = {
 }
 
 
+def design(code, rank, sigma2, max_iters, nq_msg, **design_kw):
+    """An oracle codec of `code` with its rank and rate set and the LUTs designed; nq_msg: one alphabet size, or one per iteration."""
+    cd = orc.Codec(code, skip_rank=True)
+    cd.set_rank(rank)
+    cd.rate = 1.0 - rank / code.nvar
+    nq = np.full(max_iters, nq_msg, np.int32) if np.isscalar(nq_msg) else np.asarray(nq_msg, np.int32)
+    cd.design_luts(sigma2=sigma2, max_iters=max_iters, nq_msg=nq, **design_kw)
+    return cd
+
+
 @functools.lru_cache(maxsize=None)
 def oracle_codec(name: str):
     """Load the alist and design the LUTs with the oracle (cached per test session)."""
     alist, kw = CONFIGS[name]
     kw = dict(kw)
     code = orc.Code(CODES / f"{alist}.alist")
-    cd = orc.Codec(code, skip_rank=True)
     rank = kw.pop("rank", code.nchk)
-    cd.set_rank(rank)
-    max_iters = kw.pop("max_iters")
-    nq = kw.pop("nq_msg")
-    nq_msg = np.full(max_iters, nq, np.int32) if np.isscalar(nq) else np.asarray(nq, np.int32)
     snr = kw.pop("design_snr_db", None)
     sigma2 = kw.pop("sigma2")
     if sigma2 is None:   # src/LDPC_BER_Sim.cpp:482
         rate = 1.0 - rank / code.nvar
         sigma2 = 10 ** (-snr / 10) / (2 * rate)
-    cd.design_luts(sigma2=sigma2, max_iters=max_iters, nq_msg=nq_msg, **kw)
-    cd.rate = 1.0 - rank / code.nvar
+    return design(code, rank, sigma2, kw.pop("max_iters"), kw.pop("nq_msg"), **kw)
+
+
+_designed, _tmp = {}, None
+
+
+def designed_codec(key, write_graph, *, sigma, max_iters, nq_msg, nq_cha=16, rank=None, **design_kw):
+    """The oracle-designed code of a test, made once per session and key.  write_graph: a function that writes the alist to the path
+    it is given (in the session's temporary directory), or the path of an alist that exists.  N and M come from that graph; rank:
+    M unless given; the rate is 1 - rank / N; the design noise is sigma ** 2."""
+    global _tmp
+    if key not in _designed:
+        path = write_graph
+        if callable(write_graph):
+            _tmp = _tmp or tempfile.TemporaryDirectory(prefix="designed_codes_")
+            path = Path(_tmp.name) / f"{key}.alist"
+            write_graph(path)
+        code = orc.Code(path)
+        _designed[key] = design(code, code.nchk if rank is None else rank, sigma ** 2, max_iters, nq_msg, nq_cha=nq_cha, **design_kw)
+    return _designed[key]
+
+
+def product_codec(name, device=-1):
+    """The product's own design (C++ host mirror) of a configuration."""
+    import lut_ldpc_amd as L
+    alist, kw = CONFIGS[name]
+    kw = dict(kw)
+    rank = kw.pop("rank", None)
+    cd = L.Codec(CODES / f"{alist}.alist", known_rank=rank or (32400 if "64800" in alist else 0), device=device)
+    snr = kw.pop("design_snr_db", None)
+    sigma2 = kw.pop("sigma2")
+    if sigma2 is None:
+        sigma2 = 10 ** (-snr / 10) / (2 * cd.rate)
+    if "allow_deg1" in kw:
+        kw["allow_degree_one"] = kw.pop("allow_deg1")
+    cd.design_luts(sigma2=sigma2, **kw)
     return cd
+
+
+C5_TREES = "filename=" + str(TREES / "6_32_wide.ini")      # config 5 (ber.ini.regular.example)
+
+
+def c5_sigma2(rank=325, n=2048):
+    return 10 ** (-3.9 / 10) / (2 * (1.0 - rank / n))
+
+
+def oracle_graph(pcd):
+    """The oracle's Code of a product codec's (column-permuted) graph."""
+    dv, dc, cn = pcd.graph()
+    return orc.Code(graph=(pcd.nvar, pcd.nchk, dv, dc, cn))
+
+
+# the decode paths the packed and the soft-value entries run on: name -> (environment at creation, fields of describe() -> value)
+PACKED_PATHS = {
+    "resident": ({}, dict(resident=1)),
+    "streaming": ({"LUTLDPC_RESIDENT": "0"}, dict(resident=0, skewed_pipeline=1)),
+    "per_class": ({"LUTLDPC_RESIDENT": "0", "LUTLDPC_SKEW": "0"}, dict(resident=0, skewed_pipeline=0)),
+    "byte_rows": ({"LUTLDPC_PACK": "1"}, dict(pack=1, tile_frames=256)),       # nibble input into byte rows
+}
 
 
 def product_decoder(cd, device=0):
@@ -103,6 +165,36 @@ def awgn_labels(cd, B, snr_db, seed, mode=0):
     cha = orc.quant_nonlin(llr, cd.qb_cha)
     msg = orc.quant_nonlin(llr, cd.qb_msg) if mode == 0 else cd.cha2msg_map[cha].astype(np.uint8)
     return cha, msg, llr
+
+
+def planted_labels(cd, n, snr, seed, noise_free=(), mode=0, zero=()):
+    """awgn_labels of n frames with the frames `noise_free` planted: every label at its largest, so they pass the test on the channel
+    decisions; the frames `zero`: every label 0.  (cha, msg0), read-only: computed once per batch and shared."""
+    cha, msg, _ = awgn_labels(cd, n, snr, seed=seed, mode=mode)
+    free = np.asarray(list(noise_free), np.intp)
+    cha[free] = cd.nq_cha - 1
+    msg[free] = cd.nq_msg[0] - 1
+    cha[list(zero)] = 0
+    msg[list(zero)] = 0
+    cha.setflags(write=False)
+    msg.setflags(write=False)
+    return cha, msg
+
+
+ORACLE = {}      # key of a batch -> the cache `compare` takes: the oracle decodes a batch once per exit mode, all its decoders share the result
+
+
+def oracle_cache(key):
+    return ORACLE.setdefault(key, {})
+
+
+def same(got, want, what, u=None):
+    """Equal integer arrays, or the first mismatches (with u: the 64-bit uniform of the first one)."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = np.argwhere(got != want)
+    assert bad.size == 0, (what, f"{len(bad)} mismatches, first (frame, node)", bad[:4].tolist(), "got", got[tuple(bad[0])], "want", want[tuple(bad[0])],
+                           None if u is None else hex(int(u[tuple(bad[0])])))
 
 
 def compare(cd, dec, cha, msg, psc, pisc, max_iters=None, flat=False, cache=None):

@@ -6,13 +6,10 @@ from __future__ import annotations
 
 import functools
 import os
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
-from helpers import CONFIGS, awgn_labels, oracle_codec, product_decoder, resident_variant, write_random_alist
-from oracle import oracle as orc
+from helpers import CONFIGS, designed_codec, oracle_cache, oracle_codec, planted_labels, product_decoder, resident_variant, write_random_alist      # noqa: F401
 
 K = "LUTLDPC_RESIDENT_"
 VARIANT_KNOBS = ("U", "FLAG_REDUCE", "CN_PERSISTENT", "XCD", "FM", "WAVES_EU")
@@ -79,24 +76,14 @@ LIMIT_CASES = [
     ("cls12", "cls12", {}, 1), ("cls13", "cls13", {}, 0),
 ]
 
-_tmp = None
 
-
-@functools.lru_cache(maxsize=None)
 def codec(name):
     """oracle_codec for the named configurations, the oracle-designed synthetic code for the LIMITS."""
-    global _tmp
     if name in CONFIGS:
         return oracle_codec(name)
     N, M, dvc, dvp, nqc, nqm, I, sig, _, deg1 = LIMITS[name]
-    _tmp = _tmp or tempfile.TemporaryDirectory(prefix="resident_cases_")
-    path = Path(_tmp.name) / f"{name}.alist"
-    write_random_alist(path, N, M, dvc, np.asarray(dvp) / np.sum(dvp), seed=GRAPH_SEED)
-    cd = orc.Codec(orc.Code(path), skip_rank=True)
-    cd.set_rank(M)
-    cd.rate = 1.0 - M / N
-    cd.design_luts(sigma2=sig ** 2, max_iters=I, nq_msg=np.full(I, nqm, np.int32), nq_cha=nqc, allow_deg1=deg1)
-    return cd
+    return designed_codec("resident-" + name, lambda path: write_random_alist(path, N, M, dvc, np.asarray(dvp) / np.sum(dvp), seed=GRAPH_SEED),
+                          sigma=sig, max_iters=I, nq_msg=nqm, nq_cha=nqc, allow_deg1=deg1)
 
 
 def limit_snr(name):
@@ -108,21 +95,7 @@ def limit_snr(name):
 def labels(name, B, snr, seed=None):
     """Channel and initial-message labels of a batch with three noise-free frames planted (first, middle, last: they pass the
     test on the channel decisions).  Computed once per batch, shared read-only."""
-    cd = codec(name)
-    cha, msg, _ = awgn_labels(cd, B, snr, seed=B if seed is None else seed, mode=1 if name.startswith("c5") else 0)
-    for f in (0, B // 2, B - 1):
-        cha[f] = cd.nq_cha - 1
-        msg[f] = cd.nq_msg[0] - 1
-    cha.setflags(write=False)
-    msg.setflags(write=False)
-    return cha, msg
-
-
-ORACLE = {}      # code name -> helpers.compare cache: the oracle decodes a batch once per exit mode, all variants share the result
-
-
-def oracle_cache(name):
-    return ORACLE.setdefault(name, {})
+    return planted_labels(codec(name), B, snr, B if seed is None else seed, noise_free=(0, B // 2, B - 1), mode=1 if name.startswith("c5") else 0)
 
 
 def frame_groups(dec, B):

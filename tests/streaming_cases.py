@@ -8,13 +8,10 @@ a role ragged, and every code runs through every launch path that holds its degr
 from __future__ import annotations
 
 import functools
-import tempfile
-from pathlib import Path
 
 import numpy as np
 
-from helpers import awgn_labels, product_decoder, write_degree_alist, write_zigzag_runs_alist
-from oracle import oracle as orc
+from helpers import designed_codec, oracle_cache, planted_labels, product_decoder, write_degree_alist, write_zigzag_runs_alist      # noqa: F401
 from resident_cases import EXIT_MODES      # noqa: F401  (the three exit modes every case decodes in)
 
 # kernels_fast.hpp: the degree buckets of the fused kernel, leanest first
@@ -102,55 +99,29 @@ MANY_VDEG, MANY_CDEG, MANY_SIGMA, MANY_B, MANY_LABEL_SEED = {3: 594}, {d: 3 for 
 #      the oracle's iteration codes on the batch with both exit tests on (test_streaming_cases_cpu.py): code -> frames
 MANY_CODES = {-5: 32, 0: 2, 1: 20, 2: 166, 3: 180, 4: 114, 5: 86}
 
-_tmp = None
 
-
-@functools.lru_cache(maxsize=None)
 def codec(name):
     """The oracle-designed code of a case, its graph written once per session."""
-    global _tmp
-    _tmp = _tmp or tempfile.TemporaryDirectory(prefix="streaming_cases_")
-    path = Path(_tmp.name) / f"{name}.alist"
     if name in SWEEP:
         vdeg, cdeg, nqc, nqm, sig, _, deg1 = SWEEP[name]
-        write_degree_alist(path, vdeg, cdeg, seed=GRAPH_SEED)
-        N, M = sum(vdeg.values()), sum(cdeg.values())
-    else:
-        runs, dv_info, nqc, nqm, sig, _ = ZIGZAG[name]
-        N, M = write_zigzag_runs_alist(path, runs, dv_info, seed=GRAPH_SEED)
-        deg1 = False
-    cd = orc.Codec(orc.Code(path), skip_rank=True)
-    cd.set_rank(M)
-    cd.rate = 1.0 - M / N
-    cd.design_luts(sigma2=sig ** 2, max_iters=ITERS, nq_msg=np.full(ITERS, nqm, np.int32), nq_cha=nqc, allow_deg1=deg1)
-    return cd
+        return designed_codec("streaming-" + name, lambda path: write_degree_alist(path, vdeg, cdeg, seed=GRAPH_SEED),
+                              sigma=sig, max_iters=ITERS, nq_msg=nqm, nq_cha=nqc, allow_deg1=deg1)
+    runs, dv_info, nqc, nqm, sig, _ = ZIGZAG[name]
+    return designed_codec("streaming-" + name, lambda path: write_zigzag_runs_alist(path, runs, dv_info, seed=GRAPH_SEED),
+                          sigma=sig, max_iters=ITERS, nq_msg=nqm, nq_cha=nqc, allow_deg1=False)
 
 
-@functools.lru_cache(maxsize=None)
 def many_codec():
     """Section E: the code of 33 check classes, designed with the oracle."""
-    global _tmp
-    _tmp = _tmp or tempfile.TemporaryDirectory(prefix="streaming_cases_")
-    path = Path(_tmp.name) / "many.alist"
-    write_degree_alist(path, MANY_VDEG, MANY_CDEG, seed=GRAPH_SEED)
-    N, M = sum(MANY_VDEG.values()), sum(MANY_CDEG.values())
-    cd = orc.Codec(orc.Code(path), skip_rank=True)
-    cd.set_rank(M)
-    cd.rate = 1.0 - M / N
-    cd.design_luts(sigma2=MANY_SIGMA ** 2, max_iters=ITERS, nq_msg=np.full(ITERS, 16, np.int32), nq_cha=16)
-    return cd
+    return designed_codec("streaming-many", lambda path: write_degree_alist(path, MANY_VDEG, MANY_CDEG, seed=GRAPH_SEED),
+                          sigma=MANY_SIGMA, max_iters=ITERS, nq_msg=16)
 
 
 @functools.lru_cache(maxsize=None)
 def many_labels():
     """Section E: MANY_B frames at the design SNR (4.717 dB), frame 0 noise-free.  Shared read-only."""
     cd = many_codec()
-    cha, msg, _ = awgn_labels(cd, MANY_B, -10 * np.log10(2 * cd.rate * MANY_SIGMA ** 2), seed=MANY_LABEL_SEED)
-    cha[0] = cd.nq_cha - 1
-    msg[0] = cd.nq_msg[0] - 1
-    cha.setflags(write=False)
-    msg.setflags(write=False)
-    return cha, msg
+    return planted_labels(cd, MANY_B, -10 * np.log10(2 * cd.rate * MANY_SIGMA ** 2), MANY_LABEL_SEED, noise_free=[0])
 
 
 def snr(name):
@@ -162,21 +133,8 @@ def snr(name):
 def labels(name, n=B, quiet=0.0):
     """Channel and initial-message labels of the first n frames of the code's batch, three noise-free frames planted (first, middle,
     last: they pass the test on the channel decisions); quiet: that share of the frames noise-free as well.  Shared read-only."""
-    cd = codec(name)
-    cha, msg, _ = awgn_labels(cd, n, snr(name), seed=LABEL_SEED)
     free = [0, n // 2, n - 1] + np.flatnonzero(np.random.default_rng(LABEL_SEED).random(n) < quiet).tolist()
-    cha[free] = cd.nq_cha - 1
-    msg[free] = cd.nq_msg[0] - 1
-    cha.setflags(write=False)
-    msg.setflags(write=False)
-    return cha, msg
-
-
-ORACLE = {}      # code name -> helpers.compare cache: the oracle decodes a batch once per exit mode, all paths share the result
-
-
-def oracle_cache(name):
-    return ORACLE.setdefault(name, {})
+    return planted_labels(codec(name), n, snr(name), LABEL_SEED, noise_free=free)
 
 
 def degrees(name):

@@ -15,21 +15,15 @@ from helpers import awgn_labels, compare, oracle_codec, product_decoder
 pytestmark = pytest.mark.gpu
 
 
-def _ira_codec(tmp_path, K, M, dv, max_iters, sig):
-    from helpers import write_ira_alist
-    from oracle import oracle as orc
-    N, _ = write_ira_alist(tmp_path / "ira.alist", K, M, dv, seed=K + max_iters)
-    code = orc.Code(tmp_path / "ira.alist")
-    cd = orc.Codec(code, skip_rank=True)
-    cd.set_rank(M)
-    cd.rate = 1.0 - M / N
-    cd.design_luts(sigma2=sig ** 2, max_iters=max_iters, nq_msg=np.full(max_iters, 16, np.int32), nq_cha=16)
-    return cd
+def _ira_codec(K, M, dv, max_iters, sig):
+    from helpers import designed_codec, write_ira_alist
+    return designed_codec(f"test05-ira-K{K}-M{M}-dv{dv}-I{max_iters}-s{sig}", lambda path: write_ira_alist(path, K, M, dv, seed=K + max_iters),
+                          sigma=sig, max_iters=max_iters, nq_msg=16)
 
 
 @pytest.mark.parametrize("keep", ["1", "0"])
 @pytest.mark.parametrize("K,M,dv,bucket,sig", [(840, 420, 3, 0, 0.62), (1600, 400, 3, 1, 0.52)])
-def test_ira_code_chain_fusion_with_compaction(tmp_path, monkeypatch, K, M, dv, bucket, sig, keep):
+def test_ira_code_chain_fusion_with_compaction(monkeypatch, K, M, dv, bucket, sig, keep):
     """A dual-diagonal code (check degrees 8 and 14: first and middle bucket of the fused kernel), compaction forced on with a
     check point every second iteration and no cost margin (frames move several times per decode), nine and ten frame groups
     (halves of 5 + 4 / 5 + 5, ragged last group), both row flows (the frames that left keep their rows / drop them), all three
@@ -41,7 +35,7 @@ def test_ira_code_chain_fusion_with_compaction(tmp_path, monkeypatch, K, M, dv, 
     monkeypatch.setenv("LUTLDPC_COMPACT_FIRST", "2")
     monkeypatch.setenv("LUTLDPC_COMPACT_EVERY", "2")
     monkeypatch.setenv("LUTLDPC_COMPACT_MARGIN", "0")
-    cd = _ira_codec(tmp_path, K, M, dv, 16, sig)
+    cd = _ira_codec(K, M, dv, 16, sig)
     dec = product_decoder(cd)
     desc = dec.describe()
     assert desc["fused_bucket"] == bucket and desc["skewed_pipeline"] == 1 and desc["compaction"] == 1, desc
@@ -143,14 +137,9 @@ def test_dvbs2_as_shipped_equals_the_path_without_compaction(monkeypatch):
 def test_channel_alphabet_whose_half_is_not_a_power_of_two(nq_cha, resident, monkeypatch):
     """Nq_Cha = 12 / 6: `label < Nq_Cha/2` (src/LDPC_Code_LUT.cpp:275) is not a sign BIT of the label; the test on the channel
     decisions (pisc) must go through the SWAR compare, not the bit trick of the label-row syndrome kernel."""
-    from helpers import CODES
-    from oracle import oracle as orc
+    from helpers import CODES, designed_codec
     monkeypatch.setenv("LUTLDPC_RESIDENT", resident)
-    code = orc.Code(CODES / "rate0.50_dv03_dc06_N1000.alist")
-    cd = orc.Codec(code, skip_rank=True)
-    cd.set_rank(500)
-    cd.rate = 0.5
-    cd.design_luts(sigma2=0.80 ** 2, max_iters=8, nq_msg=np.full(8, 8, np.int32), nq_cha=nq_cha)
+    cd = designed_codec(f"test05-reg36-c{nq_cha}m8", CODES / "rate0.50_dv03_dc06_N1000.alist", sigma=0.80, max_iters=8, nq_msg=8, nq_cha=nq_cha)
     dec = product_decoder(cd)
     for B, snr in ((300, 10.5), (1100, 2.5)):
         cha, msg, _ = awgn_labels(cd, B, snr, seed=B)

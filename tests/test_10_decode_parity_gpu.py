@@ -173,20 +173,14 @@ def test_fewer_iterations_than_designed_is_rejected_unless_decision_set():
 
 
 @pytest.mark.parametrize("K,M,dv,bucket", [(1600, 400, 3, 1), (3600, 400, 3, 2), (840, 420, 3, 0), (1120, 420, 3, 3)])
-def test_chain_fusion_in_every_degree_bucket(tmp_path, K, M, dv, bucket, monkeypatch):
+def test_chain_fusion_in_every_degree_bucket(K, M, dv, bucket, monkeypatch):
     """(streaming kernels: LUTLDPC_RESIDENT=0 -- these small codes would otherwise be decoded out of LDS)
     Dual-diagonal codes with check degrees 14 (middle bucket), 29 (widest), 8 (first) and 10 (bucket 3): most zigzag nodes are updated
     inside the check pass in every bucket, one frame group and several, fixed work and early termination."""
-    from helpers import write_ira_alist
-    from oracle import oracle as orc
+    from helpers import designed_codec, write_ira_alist
     monkeypatch.setenv("LUTLDPC_RESIDENT", "0")
-    N, _ = write_ira_alist(tmp_path / "ira.alist", K, M, dv, seed=K)
-    code = orc.Code(tmp_path / "ira.alist")
-    cd = orc.Codec(code, skip_rank=True)
-    cd.set_rank(M)
-    cd.rate = 1.0 - M / N
     sig = {1: 0.52, 2: 0.40, 0: 0.62, 3: 0.57}[bucket]
-    cd.design_luts(sigma2=sig ** 2, max_iters=10, nq_msg=np.full(10, 16, np.int32), nq_cha=16)
+    cd = designed_codec(f"test10-ira-K{K}-M{M}-dv{dv}", lambda path: write_ira_alist(path, K, M, dv, seed=K), sigma=sig, max_iters=10, nq_msg=16)
     dec = product_decoder(cd)
     desc = dec.describe()
     assert desc["fused_bucket"] == bucket and desc["skewed_pipeline"] == 1, desc
@@ -239,21 +233,16 @@ FUZZ = [  # N, M, variable degrees, their shares, Nq_Cha, Nq_Msg, iterations, de
 
 @pytest.mark.parametrize("case", range(len(FUZZ)))
 @pytest.mark.parametrize("resident", ["1", "0"])
-def test_random_irregular_codes(tmp_path, case, resident, monkeypatch):
+def test_random_irregular_codes(case, resident, monkeypatch):
     """Random irregular graphs the build has never seen (several variable and check degree classes, check degrees that differ
     by one, wide and narrow checks, 3- and 4-bit alphabets): design with the oracle, decode through the default path, every
     bit and iteration code against the oracle in all three exit modes, ragged batch sizes."""
-    from helpers import write_random_alist
-    from oracle import oracle as orc
+    from helpers import designed_codec, write_random_alist
     monkeypatch.setenv("LUTLDPC_RESIDENT", resident)
     N, M, dvc, dvp, nqc, nqm, I, sig, B = FUZZ[case]
-    dv, dc = write_random_alist(tmp_path / "r.alist", N, M, dvc, dvp, seed=100 + case)
-    code = orc.Code(tmp_path / "r.alist")
-    assert len(set(dc.tolist())) >= 1 and code.nvar == N
-    cd = orc.Codec(code, skip_rank=True)
-    cd.set_rank(M)
-    cd.rate = 1.0 - M / N
-    cd.design_luts(sigma2=sig ** 2, max_iters=I, nq_msg=np.full(I, nqm, np.int32), nq_cha=nqc)
+    cd = designed_codec(f"test10-fuzz{case}", lambda path: write_random_alist(path, N, M, dvc, dvp, seed=100 + case), sigma=sig, max_iters=I,
+                        nq_msg=nqm, nq_cha=nqc)
+    assert len(set(cd.code.dc.tolist())) >= 1 and cd.code.nvar == N and cd.code.nchk == M
     dec = product_decoder(cd)
     snr = -10 * np.log10(2 * cd.rate * sig * sig) + 0.5
     cha, msg, _ = awgn_labels(cd, B, snr, seed=case)
@@ -271,7 +260,7 @@ def test_output_verbosity_message_dumps_match_the_oracle_text(name, level):
     The product's text (LDPC_Code_LUT::lut_decode with the dumps taken on the device) equals the oracle's restatement of those
     print statements: frames that pass the test on the channel decisions print nothing, frames that leave through the exit test
     stop before the dump of their last variable update, iteration numbers in upper-case hex (std::hex is sticky)."""
-    from test_host_design_parity import product_codec
+    from helpers import product_codec
     cd = oracle_codec(name)
     pcd = product_codec(name, device=0)
     assert pcd.var_trees_txt == cd.var_tree_txt                        # same tables on both sides (design parity)

@@ -12,10 +12,9 @@ import numpy as np
 import pytest
 
 import lut_ldpc_amd as L
-from lut_ldpc_amd._capi import ERR_ARG, check, lib
-from helpers import CODES, ROOT, awgn_labels, oracle_codec, product_decoder, write_ira_alist
+from lut_ldpc_amd._capi import ERR_ARG, ChannelCells, check, lib
+from helpers import C5_TREES, CODES, ROOT, awgn_labels, c5_sigma2, designed_codec, oracle_codec, oracle_graph, product_codec, product_decoder, write_ira_alist
 from oracle import oracle as orc
-from test_host_design_parity import product_codec
 
 pytestmark = pytest.mark.gpu
 
@@ -155,18 +154,14 @@ def test_decode_at_every_alphabet_matches_oracle(name, snr, modes, path, monkeyp
 
 
 @pytest.mark.parametrize("keep", ["0", "1"])
-def test_chain_fusion_and_compaction_with_a_shrinking_alphabet(tmp_path, keep, monkeypatch):
+def test_chain_fusion_and_compaction_with_a_shrinking_alphabet(keep, monkeypatch):
     """Dual-diagonal code, schedule 8 8 8 8 4 4 4 2: chain fusion loads each iteration's degree-2 root table, compaction of the
     surviving frames forced at every second iteration (check points across the alphabet changes), ten frame groups."""
     monkeypatch.setenv("LUTLDPC_RESIDENT", "0")
     for k, v in (("COMPACT", "1"), ("COMPACT_FIRST", "2"), ("COMPACT_EVERY", "2"), ("COMPACT_MARGIN", "0"), ("COMPACT_KEEP", keep)):
         monkeypatch.setenv("LUTLDPC_" + k, v)
     K, M = 1600, 400
-    N, _ = write_ira_alist(tmp_path / "ira.alist", K, M, 3, seed=K)
-    cd = orc.Codec(orc.Code(tmp_path / "ira.alist"), skip_rank=True)
-    cd.set_rank(M)
-    cd.rate = 1.0 - M / N
-    cd.design_luts(sigma2=0.5 ** 2, max_iters=8, nq_msg=np.array([8, 8, 8, 8, 4, 4, 4, 2], np.int32), nq_cha=16)
+    cd = designed_codec("test15-ira-ex8421", lambda path: write_ira_alist(path, K, M, 3, seed=K), sigma=0.5, max_iters=8, nq_msg=[8, 8, 8, 8, 4, 4, 4, 2])
     dec = product_decoder(cd)
     desc = dec.describe()
     assert desc["chain_nodes"] >= M // 2 and desc["skewed_pipeline"] == 1 and desc["compaction"] == 1, desc
@@ -189,11 +184,7 @@ def test_dvbs2_with_the_example_schedule():
     off decode every frame alike, and a sample of frames equals the oracle."""
     import os
     alist = CODES / "rate0.50_irreg_dvbs2_N64800.alist"
-    cd = orc.Codec(orc.Code(alist), skip_rank=True)
-    cd.set_rank(32400)
-    cd.rate = 0.5
-    nq = np.array([8, 8, 8, 8, 4, 4, 4, 2], np.int32)
-    cd.design_luts(sigma2=0.55 ** 2, max_iters=8, nq_msg=nq, nq_cha=16, allow_deg1=True)
+    cd = designed_codec("test15-dvbs2-ex8421", alist, sigma=0.55, max_iters=8, nq_msg=[8, 8, 8, 8, 4, 4, 4, 2], rank=32400, allow_deg1=True)
     cha, msg, _ = awgn_labels(cd, 1100, 5.8, seed=64800)             # (eight iterations with 4- and 2-label messages need a high SNR)
     cha[5] = 15; msg[5] = 7
     got = {}
@@ -322,18 +313,15 @@ def test_device_quantiser_at_every_alphabet(name):
 def test_more_than_72_cells_is_refused_by_the_sampler():
     """The device cell table holds 72 cells: lutldpc_decoder_sim_batch / sample_labels refuse a bigger table with ERR_ARG and a
     message instead of truncating it."""
-    from test_40_device_codewords_gpu import Cells, _p
     cd = oracle_codec("reg36_n1000_q6")
     dec = product_decoder(cd)
     n = 100
     thr = np.sort(np.random.default_rng(0).integers(0, 2 ** 63, n - 1, dtype=np.uint64))
     lab = np.minimum(np.arange(n) * 64 // n, 63).astype(np.uint8)
-    keep = [thr, lab, lab.copy(), (np.arange(n) < n // 2).astype(np.uint8), lab[::-1].copy(), lab[::-1].copy()]
-    cells = Cells(n, _p(keep[0], C.c_uint64), *[_p(a, C.c_uint8) for a in keep[1:]])
+    cells = ChannelCells.from_table({"thr": thr, "cha": lab, "msg": lab.copy(), "neg": (np.arange(n) < n // 2).astype(np.uint8), "cha_m": lab[::-1].copy(),
+                                     "msg_m": lab[::-1].copy()})
     stats = np.zeros((10, 4), np.int32)
-    lib.lutldpc_decoder_sim_batch.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(C.c_uint8), C.c_int,
-                                              C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
-    rc = lib.lutldpc_decoder_sim_batch(dec._h, C.byref(cells), 1, 0, 0, 10, None, 500, _p(stats, C.c_int32), None, None)
+    rc = lib.lutldpc_decoder_sim_batch(dec._h, C.byref(cells), 1, 0, 0, 10, None, 500, stats.ctypes.data_as(C.POINTER(C.c_int32)), None, None)
     assert rc == ERR_ARG
     assert "72" in lib.lutldpc_last_error().decode()
     dec.close()
@@ -344,7 +332,6 @@ def test_ber_sim_regular_example_with_its_message_schedule_matches_oracle(tmp_pa
     """data/params/ber.ini.regular.example with its commented-out `qbits_messages = 3 3 3 3 2 2 2 1` in force (Nframes raised):
     the C++ driver and lut_ldpc_amd.ber_sim.run equal the oracle's frame loop at every SNR point."""
     from lut_ldpc_amd import ber_sim
-    from test_40_device_codewords_gpu import C5_TREES, _c5_sigma2, _oracle_graph
     for d in ("codes", "trees"):
         (tmp_path / d).mkdir()
     shutil.copy(CODES / "rate0.84_reg_v6c32_N2048.alist", tmp_path / "codes")
@@ -362,10 +349,10 @@ def test_ber_sim_regular_example_with_its_message_schedule_matches_oracle(tmp_pa
     assert len(pts) == n and (np.array([c for _, c in pts]) == got).all()
     nq = np.array([8, 8, 8, 8, 4, 4, 4, 2], np.int32)
     pcd = L.Codec(CODES / "rate0.84_reg_v6c32_N2048.alist", with_generator=True, device=0)
-    pcd.design_luts(tree_method=C5_TREES, sigma2=_c5_sigma2(), max_iters=8, nq_cha=16, nq_msg=nq)
-    ref = orc.Codec(_oracle_graph(pcd), skip_rank=True)
+    pcd.design_luts(tree_method=C5_TREES, sigma2=c5_sigma2(), max_iters=8, nq_cha=16, nq_msg=nq)
+    ref = orc.Codec(oracle_graph(pcd), skip_rank=True)
     ref.set_rank(325)
-    ref.design_luts(tree_method=C5_TREES, sigma2=_c5_sigma2(), max_iters=8, nq_cha=16, nq_msg=nq)
+    ref.design_luts(tree_method=C5_TREES, sigma2=c5_sigma2(), max_iters=8, nq_cha=16, nq_msg=nq)
     assert ref.var_tree_txt == pcd.var_trees_txt
     ref.set_initial_message_mode(1)
     ref.set_exit_conditions(8, True, True)

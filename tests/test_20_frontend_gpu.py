@@ -9,10 +9,9 @@ import numpy as np
 import pytest
 
 import lut_ldpc_amd as L
-from helpers import CODES, ROOT, TREES, oracle_codec
+from helpers import CODES, ROOT, TREES, oracle_codec, product_codec
 from itfile_reader import itload
 from oracle import oracle as orc
-from test_host_design_parity import product_codec
 
 pytestmark = pytest.mark.gpu
 

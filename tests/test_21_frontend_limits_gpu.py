@@ -11,13 +11,10 @@ import numpy as np
 import pytest
 
 import frontend_cases as fc
-from lut_ldpc_amd._capi import ERR_ARG, ERR_UNSUPPORTED, check, last_error, lib
-from helpers import product_decoder
-from test_40_device_codewords_gpu import Cells, _p
+from lut_ldpc_amd._capi import ERR_ARG, ERR_UNSUPPORTED, ChannelCells, EventRequest, LutLdpcError, last_error, lib
+from helpers import product_decoder, same as _same
 
 pytestmark = pytest.mark.gpu
-
-u8p, i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
 
 
 @pytest.fixture(scope="module")
@@ -45,46 +42,18 @@ def handles():
         dec.close()
 
 
-def _argtypes():
-    """(set before every call, as every test that calls these two entries sets its own)"""
-    lib.lutldpc_decoder_sim_batch.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, u8p, C.c_int, i32p, u8p, u8p]
-    lib.lutldpc_decoder_sample_labels.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, u8p, u8p, u8p]
-
-
-def _cells(t):
-    _argtypes()
-    keep = [np.ascontiguousarray(t[k]) for k in ("thr", "cha", "msg", "neg", "cha_m", "msg_m")]
-    return Cells(len(t["cha"]), _p(keep[0], C.c_uint64), *[_p(a, C.c_uint8) for a in keep[1:]]), keep
-
-
-def _cw(cw):
-    return None if cw is None else _p(np.ascontiguousarray(cw), C.c_uint8)
+def _p(a, t):
+    return a.ctypes.data_as(C.POINTER(t))
 
 
 def _sample(dec, table, seed, stream, f0, B, cw):
-    cells, keep = _cells(table)
-    cha, msg = np.full((B, dec.nvar), 0xEE, np.uint8), np.full((B, dec.nvar), 0xEE, np.uint8)
-    cw = None if cw is None else np.ascontiguousarray(cw)
-    check(lib.lutldpc_decoder_sample_labels(dec._h, C.byref(cells), seed, stream, f0, B, _cw(cw), _p(cha, C.c_uint8), _p(msg, C.c_uint8)))
-    return cha, msg
+    return dec.sample_labels(table, seed, stream, f0, B, codewords=cw, cha=np.full((B, dec.nvar), 0xEE, np.uint8), msg=np.full((B, dec.nvar), 0xEE, np.uint8))
 
 
 def _sim(dec, table, seed, stream, f0, B, cw, K, random=False):
     """(frame_stats, cha_out, bits_out) of sim_batch on host codewords (or none), or of sim_batch_random."""
-    cells, keep = _cells(table)
-    stats, cha, bits = np.full((B, 4), -7, np.int32), np.full((B, dec.nvar), 0xEE, np.uint8), np.full((B, dec.nvar), 0xEE, np.uint8)
-    cw = None if cw is None else np.ascontiguousarray(cw)
-    if random:
-        check(lib.lutldpc_decoder_sim_batch_random(dec._h, C.byref(cells), seed, stream, f0, B, K, _p(stats, C.c_int32), _p(cha, C.c_uint8), _p(bits, C.c_uint8)))
-    else:
-        check(lib.lutldpc_decoder_sim_batch(dec._h, C.byref(cells), seed, stream, f0, B, _cw(cw), K, _p(stats, C.c_int32), _p(cha, C.c_uint8), _p(bits, C.c_uint8)))
-    return stats, cha, bits
-
-
-def _same(got, want, what, u=None):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, (what, len(bad), "first (frame, node)", bad[:4].tolist(), "got", got[tuple(bad[0])], "want", want[tuple(bad[0])],
-                           None if u is None else hex(int(u[tuple(bad[0])])))
+    return dec.sim_batch(table, seed, stream, f0, B, K, codewords=cw, random=random, frame_stats=np.full((B, 4), -7, np.int32),
+                         cha_out=np.full((B, dec.nvar), 0xEE, np.uint8), bits_out=np.full((B, dec.nvar), 0xEE, np.uint8))
 
 
 @pytest.mark.parametrize("case", fc.SAMPLER_CASES, ids=fc.case_id)
@@ -133,22 +102,18 @@ def test_stats_row_at_the_edges_of_k_info(handle, Ks, bk, handles):
 
 
 def _set_generator(dec, K, R):
-    rows = np.ascontiguousarray(fc.generator_rows(K, R))
-    buf = rows if R else np.zeros(1, np.uint64)                 # (R = 0: no row is read, the pointer must not be null)
-    return lib.lutldpc_decoder_set_generator(dec._h, K, R, _p(buf, C.c_uint64))
+    dec.set_generator(K, R, fc.generator_rows(K, R))
 
 
 def _encode(dec, seed, stream, f0, B):
-    cw = np.full((B, dec.nvar), 0xEE, np.uint8)
-    check(lib.lutldpc_decoder_encode_random(dec._h, seed, stream, f0, B, _p(cw, C.c_uint8)))
-    return cw
+    return dec.encode_random(seed, stream, f0, B, out=np.full((B, dec.nvar), 0xEE, np.uint8))
 
 
 @pytest.mark.parametrize("handle,K,R", fc.GENERATOR_CASES, ids=[f"{h}-K{K}-R{R}" for h, K, R in fc.GENERATOR_CASES])
 def test_encoder_equals_the_reference_at_the_edges_of_k_and_r(handle, K, R, handles):
     dec = handles(handle)
     T = fc.HANDLES[handle][2]
-    check(_set_generator(dec, K, R))                            # (replaces the generator of the case before on this live handle)
+    _set_generator(dec, K, R)                                   # (replaces the generator of the case before on this live handle)
     assert dec.describe()["generator"] == {"K": K, "R": R}
     sizes = [fc.gen_batch(b, T) for b in fc.GEN_B]
     want = fc.generator_reference(K, R, max(sizes))
@@ -177,17 +142,20 @@ def test_generator_replaced_on_a_live_handle_takes_effect_and_a_refused_one_chan
     dec = handles("q4")
     out = {}
     for K in (33, 500, 33):
-        check(_set_generator(dec, K, 1000 - K))
+        _set_generator(dec, K, 1000 - K)
         cw = _encode(dec, fc.GEN_SEED, 7, fc.GEN_F0, 65)
         assert (cw == fc.encode(fc.generator_bits(fc.generator_rows(K, 1000 - K), K), fc.info_bits(fc.GEN_SEED, 7, fc.GEN_F0, 65, K))).all(), K
         assert K not in out or (out[K] == cw).all()
         out[K] = cw
     assert (out[33] != out[500]).any()
     big = handles("n10000")
-    check(_set_generator(big, 8192, 1808))
+    _set_generator(big, 8192, 1808)
     before = _encode(big, fc.GEN_SEED, 7, fc.GEN_F0, 3)
     h, K, R = fc.GENERATOR_REFUSED
-    assert h == "n10000" and _set_generator(big, K, R) == ERR_UNSUPPORTED and "8192" in last_error()
+    assert h == "n10000"
+    with pytest.raises(LutLdpcError, match="8192") as refused:
+        _set_generator(big, K, R)
+    assert refused.value.code == ERR_UNSUPPORTED
     assert big.describe()["generator"] == {"K": 8192, "R": 1808}
     assert (_encode(big, fc.GEN_SEED, 7, fc.GEN_F0, 3) == before).all()
 
@@ -195,13 +163,12 @@ def test_generator_replaced_on_a_live_handle_takes_effect_and_a_refused_one_chan
 def test_stream_with_bit_31_is_refused_and_nothing_is_written(handles):
     """Counter word 3 is `stream` for the channel and `stream | 0x80000000` for the information bits: every entry that takes a stream
     answers one with bit 31 set with ERR_ARG and leaves its outputs alone; 2^31 - 1 is the largest stream and works."""
-    from lut_ldpc_amd._capi import EventRequest
     dec = handles("q4")
     N, B, K = dec.nvar, 65, 500
-    check(_set_generator(dec, K, N - K))
+    _set_generator(dec, K, N - K)
     cd = fc.codec("reg36_n1000_q4")
     table = cd.channel_cells(fc.STATS_SNR, cd.rate)
-    cells, keep = _cells(table)
+    cells = ChannelCells.from_table(table)
     nd, groups, labels, _ = dec.histogram_shape(3)
     for stream in (2 ** 31, 2 ** 32 - 1):
         cha, msg, bits, cw = (np.full((B, N), 0xEE, np.uint8) for _ in range(4))

@@ -9,6 +9,7 @@ import pytest
 
 import lut_ldpc_amd as L
 import bp_cases as bc
+from helpers import same
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -19,10 +20,9 @@ def _decoder(code, d=(12, 300, 7, 28)):
 
 
 def _same(got, want):
-    gb, gi, gq = got
-    wb, wi, wq = want
-    assert (gi == wi).all(), (np.flatnonzero(gi != wi)[:8], gi[:8], wi[:8])
-    assert (gq == wq).all() and (gb == wb).all()
+    """(bits, iteration codes, output QLLRs) of two decodes."""
+    for k, what in ((1, "iteration codes"), (2, "output QLLRs"), (0, "decided bits")):
+        same(got[k], want[k], what)
 
 
 @pytest.mark.parametrize("d", bc.STAR_SETTINGS, ids=str)

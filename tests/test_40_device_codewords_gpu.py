@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 
 import lut_ldpc_amd as L
-from lut_ldpc_amd._capi import check, lib
-from helpers import CODES, ROOT, TREES
+from lut_ldpc_amd._capi import ChannelCells, check, lib
+from helpers import C5_TREES, CODES, ROOT, TREES, c5_sigma2, oracle_graph
 from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -17,25 +17,6 @@ pytestmark = pytest.mark.gpu
 # every code in data/codes the host builds a generator for (the N = 64800 codes are beyond its dense elimination)
 GEN_CODES = ["rate0.50_dv02-17_dc08-09_lut_q4_N500", "rate0.50_dv02-17_dc08-09_lut_q4_N1000", "rate0.50_dv03_dc06_N1000",
              "rate0.84_reg_v6c32_N2048", "rate0.50_dv03_dc06_N10000"]
-C5_TREES = "filename=" + str(TREES / "6_32_wide.ini")
-
-
-class Cells(C.Structure):
-    _fields_ = [("n_cells", C.c_int32), ("thr", C.POINTER(C.c_uint64)), ("cha_label", C.POINTER(C.c_uint8)), ("msg_label", C.POINTER(C.c_uint8)),
-                ("slicer_neg", C.POINTER(C.c_uint8)), ("cha_label_mirror", C.POINTER(C.c_uint8)), ("msg_label_mirror", C.POINTER(C.c_uint8))]
-
-
-def _p(a, t):
-    return a.ctypes.data_as(C.POINTER(t))
-
-
-def _oracle_graph(pcd):
-    dv, dc, cn = pcd.graph()
-    return orc.Code(graph=(pcd.nvar, pcd.nchk, dv, dc, cn))
-
-
-def _c5_sigma2(rank=325, n=2048):
-    return 10 ** (-3.9 / 10) / (2 * (1.0 - rank / n))
 
 
 @pytest.mark.parametrize("alist", GEN_CODES)
@@ -46,7 +27,7 @@ def test_device_encoder_matches_oracle_info_bits_parity_checks_and_host_encoder(
     assert pcd.decoder().describe()["generator"] == {"K": K, "R": pcd.rank}
     if alist.endswith("N2048"):
         assert pcd.rank == 325 < pcd.nchk                            # rank-deficient H
-    oc = orc.Codec(_oracle_graph(pcd), skip_rank=True)
+    oc = orc.Codec(oracle_graph(pcd), skip_rank=True)
     seed, stream, f0 = 2 ** 32 + 77, 3, 2 ** 32 + 5
     rng = np.random.default_rng(1)
     for B in (1, 17, 4097):
@@ -73,7 +54,7 @@ def _product_c1():
 
 def _product_c5():
     pcd = L.Codec(CODES / "rate0.84_reg_v6c32_N2048.alist", with_generator=True, device=0)
-    pcd.design_luts(tree_method=C5_TREES, sigma2=_c5_sigma2(), max_iters=8, nq_cha=16, nq_msg=8)
+    pcd.design_luts(tree_method=C5_TREES, sigma2=c5_sigma2(), max_iters=8, nq_cha=16, nq_msg=8)
     pcd.set_initial_message_mode(1)                                   # from_quantized_channel_llrs
     pcd.set_exit_conditions(8, True, True)
     return pcd, 4.0
@@ -89,32 +70,20 @@ def test_sim_batch_on_device_codewords_equals_host_codewords(cfg, resident, monk
     # the same frames through lutldpc_decoder_sim_batch, fed the codewords of the HOST encoder (sample_labels keeps it)
     cha_host, msg_host, cw = pcd.sample_labels(snr, seed, stream, 0, B, zero_codeword=False)
     assert cw.any()
-    cc = pcd.channel_cells(snr)
-    keep = [np.ascontiguousarray(cc[k]) for k in ("thr", "cha", "msg", "neg", "cha_m", "msg_m")]
-    cells = Cells(len(cc["cha"]), _p(keep[0], C.c_uint64), *[_p(a, C.c_uint8) for a in keep[1:]])
-    want = np.empty((B, 4), np.int32)
+    cells = ChannelCells.from_table(pcd.channel_cells(snr))
     dec = pcd.decoder()
     assert dec.describe()["resident"] == int(resident)
-    lib.lutldpc_decoder_sim_batch.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(C.c_uint8), C.c_int,
-                                              C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]
-    cw = np.ascontiguousarray(cw)
     N = pcd.nvar
     cha_h, bits_h, cha_d, bits_d = (np.full((B, N), 0xEE, np.uint8) for _ in range(4))
-    check(lib.lutldpc_decoder_sim_batch(dec._h, C.byref(cells), seed, stream, 0, B, _p(cw, C.c_uint8), pcd.ninfo,
-                                        _p(want, C.c_int32), cha_h.ctypes.data, bits_h.ctypes.data))
+    want, _, _ = dec.sim_batch(cells, seed, stream, 0, B, pcd.ninfo, codewords=cw, cha_out=cha_h, bits_out=bits_h)
     assert (got == want).all(), np.argwhere(got != want)[:5]
     assert (want[:, 3] > 0).all()
     # the labels and decided bits of both: the host codewords reach the sampler and the counters as the same sent-bit rows
-    rnd = np.empty((B, 4), np.int32)
-    check(lib.lutldpc_decoder_sim_batch_random(dec._h, C.byref(cells), seed, stream, 0, B, pcd.ninfo, _p(rnd, C.c_int32), _p(cha_d, C.c_uint8),
-                                               _p(bits_d, C.c_uint8)))
+    rnd, _, _ = dec.sim_batch(cells, seed, stream, 0, B, pcd.ninfo, random=True, cha_out=cha_d, bits_out=bits_d)
     assert (rnd == want).all()
     assert (cha_h == cha_d).all() and (bits_h == bits_d).all()
     # ... and the test entry of the sampler, fed the same host codewords: that cha again, and the msg0 of the call above
-    lib.lutldpc_decoder_sample_labels.argtypes = [C.c_void_p, C.POINTER(Cells), C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(C.c_uint8),
-                                                  C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
-    cha_s, msg_s = np.full((B, N), 0xEE, np.uint8), np.full((B, N), 0xEE, np.uint8)
-    check(lib.lutldpc_decoder_sample_labels(dec._h, C.byref(cells), seed, stream, 0, B, _p(cw, C.c_uint8), _p(cha_s, C.c_uint8), _p(msg_s, C.c_uint8)))
+    cha_s, msg_s = dec.sample_labels(cells, seed, stream, 0, B, codewords=cw, cha=np.full((B, N), 0xEE, np.uint8), msg=np.full((B, N), 0xEE, np.uint8))
     assert (cha_s == cha_h).all() and (cha_s == cha_host).all() and (msg_s == msg_host).all()
     # pad frames carry zero codewords and no counts: the first frames of a larger batch (no padding there) are the same frames
     big = pcd.sim_batch(snr, seed, stream, 0, 2048, zero_codeword=False)
@@ -128,7 +97,6 @@ def test_host_codewords_equal_device_codewords_in_histogram_and_events(pack, B, 
     encoder's codewords and once on the bytes encode_random returns for them, passed back as host codewords: the same sent-bit
     rows either way, so identical histograms, frame_stats, records, lists and profiles.  Two frame groups, three frames in the
     second: nibble rows at B = 515, byte rows (LUTLDPC_PACK = 1) at B = 259."""
-    from lut_ldpc_amd.err_events import _Request
     if pack:
         monkeypatch.setenv("LUTLDPC_PACK", pack)                    # read when the device handle is created
     pcd, snr = _product_c1()
@@ -137,20 +105,15 @@ def test_host_codewords_equal_device_codewords_in_histogram_and_events(pack, B, 
     seed, stream, f0 = 2 ** 33 + 11, 4, 2 ** 32 + 3
     cw = np.ascontiguousarray(pcd.encode_random(seed, stream, f0, B))
     assert cw.any() and cw.max() <= 1
-    cc = pcd.channel_cells(snr)
-    keep = [np.ascontiguousarray(cc[k]) for k in ("thr", "cha", "msg", "neg", "cha_m", "msg_m")]
-    cells = Cells(len(cc["cha"]), _p(keep[0], C.c_uint64), *[_p(a, C.c_uint8) for a in keep[1:]])
+    cells = ChannelCells.from_table(pcd.channel_cells(snr))
     nd, groups, labels, _ = dec.histogram_shape(3)
     res = []
-    for codewords, on_device in ((None, 1), (_p(cw, C.c_uint8), 0)):
-        hist, got = np.zeros((nd, groups, 2, labels), np.int64), C.c_int32()
-        check(lib.lutldpc_decoder_sim_batch_histogram(dec._h, C.byref(cells), seed, stream, f0, B, codewords, on_device, 3, 0, labels,
-                                                      _p(hist, C.c_int64), hist.size, C.byref(got)))
-        assert got.value == nd and hist[:, :, 1].any()
-        rq, stats = _Request(pcd.nvar, pcd.nchk, "codeword", B, 64, 64, True), np.full((B, 4), -7, np.int32)
-        check(lib.lutldpc_decoder_sim_batch_events(dec._h, C.byref(cells), seed, stream, f0, B, codewords, on_device, pcd.ninfo, _p(stats, C.c_int32),
-                                                   C.byref(rq.c)))
-        res.append((hist, stats, rq.result()))
+    for codewords, on_device in ((None, True), (cw, False)):
+        hist = dec.sim_batch_histogram(cells, seed, stream, f0, B, codewords=codewords, device_codewords=on_device, level=3, mode="all", n_labels=labels)
+        assert hist.shape == (nd, groups, 2, labels) and hist[:, :, 1].any()
+        ev, stats = dec.sim_batch_events(cells, seed, stream, f0, B, k_info=pcd.ninfo, codewords=codewords, device_codewords=on_device, select="codeword",
+                                         max_frames=B, max_pos=64, max_chk=64, profiles=True, frame_stats=np.full((B, 4), -7, np.int32))
+        res.append((hist, stats, ev))
     (h_d, s_d, e_d), (h_h, s_h, e_h) = res
     assert (h_d == h_h).all() and (s_d == s_h).all()
     assert e_d.n_selected == e_h.n_selected > 0 and len(e_d.events) == len(e_h.events) > 0
@@ -176,9 +139,9 @@ def test_ber_sim_regular_example_with_random_codewords_matches_oracle(tmp_path):
     assert n == 7 and list(snr[:n]) == [3, 3.5, 4, 4.5, 5, 5.5, 6]
     got = np.array(cnt[:n * 5]).reshape(n, 5)
     pcd, _ = _product_c5()
-    ref = orc.Codec(_oracle_graph(pcd), skip_rank=True)
+    ref = orc.Codec(oracle_graph(pcd), skip_rank=True)
     ref.set_rank(325)
-    ref.design_luts(tree_method=C5_TREES, sigma2=_c5_sigma2(), max_iters=8, nq_cha=16, nq_msg=np.full(8, 8, np.int32))
+    ref.design_luts(tree_method=C5_TREES, sigma2=c5_sigma2(), max_iters=8, nq_cha=16, nq_msg=np.full(8, 8, np.int32))
     assert ref.var_tree_txt == pcd.var_trees_txt
     ref.set_initial_message_mode(1)
     ref.set_exit_conditions(8, True, True)

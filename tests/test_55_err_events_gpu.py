@@ -178,20 +178,15 @@ def test_streaming_decode_path(monkeypatch):
     dec.close()
 
 
-def test_compaction_path(tmp_path, monkeypatch):
+def test_compaction_path(monkeypatch):
     """A dual-diagonal code at nine frame groups with compaction forced on as in tests/test_05: frames move between rows during
     the decode; the capture reads the rows after they are back in the caller's order."""
-    from helpers import awgn_labels, write_ira_alist
-    from oracle import oracle as orc
+    from helpers import awgn_labels, designed_codec, write_ira_alist
     for k, v in (("LUTLDPC_RESIDENT", "0"), ("LUTLDPC_COMPACT", "1"), ("LUTLDPC_COMPACT_KEEP", "1"), ("LUTLDPC_COMPACT_FIRST", "2"),
                  ("LUTLDPC_COMPACT_EVERY", "2"), ("LUTLDPC_COMPACT_MARGIN", "0")):
         monkeypatch.setenv(k, v)
     K, M, sig, I = 840, 420, 0.62, 16
-    N, _ = write_ira_alist(tmp_path / "ira.alist", K, M, 3, seed=K + I)
-    cd = orc.Codec(orc.Code(tmp_path / "ira.alist"), skip_rank=True)
-    cd.set_rank(M)
-    cd.rate = 1.0 - M / N
-    cd.design_luts(sigma2=sig ** 2, max_iters=I, nq_msg=np.full(I, 16, np.int32), nq_cha=16)
+    cd = designed_codec("test55-ira", lambda path: write_ira_alist(path, K, M, 3, seed=K + I), sigma=sig, max_iters=I, nq_msg=16)
     dec = product_decoder(cd)
     assert dec.describe()["compaction"] == 1 and dec.describe()["skewed_pipeline"] == 1
     B = 512 * 8 + 77

@@ -20,8 +20,7 @@ from lut_ldpc_amd import packing
 from lut_ldpc_amd._capi import IN_BYTES, IN_NIBBLES, PackedIO, check, lib
 
 import frontend_cases as fc
-from helpers import CODES as CODE_DIR, awgn_labels, oracle_codec, product_decoder
-from oracle import oracle as orc
+from helpers import CODES as CODE_DIR, PACKED_PATHS as PATHS, awgn_labels, designed_codec, oracle_codec, product_decoder
 
 pytestmark = pytest.mark.gpu
 
@@ -46,12 +45,8 @@ def codec(name):
         return oracle_codec("reg36_n1000_q5")
     if name in ("n127", "n33"):
         return fc.codec(name)
-    code = orc.Code(CODE_DIR / "rate0.50_dv03_dc06_N1000.alist")          # "six": 6 channel labels, 8 message labels
-    cd = orc.Codec(code, skip_rank=True)
-    cd.set_rank(code.nchk)
-    cd.rate = 0.5
-    cd.design_luts(sigma2=0.8 ** 2, max_iters=8, nq_msg=np.full(8, 8, np.int32), nq_cha=6)
-    return cd
+    # "six": 6 channel labels, 8 message labels
+    return designed_codec("test56-six", CODE_DIR / "rate0.50_dv03_dc06_N1000.alist", sigma=0.8, max_iters=8, nq_msg=8, nq_cha=6)
 
 
 def batches(name):
@@ -185,14 +180,6 @@ def test_packed_decode_matches_oracle_and_the_byte_entry(name, B):
     assert desc["tile_frames"] == CASES[name]["tile"] and desc["pack"] == (2 if CASES[name]["tile"] == 512 else 1), desc
     run_case(dec, name, B)
     dec.close()
-
-
-PATHS = {
-    "resident": ({}, dict(resident=1)),
-    "streaming": ({"LUTLDPC_RESIDENT": "0"}, dict(resident=0, skewed_pipeline=1)),
-    "per_class": ({"LUTLDPC_RESIDENT": "0", "LUTLDPC_SKEW": "0"}, dict(resident=0, skewed_pipeline=0)),
-    "byte_rows": ({"LUTLDPC_PACK": "1"}, dict(pack=1, tile_frames=256)),       # nibble input into byte rows
-}
 
 
 @pytest.mark.parametrize("path", list(PATHS))

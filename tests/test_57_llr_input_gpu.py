@@ -12,9 +12,8 @@ from lut_ldpc_amd import _capi, packing
 from lut_ldpc_amd._capi import ERR_ARG, LlrIO, check, last_error, lib
 
 import llr_cases as lc
-from helpers import CODES as CODE_DIR, product_decoder
+from helpers import CODES as CODE_DIR, PACKED_PATHS as PATHS, product_decoder
 from oracle import oracle as orc
-from test_56_packed_io_gpu import PATHS
 
 pytestmark = pytest.mark.gpu
 

@@ -12,7 +12,7 @@ import pytest
 
 import encode_cases as ec
 import frontend_cases as fc
-from helpers import product_decoder
+from helpers import product_decoder, same as _same
 from lut_ldpc_amd import packing
 from lut_ldpc_amd._capi import ERR_ARG, ERR_STATE, EncodeIO, LutLdpcError, check, last_error, lib
 
@@ -45,12 +45,6 @@ def handles():
         dec.close()
 
 
-def _set_generator(dec, K, R):
-    rows = np.ascontiguousarray(fc.generator_rows(K, R))
-    buf = rows if R else np.zeros(1, np.uint64)                 # (R = 0: no row is read, the pointer must not be null)
-    return lib.lutldpc_decoder_set_generator(dec._h, K, R, buf.ctypes.data_as(C.POINTER(C.c_uint64)))
-
-
 def _raw(dec, info, in_stride, B, first, count, io=None):
     """The raw entry on host memory: (return code, output words [B, W], guard words) -- the buffer pre-filled with 0xEE."""
     W = (count + 31) // 32
@@ -60,16 +54,11 @@ def _raw(dec, info, in_stride, B, first, count, io=None):
     return rc, buf[:B * W].reshape(B, W), buf[B * W:]
 
 
-def _same(got, want, what):
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, (what, len(bad), "first (frame, word)", bad[:4].tolist(), "got", hex(int(got[tuple(bad[0])])), "want", hex(int(want[tuple(bad[0])])))
-
-
 @pytest.mark.parametrize("case", ec.SYNTH_CASES, ids=ec.synth_id)
 def test_synthetic_generators_at_the_edges_of_k_and_r_every_window_batch_and_stride(case, handles):
     handle, K, R = case
     dec = handles(handle)
-    check(_set_generator(dec, K, R))                            # (replaces the generator of the case before on this live handle)
+    dec.set_generator(K, R, fc.generator_rows(K, R))                            # (replaces the generator of the case before on this live handle)
     assert dec.describe()["generator"] == {"K": K, "R": R} and dec.nvar == K + R
     for in_stride, stride in ec.strides(K):
         words, cw = ec.info_words(K, stride), ec.synth_reference(K, R, stride)
@@ -89,7 +78,7 @@ def test_host_memory_equals_device_memory_strided_views_and_the_asynchronous_cal
     import torch
     dec = handles("q4")
     K, R, B = 500, 500, 130
-    check(_set_generator(dec, K, R))
+    dec.set_generator(K, R, fc.generator_rows(K, R))
     W = (K + 31) // 32
     words, cw = ec.info_words(K, W + ec.SPARE_WORDS), ec.synth_reference(K, R, W + ec.SPARE_WORDS)
     dev = torch.device("cuda", 0)
@@ -215,7 +204,7 @@ def test_state_of_the_handle_is_left_alone_and_a_new_generator_takes_effect(hand
     dec = handles("q4")
     out = {}
     for K in (33, 500, 33):
-        check(_set_generator(dec, K, 1000 - K))
+        dec.set_generator(K, 1000 - K, fc.generator_rows(K, 1000 - K))
         W = (K + 31) // 32
         got = dec.encode_packed(np.ascontiguousarray(ec.info_words(K, W)[:65]))
         _same(got, ec.pack(ec.synth_reference(K, 1000 - K, W)[:65]), f"K {K}")
@@ -231,7 +220,7 @@ def test_refusals_on_a_live_handle_write_nothing():
     info = np.ascontiguousarray(ec.info_words(K, W)[:B])
     rc, got, guard = _raw(dec, info, 0, B, 0, N)
     assert rc == ERR_STATE and "lutldpc_decoder_set_generator" in last_error() and (got == FILL32).all()
-    check(_set_generator(dec, K, N - K))
+    dec.set_generator(K, N - K, fc.generator_rows(K, N - K))
     out = np.full((B, (N + 31) // 32 + 1), FILL32, np.uint32)
     good = lambda **kw: EncodeIO(**{**dict(on_device=0, in_stride=0, out_first=0, out_count=N, sync=0), **kw})
     call = lambda h, io, src, b, dst: lib.lutldpc_decoder_encode_packed(h, C.byref(io) if io is not None else None, src, b, dst)

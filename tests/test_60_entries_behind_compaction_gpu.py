@@ -4,8 +4,6 @@ channel-label rows in place, launch_uncompaction brings back the decided bits an
 out or counts after the decode -- sampled labels, histograms, statistics, windows of bits -- must still be in the caller's frame
 order.  Every comparison is exact equality of integer arrays over ALL frames; every entry is called three times on one handle with
 the same key (plain launches, graph capture, graph replay) and the three results are equal."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -14,11 +12,9 @@ import compact_cases as cc
 from events_helpers import assert_equal, expected
 from lut_ldpc_amd import msg_stats as ms
 from lut_ldpc_amd import packing
-from lut_ldpc_amd._capi import check, lib
+from helpers import same as _same
 from oracle import oracle as orc
 from stats_helpers import hist_from_trace
-from test_21_frontend_limits_gpu import _cells, _cw
-from test_40_device_codewords_gpu import _p
 
 pytestmark = pytest.mark.gpu
 
@@ -34,8 +30,7 @@ def _handle(variant, monkeypatch, sizes=None, generator=False):
     dec, desc = cc.describe(cc.knobs(variant), monkeypatch, device=0)
     cc.check_path(variant, desc, sizes if sizes is not None else [cc.batch(variant, w) for w in cc.BATCHES])
     if generator:
-        rows = cc.generator_rows()
-        check(lib.lutldpc_decoder_set_generator(dec._h, cc.K_INFO, cc.R_GEN, _p(rows, C.c_uint64)))
+        dec.set_generator(cc.K_INFO, cc.R_GEN, cc.generator_rows())
         assert dec.describe()["generator"] == {"K": cc.K_INFO, "R": cc.R_GEN}
     dec.set_exit_conditions(I, True, True)
     return dec
@@ -57,23 +52,12 @@ def thrice(call, what=""):
     return runs[0]
 
 
-def _same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, (what, f"{len(bad)} mismatches, first (frame, node)", bad[:4].tolist(), "got", got[tuple(bad[0])], "want", want[tuple(bad[0])])
-
-
 def _sim(dec, seed, stream, f0, B, cw, K, random=False, table=None):
     """(frame_stats, cha_out, bits_out) of sim_batch on host codewords (or none) or of sim_batch_random, each with two canary rows
     after frame B - 1 that must stay as they were."""
-    cells, keep = _cells(table if table is not None else cc.cells())
     stats, cha, bits = np.full((B + 2, 4), -7, np.int32), np.full((B + 2, dec.nvar), 0xEE, np.uint8), np.full((B + 2, dec.nvar), 0xEE, np.uint8)
-    cw = None if cw is None else np.ascontiguousarray(cw)
-    if random:
-        check(lib.lutldpc_decoder_sim_batch_random(dec._h, C.byref(cells), seed, stream, f0, B, K, _p(stats, C.c_int32), _p(cha, C.c_uint8), _p(bits, C.c_uint8)))
-    else:
-        check(lib.lutldpc_decoder_sim_batch(dec._h, C.byref(cells), seed, stream, f0, B, _cw(cw), K, _p(stats, C.c_int32), _p(cha, C.c_uint8), _p(bits, C.c_uint8)))
+    out = dec.sim_batch(table if table is not None else cc.cells(), seed, stream, f0, B, K, codewords=cw, random=random, frame_stats=stats, cha_out=cha, bits_out=bits)
+    assert all(a is b for a, b in zip(out, (stats, cha, bits)))
     assert (stats[B:] == -7).all() and (cha[B:] == 0xEE).all() and (bits[B:] == 0xEE).all(), "rows after frame B - 1 were written"
     return stats[:B], cha[:B], bits[:B]
 
@@ -178,15 +162,7 @@ def test_histogram_batch_counts_every_frame_under_its_own_code(variant, mode, wi
 
 # ---------------------------------------------------------------------------------------------------------------- 3. sim_batch_histogram
 def _sim_hist(dec, f0, B, cw, on_device, hist=None):
-    cells, keep = _cells(cc.cells())
-    nd, groups, labels, _ = dec.histogram_shape(LEVEL)
-    hist = np.zeros((nd, groups, 2, labels), np.int64) if hist is None else hist
-    got = C.c_int32()
-    cw = None if cw is None else np.ascontiguousarray(cw)
-    check(lib.lutldpc_decoder_sim_batch_histogram(dec._h, C.byref(cells), cc.SEED, cc.STREAM, f0, B, _cw(cw), int(on_device), LEVEL, 1, labels,
-                                                  _p(hist, C.c_int64), hist.size, C.byref(got)))
-    assert got.value == nd
-    return hist
+    return dec.sim_batch_histogram(cc.cells(), cc.SEED, cc.STREAM, f0, B, codewords=cw, device_codewords=on_device, level=LEVEL, mode="active", hist=hist)
 
 
 @pytest.mark.parametrize("source", ["zero", "device_codewords"])

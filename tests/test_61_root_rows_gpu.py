@@ -9,15 +9,12 @@ between iterations; 1 frame, 513 frames (a second group with one live frame) and
 or more are planted: every label at its maximum -- ch = 15 with `top` saturated, bits 60 .. 63 of the last row -- and every label
 0, nibble 0 of row 0."""
 import functools
-import tempfile
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import streaming_cases as sc
-from helpers import awgn_labels, compare, write_degree_alist
-from oracle import oracle as orc
+from helpers import compare, designed_codec, oracle_cache, planted_labels, write_degree_alist
 
 pytestmark = pytest.mark.gpu
 
@@ -30,25 +27,14 @@ OWN = {
     "c2m2": (2, [2] * ITERS, 0.50, 3.5),                    # (one-bit messages: a frame passes on the channel decisions or never, so half of them do)
     "grow": (8, [4, 8, 8, 16, 16, 16], 0.70, 0.5),         # the message alphabet changes between iterations: rows of 4, 8 and 16 nibbles
 }
-_tmp = None
 
 
-@functools.lru_cache(maxsize=None)
 def codec(name):
     if name in sc.CODES:
         return sc.codec(name)
-    global _tmp
-    _tmp = _tmp or tempfile.TemporaryDirectory(prefix="root_rows_")
-    path = Path(_tmp.name) / "d348.alist"
-    if not path.exists():
-        write_degree_alist(path, VDEG, CDEG, seed=sc.GRAPH_SEED)
     nqc, nqm, sig, _ = OWN[name]
-    N, M = sum(VDEG.values()), sum(CDEG.values())
-    cd = orc.Codec(orc.Code(path), skip_rank=True)
-    cd.set_rank(M)
-    cd.rate = 1.0 - M / N
-    cd.design_luts(sigma2=sig ** 2, max_iters=ITERS, nq_msg=np.asarray(nqm, np.int32), nq_cha=nqc)
-    return cd
+    return designed_codec("root_rows-" + name, lambda path: write_degree_alist(path, VDEG, CDEG, seed=sc.GRAPH_SEED), sigma=sig, max_iters=ITERS,
+                          nq_msg=nqm, nq_cha=nqc)
 
 
 @functools.lru_cache(maxsize=None)
@@ -56,16 +42,8 @@ def labels(name, n):
     """n frames near the design SNR; of three or more, frame 0 carries the largest label everywhere and frame 1 label 0 everywhere."""
     cd = codec(name)
     snr = sc.snr(name) if name in sc.CODES else -10 * np.log10(2 * cd.rate * OWN[name][2] ** 2) + OWN[name][3]
-    cha, msg, _ = awgn_labels(cd, n, snr, seed=61)
-    if n >= 3:
-        cha[0], msg[0] = cd.nq_cha - 1, cd.nq_msg[0] - 1
-        cha[1], msg[1] = 0, 0
-    cha.setflags(write=False)
-    msg.setflags(write=False)
-    return cha, msg
+    return planted_labels(cd, n, snr, 61, noise_free=[0] if n >= 3 else [], zero=[1] if n >= 3 else [])
 
-
-ORACLE = {}      # (code, frames) -> helpers.compare cache: the oracle decodes a batch once per exit mode, all paths share it
 
 SKEW0 = {"LUTLDPC_SKEW": "0"}
 
@@ -110,7 +88,7 @@ def _create(name, kn, monkeypatch):
 def _decode(dec, name, n):
     cd = codec(name)
     cha, msg = labels(name, n)
-    cache = ORACLE.setdefault((name, n), {})
+    cache = oracle_cache(("root_rows", name, n))
     return [compare(cd, dec, cha, msg, psc, pisc, flat=True, cache=cache) for psc, pisc in sc.EXIT_MODES][0]
 
 

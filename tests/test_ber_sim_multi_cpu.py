@@ -24,7 +24,6 @@ sys.path.insert(0, {root!r})
 from lut_ldpc_amd._capi import lib
 argv = {argv!r}
 arr = (C.c_char_p * len(argv))(*[a.encode() for a in argv])
-lib.lutldpc_ber_sim_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
 rc = lib.lutldpc_ber_sim_main(len(argv), arr)
 print("ber_sim rc", rc)
 sys.exit(rc)
@@ -91,7 +90,6 @@ libc = C.CDLL(None)
 libc.getenv.restype = C.c_char_p          # (the C environment itself: os.environ is Python's copy and does not see a setenv of the library)
 argv = {argv!r}
 arr = (C.c_char_p * len(argv))(*[a.encode() for a in argv])
-lib.lutldpc_ber_sim_main.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
 assert libc.getenv(b"LUTLDPC_PLACE") is None
 assert lib.lutldpc_ber_sim_main(len(argv), arr) == 0
 assert libc.getenv(b"LUTLDPC_PLACE") is None, libc.getenv(b"LUTLDPC_PLACE")

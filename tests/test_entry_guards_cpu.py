@@ -8,17 +8,12 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from lut_ldpc_amd._capi import ERR_ARG, ERR_STATE, EventRequest, last_error, lib
+from lut_ldpc_amd._capi import ERR_ARG, ERR_STATE, ChannelCells, EventRequest, last_error, lib
 
 from helpers import oracle_codec, product_decoder
 
 B0 = 3
 u8p, i32p, i64p, f64p = C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)
-
-
-class Cells(C.Structure):
-    _fields_ = [("n_cells", C.c_int32), ("thr", C.POINTER(C.c_uint64)), ("cha_label", u8p), ("msg_label", u8p), ("slicer_neg", u8p),
-                ("cha_label_mirror", u8p), ("msg_label_mirror", u8p)]
 
 
 @pytest.fixture(scope="module")
@@ -35,7 +30,7 @@ def ctx():
     assert len(a["qc"]) == cd.nq_cha - 1 and len(a["qm"]) == cd.nq_msg[0] - 1
     p = {k: v.ctypes.data_as({np.uint8: u8p, np.int32: i32p, np.int64: i64p, np.float64: f64p, np.uint64: C.POINTER(C.c_uint64)}[v.dtype.type])
          for k, v in a.items()}
-    cells = Cells(2, p["thr"], p["lab"], p["lab"], p["lab"], p["lab"], p["lab"])
+    cells = ChannelCells(2, p["thr"], p["lab"], p["lab"], p["lab"], p["lab"], p["lab"])
     yield dict(h=dec._h, N=N, I=I, p=p, cells=cells, keep=a)
     dec.close()
 
@@ -47,13 +42,10 @@ def _request(p, **kw):
 
 
 def _entries(c, stream=1):
-    """name -> call(handle, B) with otherwise valid small arguments; sim_batch and sample_labels have no signature in _capi."""
+    """name -> call(handle, B) with otherwise valid small arguments."""
     p, cells, N, I = c["p"], C.byref(c["cells"]), c["N"], c["I"]
     K, nh = N // 2, (1 + 2 * I) * 2 * 16
     rq = lambda: C.byref(_request(p))
-    vp = C.c_void_p                                # (set here, as every test that calls these two sets its own)
-    lib.lutldpc_decoder_sim_batch.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, u8p, C.c_int, i32p, u8p, u8p]
-    lib.lutldpc_decoder_sample_labels.argtypes = [vp, vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, u8p, u8p, u8p]
     return {
         "decode_batch": lambda h, B: lib.lutldpc_decoder_decode_batch(h, p["u8"], p["u8"], B, p["out"], p["it"]),
         "decode_batch_device": lambda h, B: lib.lutldpc_decoder_decode_batch_device(h, p["u8"], p["u8"], B, p["out"], p["it"], 1),

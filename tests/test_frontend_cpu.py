@@ -5,8 +5,7 @@ import pytest
 
 import lut_ldpc_amd as L
 from lut_ldpc_amd.ber_sim import Comm, sim_snr_point_sharded
-from helpers import CODES, oracle_codec
-from test_host_design_parity import product_codec
+from helpers import CODES, oracle_codec, product_codec
 
 
 @pytest.mark.parametrize("name,mode", [("n500_q4_i8", 0), ("reg36_n1000_mixed", 0), ("c5_minlut", 1)] +

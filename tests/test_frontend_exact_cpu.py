@@ -106,7 +106,7 @@ def test_oracle_sampler_equals_the_reference_on_real_tables(handle, snr):
 
 
 def test_real_dense_tables_are_the_products_and_as_dense_as_stated():
-    from test_host_design_parity import product_codec
+    from helpers import product_codec
     for name, (cfg, dense) in fc.REAL_DENSE.items():
         cells = fc.real_dense(name)
         pcd = product_codec(cfg)

@@ -4,22 +4,7 @@ import numpy as np
 import pytest
 
 import lut_ldpc_amd as L
-from helpers import CODES, CONFIGS, oracle_codec
-
-
-def product_codec(name, device=-1):
-    alist, kw = CONFIGS[name]
-    kw = dict(kw)
-    rank = kw.pop("rank", None)
-    cd = L.Codec(CODES / f"{alist}.alist", known_rank=rank or (32400 if "64800" in alist else 0), device=device)
-    snr = kw.pop("design_snr_db", None)
-    sigma2 = kw.pop("sigma2")
-    if sigma2 is None:
-        sigma2 = 10 ** (-snr / 10) / (2 * cd.rate)
-    if "allow_deg1" in kw:
-        kw["allow_degree_one"] = kw.pop("allow_deg1")
-    cd.design_luts(sigma2=sigma2, **kw)
-    return cd
+from helpers import CODES, oracle_codec, product_codec
 
 
 @pytest.mark.parametrize("name", ["n500_q4_i8", "reg36_n1000_mixed", "reg36_n1000_q3_chklut", "reg36_n1000_rootonly",

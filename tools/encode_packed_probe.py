@@ -25,7 +25,7 @@ import numpy as np
 import bench
 import lut_ldpc_amd as L
 from lut_ldpc_amd import packing
-from lut_ldpc_amd._capi import check, lib
+from lut_ldpc_amd._capi import lib
 
 
 def run(wl, rounds, warmup, frames, say):
@@ -44,7 +44,7 @@ def run(wl, rounds, warmup, frames, say):
     res = {}
 
     def random():
-        check(lib.lutldpc_decoder_encode_random(dec._h, 58, 1, 0, B, None))
+        dec.encode_random(58, 1, 0, B, fetch=False)
 
     entries = {"host": lambda: res.__setitem__("host", dec.encode_packed(words)),
                "dev": lambda: res.__setitem__("dev", dec.encode_packed(d_words)),

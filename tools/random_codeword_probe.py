@@ -6,7 +6,6 @@ copy to the host).  Run it against another build of the library with LUTLDPC_LIB
 device encoder encodes on the host, and reports no encoder time).
 Usage: tools/random_codeword_probe.py [--steps K] [workload ...]"""
 import argparse
-import ctypes as C
 import json
 import sys
 import time
@@ -18,7 +17,7 @@ import numpy as np
 
 import bench
 import lut_ldpc_amd as L
-from lut_ldpc_amd._capi import check, lib
+from lut_ldpc_amd._capi import lib
 
 
 def lib_name():
@@ -47,11 +46,11 @@ def run(wl, steps):
                                              "fer": round(float(st[:, 1].mean()), 5)}
     out["random_over_zero"] = round(out["random"]["frames_per_s"] / out["zero"]["frames_per_s"], 3)
     if hasattr(lib, "lutldpc_decoder_encode_random"):
-        h = C.c_void_p(lib.lutldpc_codec_decoder(cd._h))
-        check(lib.lutldpc_decoder_encode_random(h, 7, 0, 0, B, None))
+        dec = cd.decoder()
+        dec.encode_random(7, 0, 0, B, fetch=False)
         t0 = time.perf_counter()
         for k in range(steps):
-            check(lib.lutldpc_decoder_encode_random(h, 7, 0, k * B, B, None))     # (synchronises)
+            dec.encode_random(7, 0, k * B, B, fetch=False)                       # (synchronises)
         dt = (time.perf_counter() - t0) / steps
         valu_s = B * cd.rank * ((cd.ninfo + 31) // 32) / 7.9e13
         out["encoder"] = {"ms_per_call_host_timed": round(dt * 1e3, 4), "bound_ms": round(max(valu_s, B * cd.nvar / 8 / 8e12) * 1e3, 5)}
