@@ -252,12 +252,23 @@ int lutldpc_decoder_sim_batch(lutldpc_decoder *d, const lutldpc_channel_cells *c
  *
  * set_generator: rows = R rows of ceil(K/64) words (bit j of word w = information bit 64w + j), K + R = nvar; copied to the
  *   device, replaces an earlier generator.  ERR_ARG: rows NULL or K + R != nvar; ERR_STATE: host-only handle;
- *   ERR_UNSUPPORTED: K > 8192.  describe() gains "generator": {"K":.., "R":..}.
+ *   ERR_UNSUPPORTED: K > 8192 (the sparse form below has no such limit).  describe() gains "generator": {"K":.., "R":..}.
+ * set_sparse_generator: the generator as a sparse triangular system, for codes H = [A | T] with T (a permutation of) a triangular
+ *   matrix, of any size: codeword bit K+i = XOR of the codeword bits cols[row_ptr[i] .. row_ptr[i+1]), entries in [0, K+R), any
+ *   order; parity bits may name other parity bits as long as no bit depends on itself.  The library finds the solve order
+ *   (topological sort) and encodes on bit rows (kernels_encode_sparse.hpp).  Works on any handle with K + R = nvar; the handle's
+ *   graph is not looked at.  Either setter replaces an earlier generator of either form; a refused call leaves it in place.
+ *   ERR_ARG: a NULL array, K < 1, R < 0, K + R != nvar, row_ptr not ascending from 0, an entry outside [0, K+R), a row that names
+ *   its own bit, a dependency cycle (the message names one bit on it); then ERR_STATE: host-only handle.
+ *   describe() gains "generator": {"K", "R", "form": "sparse", "terms", "block", "depth"}: the number of terms, the parity bits per
+ *   block of the blocked solve, the bits on the longest chain of parity-on-parity dependencies.
+ *   Every entry below runs the kernels of the form that was set last.
  * encode_random: the codewords of frames frame0 .. frame0+B-1; codewords = host [B*nvar] bytes (0/1), or NULL to keep
  *   them on the device only.  ERR_STATE without a generator.
  * sim_batch_random: lutldpc_decoder_sim_batch with those codewords as the sent ones (same seed / stream for the info bits
  *   and the channel): no host encoding, no upload.  ERR_STATE without a generator. */
 int lutldpc_decoder_set_generator(lutldpc_decoder *d, int K, int R, const uint64_t *rows);
+int lutldpc_decoder_set_sparse_generator(lutldpc_decoder *d, int K, int R, const int32_t *row_ptr /* R+1 */, const int32_t *cols);
 int lutldpc_decoder_encode_random(lutldpc_decoder *d, uint64_t seed, uint32_t stream, uint64_t frame0, int B, uint8_t *codewords);
 int lutldpc_decoder_sim_batch_random(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream,
                                      uint64_t frame0, int B, int K_info, int32_t *frame_stats, uint8_t *cha_out, uint8_t *bits_out);

@@ -21,6 +21,9 @@ typedef struct lutldpc_codec lutldpc_codec;
 
 /* new LDPC_Parity(alist) [+ LDPC_Generator_Systematic(H)] + new LDPC_Code_LUT(H, G)
  * (src/LDPC_BER_Sim.cpp:443-476).  known_rank > 0 skips the GF(2) rank computation.
+ * with_generator: 0 none; 1 the dense generator where the matrix is small enough to eliminate (N * M <= 6.4e8), beyond that the
+ * sparse triangular form where the last M columns of H peel (else an error that names how many peeled); 2 the sparse form at any
+ * size, or an error.  Both forms order the columns alike and give the same codewords.
  * device = -1 gives a host-only object (LUT design, files) that cannot decode. */
 int lutldpc_codec_create(const char *alist_path, int with_generator, int known_rank, int device, lutldpc_codec **out);
 /* LDPC_Code_LUT(filename, G): load a lut_codec.it (src/LDPC_Code_LUT.cpp:568-641) */
@@ -69,7 +72,7 @@ int lutldpc_codec_encode(lutldpc_codec *c, const uint8_t *info, uint8_t *codewor
  * snr_db: frames frame0 .. frame0+B-1 of stream `stream` (= index of the SNR point).  The channel
  * cells are derived from the codec's boundaries; with zero_codeword = 0 the data bits come from the
  * Philox stream and are encoded on the device (lutldpc_decoder_sim_batch_random; needs with_generator;
- * generators of more than 8192 information bits stay on the host encoder).  stats: host [B*4] int32 as
+ * dense generators of more than 8192 information bits whose H has no sparse triangular form stay on the host encoder).  stats: host [B*4] int32 as
  * in lutldpc_decoder_sim_batch. */
 int lutldpc_codec_sim_batch(lutldpc_codec *c, double snr_db, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
                             int zero_codeword, int32_t *stats);

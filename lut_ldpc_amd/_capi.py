@@ -131,6 +131,7 @@ _SIGNATURES = {
     "lutldpc_selftest_resident_source": (C.c_int64, [_vp, C.c_int, C.c_char_p, C.c_int64, C.c_int, C.POINTER(C.c_int32)]),
     "lutldpc_check_stream": (C.c_int, [C.c_uint32]),
     "lutldpc_decoder_set_generator": (C.c_int, [_vp, C.c_int, C.c_int, _u64p]),
+    "lutldpc_decoder_set_sparse_generator": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _ip]),
     "lutldpc_decoder_encode_random": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p]),
     "lutldpc_decoder_sim_batch": (C.c_int, [_vp, _ccp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p, C.c_int, _ip, _u8p, _u8p]),
     "lutldpc_decoder_sample_labels": (C.c_int, [_vp, _ccp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p, _u8p, _u8p]),

@@ -24,7 +24,12 @@ class Codec:
         if codec_path is not None:
             check(lib.lutldpc_codec_load(str(codec_path).encode(), int(device), C.byref(self._h)))
         else:
-            check(lib.lutldpc_codec_create(str(alist_path).encode(), int(with_generator), int(known_rank), int(device), C.byref(self._h)))
+            # with_generator: False / True (dense where the matrix is small enough to eliminate, else the sparse triangular form where
+            # the parity part of H peels) / "sparse" (the sparse form, or an error)
+            if isinstance(with_generator, str) and with_generator != "sparse":
+                raise ValueError('with_generator must be False, True or "sparse"')
+            gen = 2 if with_generator == "sparse" else int(bool(with_generator))
+            check(lib.lutldpc_codec_create(str(alist_path).encode(), gen, int(known_rank), int(device), C.byref(self._h)))
         n, m, e, r = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
         check(lib.lutldpc_codec_dims(self._h, n, m, e, r))
         self.nvar, self.nchk, self.nedges, self.rank = n.value, m.value, e.value, r.value
@@ -214,7 +219,8 @@ class Codec:
         dec = self.decoder()
         if "generator" not in dec.describe():
             raise ValueError("encode_packed needs the generator on the device: make the Codec with with_generator=True on a device "
-                             "(the device encoder holds at most 8192 information bits)")
+                             "(a dense generator holds at most 8192 information bits there; beyond that the parity part of H must "
+                             'peel to the sparse triangular form, which with_generator="sparse" asks for at any size)')
         if isinstance(data, np.ndarray) and data.dtype == np.uint8:
             from .packing import pack_bits
             if data.ndim != 2 or data.shape[1] != self.ninfo:

@@ -81,7 +81,11 @@ void make_describe(lutldpc_decoder *d) {
           << kernels_of(TT_CHK, i, {"cn_minsum_fast_kernel", "lutldpc_jit_pass", d->min_lut ? "cn_minsum_generic_kernel" : "tree_pass_kernel<CHK>"}) << "\"}";
     }
     o << "],\"resident\":" << (resident_active(d) ? 1 : 0) << ",\"skewed_pipeline\":" << ((d->opt.skew && d->skew_ok) ? 1 : 0) << ",\"fused_bucket\":" << d->fused_bucket_id << ",\"compaction\":" << (d->opt.use_compact < 0 ? 2 : d->opt.use_compact) << ",\"compaction_min_groups\":" << compaction_min_groups(d) << ",\"chain_nodes\":" << (d->opt.use_chain ? d->n_chain_nodes : 0) << ",\"placement\":" << d->place_info;
-    if (d->gen_set) o << ",\"generator\":{\"K\":" << d->gen_K << ",\"R\":" << d->gen_R << "}";
+    if (d->gen_set) {
+        o << ",\"generator\":{\"K\":" << d->gen_K << ",\"R\":" << d->gen_R;
+        if (d->gen_sparse) o << ",\"form\":\"sparse\",\"terms\":" << d->sp.terms << ",\"block\":" << d->sp.block << ",\"depth\":" << d->sp.depth;
+        o << "}";
+    }
     {   // the static blobs, comparable between builds without a device.  (An Op has two bytes of padding before `mult`.)
         uint32_t ops = 0;
         for (const Op &op : d->all_ops) ops = crc32(crc32(ops, &op, offsetof(Op, child) + sizeof(op.child)), &op.mult, sizeof(Op) - offsetof(Op, mult));

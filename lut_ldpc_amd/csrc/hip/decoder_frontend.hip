@@ -1,8 +1,13 @@
 // decoder_frontend.hip -- the simulation front end on the device: channel sampler, random-codeword encoder, error counters, the
-// encoder of the caller's packed data bits, and the C-ABI entries built on them.  Home of every kernel of kernels_frontend.hpp and kernels_encode.hpp.
+// encoder of the caller's packed data bits, and the C-ABI entries built on them.  Home of every kernel of kernels_frontend.hpp,
+// kernels_encode.hpp and kernels_encode_sparse.hpp.
 #include "decoder_state.hpp"
 #include "kernels_frontend.hpp"
 #include "kernels_encode.hpp"
+#include "kernels_encode_sparse.hpp"
+#include "../host/sparse_generator.hpp"
+
+static_assert(kSparseBlockRows == lut_ldpc::kSparseBlock, "the block of the host's inverse rows is the block of sparse_phase_b_kernel");
 
 #pragma GCC visibility push(hidden)
 
@@ -50,6 +55,21 @@ int sample_tiles(lutldpc_decoder *d, const ChannelCells &C, uint64_t seed, uint3
     return LUTLDPC_OK;
 }
 
+// The sparse form: the parity rows K .. K+R-1 of `rows` (G frame groups, information rows in place) from the information rows --
+// phase A (s = A u) and phase B (p = T^-1 s, in place), ordered by the stream
+static int launch_sparse_parity(lutldpc_decoder *d, uint8_t *rows, int G) {
+    const int K = d->gen_K, R = d->gen_R, N = d->nvar, DW = d->tile() / 32;
+    if (R < 1) return LUTLDPC_OK;
+    uint32_t *r32 = reinterpret_cast<uint32_t *>(rows);
+    const int gpw = 64 / DW;                    // frame groups per wave of phase A
+    launch_k(sparse_phase_a_kernel, dim3((unsigned)((R + 3) / 4), (unsigned)((G + gpw - 1) / gpw)), dim3(256), 0, d->stream, d->sp.a_ptr.p, d->sp.a_cols.p, K, R, N, G, DW, r32);
+    LAUNCH_CHECK();
+    launch_k(sparse_phase_b_kernel, dim3((unsigned)(G * (DW / kSparseSliceDwords))), dim3(256), 0, d->stream, d->sp.order.p, d->sp.e_ptr.p, d->sp.e_cols.p, d->sp.inv.p,
+             K, d->sp.Rp, N, DW, r32);
+    LAUNCH_CHECK();
+    return LUTLDPC_OK;
+}
+
 // random codewords of frames frame0 .. frame0+B-1 -> d_sent (sent-bit rows of bpad(B) frames; pad frames zero)
 int encode_tiles(lutldpc_decoder *d, uint64_t seed, uint32_t stream, uint64_t frame0, int B) {
     if (!d->gen_set) return fail(LUTLDPC_ERR_STATE, "no generator set: random codewords on the device need lutldpc_decoder_set_generator first");
@@ -58,6 +78,13 @@ int encode_tiles(lutldpc_decoder *d, uint64_t seed, uint32_t stream, uint64_t fr
     HIP_TRY(d->d_sent.alloc((size_t)G * N * RB));
     Timed t(d, LUTLDPC_K_FRONTEND);
     const int K = d->gen_K, R = d->gen_R;
+    if (d->gen_sparse) {
+        const unsigned ny = (unsigned)std::min(64, std::max(1, ((K + 127) / 128 + 3) / 4));
+        launch_k(info_rows_random_kernel, dim3((unsigned)(Bpad / 64), ny), dim3(256), 0, d->stream, K, (uint32_t)seed, (uint32_t)(seed >> 32), stream, frame0, B, N,
+                 d->tile(), d->d_sent.p);
+        LAUNCH_CHECK();
+        return launch_sparse_parity(d, d->d_sent.p, G);
+    }
     const int W128 = (K + 127) / 128, T = (R + kEncTileRows - 1) / kEncTileRows, W32 = (K + 31) / 32;
     // one wave per parity tile (at least one information word per wave where the tiles are fewer); a workgroup is 64 frames
     const unsigned gx = (unsigned)(Bpad / kEncFrames), gy = (unsigned)std::max(1, (std::max(T, (W32 + 7) / 8) + 3) / 4);
@@ -141,7 +168,7 @@ int lutldpc_decoder_set_generator(lutldpc_decoder *d, int K, int R, const uint64
     if (!rows) return fail(LUTLDPC_ERR_ARG, "generator rows are NULL");
     if (K < 1 || R < 0 || K + R != d->nvar) return fail(LUTLDPC_ERR_ARG, "generator: K + R must equal nvar (K >= 1)");
     if (int rc = device_entry(d)) return rc;
-    if (K > kEncMaxInfoBits) return fail(LUTLDPC_ERR_UNSUPPORTED, "generator: more than 8192 information bits (device encoder limit)");
+    if (K > kEncMaxInfoBits) return fail(LUTLDPC_ERR_UNSUPPORTED, "generator: more than 8192 information bits (limit of the dense device encoder; lutldpc_decoder_set_sparse_generator has none)");
     const int WK = (K + 63) / 64, W32p = 4 * ((K + 127) / 128), Rp = (R + kEncTileRows - 1) / kEncTileRows * kEncTileRows;
     std::vector<uint32_t> a((size_t)std::max(Rp, 1) * W32p, 0u);
     for (int i = 0; i < R; i++)
@@ -153,7 +180,31 @@ int lutldpc_decoder_set_generator(lutldpc_decoder *d, int K, int R, const uint64
         }
     HIP_TRY(hipStreamSynchronize(d->stream));           // (a batch in flight may still read the previous generator)
     HIP_TRY(d->d_gen.upload(a));
-    d->gen_K = K; d->gen_R = R; d->gen_W32p = W32p; d->gen_set = true;
+    d->gen_K = K; d->gen_R = R; d->gen_W32p = W32p; d->gen_set = true; d->gen_sparse = false;
+    make_describe(d);
+    return LUTLDPC_OK;
+}
+
+int lutldpc_decoder_set_sparse_generator(lutldpc_decoder *d, int K, int R, const int32_t *row_ptr, const int32_t *cols) {
+    if (!d) return fail(LUTLDPC_ERR_ARG, "NULL decoder");
+    if (!row_ptr || !cols) return fail(LUTLDPC_ERR_ARG, "sparse generator: row_ptr or cols is NULL");
+    if (K < 1 || R < 0 || K + R != d->nvar) return fail(LUTLDPC_ERR_ARG, "sparse generator: K + R must equal nvar (K >= 1, R >= 0)");
+    std::vector<int32_t> order;
+    int depth = 0;
+    const std::string bad = lut_ldpc::sparse_order(K, R, row_ptr, cols, order, depth);
+    if (!bad.empty()) return fail(LUTLDPC_ERR_ARG, "sparse generator: " + bad);
+    if (int rc = device_entry(d)) return rc;
+    lut_ldpc::SparsePacked P;
+    lut_ldpc::sparse_pack(K, R, row_ptr, cols, order, depth, P);
+    const std::string oob = lut_ldpc::sparse_packed_check(P);         // every index the kernels follow, before anything reaches the device
+    if (!oob.empty()) return fail(LUTLDPC_ERR_STATE, "sparse generator: packed arrays out of bounds (" + oob + ")");
+    lutldpc_decoder::SparseGen up;                                     // complete before it replaces the generator in place
+    HIP_TRY(up.a_ptr.upload(P.a_ptr)); HIP_TRY(up.a_cols.upload(P.a_cols)); HIP_TRY(up.order.upload(P.order));
+    HIP_TRY(up.e_ptr.upload(P.e_ptr)); HIP_TRY(up.e_cols.upload(P.e_cols)); HIP_TRY(up.inv.upload(P.inv));
+    up.Rp = P.Rp; up.depth = P.depth; up.terms = (long long)P.terms(); up.block = kSparseBlockRows;
+    HIP_TRY(hipStreamSynchronize(d->stream));           // (a batch in flight may still read the previous generator)
+    d->sp = std::move(up);
+    d->gen_K = K; d->gen_R = R; d->gen_W32p = 0; d->gen_set = true; d->gen_sparse = true;
     make_describe(d);
     return LUTLDPC_OK;
 }
@@ -187,6 +238,8 @@ int lutldpc_decoder_encode_packed(lutldpc_decoder *d, const lutldpc_encode_io *i
     const size_t stride = io->in_stride ? (size_t)io->in_stride : (size_t)W32;
     const uint32_t *src = info;
     uint32_t *dst = out_words;
+    const int G = d->bpad(B) / d->tile();
+    if (d->gen_sparse) HIP_TRY(d->d_enc_rows.alloc((size_t)G * d->nvar * (size_t)(d->tile() / 8)));
     if (!dev) {         // the whole batch, gaps included, up to the last word read
         const size_t words = (size_t)(B - 1) * stride + (size_t)W32;
         HIP_TRY(d->d_llr_in.alloc((words + 1) / 2));
@@ -195,7 +248,18 @@ int lutldpc_decoder_encode_packed(lutldpc_decoder *d, const lutldpc_encode_io *i
         HIP_TRY(d->d_out_words.alloc((size_t)B * (size_t)Wout));
         dst = d->d_out_words.p;
     }
-    {
+    if (d->gen_sparse) {       // bit rows of its own: information rows in, parity where the window reaches it, the window out
+        Timed t(d, LUTLDPC_K_FRONTEND);
+        const unsigned gx = (unsigned)(d->bpad(B) / 64);
+        const unsigned ny_in = (unsigned)std::min(64, std::max(1, (W32 + 4 * kRowsWordChunk - 1) / (4 * kRowsWordChunk)));
+        launch_k(info_rows_packed_kernel, dim3(gx, ny_in), dim3(256), 0, d->stream, K, src, stride, B, d->nvar, d->tile(), d->d_enc_rows.p);
+        LAUNCH_CHECK();
+        if (io->out_first + io->out_count > K && (rc = launch_sparse_parity(d, d->d_enc_rows.p, G))) return rc;
+        const unsigned ny_out = (unsigned)std::min(64, std::max(1, (Wout + 4 * kRowsWordChunk - 1) / (4 * kRowsWordChunk)));
+        launch_k(rows_window_out_kernel, dim3((unsigned)((B + 63) / 64), ny_out), dim3(256), 0, d->stream, d->d_enc_rows.p, B, d->nvar, d->tile(), io->out_first,
+                 io->out_count, dst);
+        LAUNCH_CHECK();
+    } else {
         Timed t(d, LUTLDPC_K_FRONTEND);
         // one wave per output word that holds parity rows (at least one information-only word per wave where those are fewer)
         const int c_last = io->out_first + io->out_count - 1;

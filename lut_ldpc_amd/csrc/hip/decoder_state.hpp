@@ -12,7 +12,7 @@
 //                          pass, graph replay, message trace   (kernels_generic.hpp)
 //   decoder_skew.hip       skewed two-half pipeline through pass_fused_kernel, compaction                     (kernels_compact.hpp)
 //   decoder_resident.hip   LDS-resident decoder (jit_resident.hpp)
-//   decoder_frontend.hip   channel sampler, encoder, error counters and their C-ABI entries    (kernels_frontend.hpp, kernels_encode.hpp)
+//   decoder_frontend.hip   channel sampler, encoders, error counters and their C-ABI entries   (kernels_frontend.hpp, kernels_encode.hpp, kernels_encode_sparse.hpp)
 //   decoder_stats.hip      message-label histograms per dump: edge groups, the counted decode, C-ABI   (kernels_stats.hpp)
 //   decoder_events.hip     failed frames captured on the device: weights, selection, sorted error / syndrome lists, C-ABI   (kernels_events.hpp)
 //   decoder_layout.hip     frame-major <-> rows: labels in (bytes / nibbles), labels out, decided bits out                  (kernels_layout.hpp)
@@ -220,6 +220,17 @@ struct lutldpc_decoder {
     int gen_K = 0, gen_R = 0, gen_W32p = 0;
     DevBuf<uint32_t> d_gen;
     DevBuf<uint8_t> d_sent;
+    // ... or its sparse triangular form (kernels_encode_sparse.hpp; gen_sparse, set by lutldpc_decoder_set_sparse_generator): the
+    // arrays of lut_ldpc::SparsePacked on the device, sp_Rp solve positions in whole blocks; d_enc_rows: the bit rows encode_packed
+    // works on with this form (its own: no entry of a decode reads or writes them)
+    struct SparseGen {
+        int Rp = 0, depth = 0, block = 0;
+        long long terms = 0;
+        DevBuf<int32_t> a_ptr, a_cols, order, e_ptr, e_cols;
+        DevBuf<uint64_t> inv;
+    } sp;
+    bool gen_sparse = false;
+    DevBuf<uint8_t> d_enc_rows;
     // compaction of the surviving frames (kernels_compact.hpp)
     DevBuf<int32_t> d_frame_of, d_perm, d_tmp3, d_ctl, d_slot_of, d_iters_tmp;
     DevBuf<int32_t> d_grp;                           // per frame group: every frame failed the probe of the test on the channel decisions

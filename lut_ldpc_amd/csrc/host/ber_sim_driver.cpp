@@ -139,6 +139,8 @@ LDPC_BER_Sim::LDPC_BER_Sim(const std::string &params, const std::string &base) :
     parity_filename = ini.get("LDPC.parity_filename", "");
     zero_codeword = ini.get("LDPC.zero_codeword", true);
     save_permuted = ini.get("LDPC.save_permuted", false);
+    generator_form = ini.get("LDPC.generator_form", "auto");
+    if (generator_form != "auto" && generator_form != "sparse") throw std::runtime_error("LDPC.generator_form must be auto or sparse");
     parity_check_iter = ini.get("LDPC.parity_check_iter", true);
     max_iter = ini.get("BP.max_iter", 30);
     // build-side: upper bound of the frames per device call.  32768 is the measured optimum on MI355X for the N = 64800 codes
@@ -230,7 +232,7 @@ void LDPC_BER_Sim::load_parity_and_generator() {
     G.reset(new LDPC_Generator_Systematic());
     if (fs::exists(gen_path)) G->load(gen_path.string());
     if (!G->is_initialized()) {
-        G->construct(H.get());
+        G->construct(H.get(), generator_form == "sparse" ? LDPC_Generator_Systematic::SPARSE : LDPC_Generator_Systematic::AUTO);
         if (save_permuted) {
             H->save_alist(parity_path.string());
             { it_file_writer f(gen_path.string()); f.write("Fileversion", 2); f.close(); }

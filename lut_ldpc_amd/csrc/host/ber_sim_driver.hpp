@@ -127,6 +127,7 @@ public:
     int rand_seed_offset = 0, save_codec = 0;
     std::string custom_name, results_prefix = "RES", results_dir = "results", codes_dir = "codes", codec_filename, parity_filename;
     bool zero_codeword = true, save_permuted = false, parity_check_iter = true;
+    std::string generator_form = "auto";     // LDPC.generator_form: auto (dense where the matrix is small enough, else sparse) or sparse
     int max_iter = 30;
     LDPC_BER_Sim_Results results;
     // build-side knobs

@@ -43,7 +43,8 @@ int lutldpc_codec_create(const char *alist_path, int with_generator, int known_r
         if (!alist_path || !out) throw std::invalid_argument("NULL argument");
         std::unique_ptr<lutldpc_codec> c(new lutldpc_codec);
         c->H.reset(new LDPC_Parity(alist_path));
-        if (with_generator) c->G.reset(new LDPC_Generator_Systematic(c->H.get()));
+        if (with_generator != 0 && with_generator != 1 && with_generator != 2) throw std::invalid_argument("with_generator must be 0, 1 or 2 (sparse form)");
+        if (with_generator) c->G.reset(new LDPC_Generator_Systematic(c->H.get(), with_generator == 2 ? LDPC_Generator_Systematic::SPARSE : LDPC_Generator_Systematic::AUTO));
         c->C.reset(new LDPC_Code_LUT());
         c->C->set_device(device);
         // known_rank > 0: rank(H) supplied by the caller (dense elimination of a 64800-column
@@ -184,7 +185,7 @@ int lutldpc_codec_sim_batch(lutldpc_codec *c, double snr_db, uint64_t seed, uint
         if (int rc = lutldpc_check_stream(stream)) return rc;
         const ChannelCellTable cells = channel_cells_at(*c->C, snr_db);
         const lutldpc_channel_cells view = cells.view();
-        // random codewords: made on the device (generators beyond the device encoder's size: on the host, as before)
+        // random codewords: made on the device (dense generators beyond the device encoder's size whose H has no sparse form: on the host)
         if (!zero_codeword && c->C->has_device_generator())
             return lutldpc_decoder_sim_batch_random(c->C->device_handle(), &view, seed, stream, frame0, B, c->C->get_ninfo(), stats, nullptr, nullptr);
         std::vector<unsigned char> cw;
@@ -231,7 +232,8 @@ int lutldpc_codec_encode_random(lutldpc_codec *c, uint64_t seed, uint32_t stream
     return guarded([&] {
         if (!c || !codewords || B <= 0) throw std::invalid_argument("NULL / bad argument");
         if (int rc = lutldpc_check_stream(stream)) return rc;
-        if (!c->C->has_device_generator()) throw std::logic_error("encode_random: the codec has no generator on the device (with_generator, at most 8192 information bits)");
+        if (!c->C->has_device_generator()) throw std::logic_error("encode_random: the codec has no generator on the device (with_generator; a dense generator holds at most 8192 information bits there, "
+                                                                         "beyond that the parity part of H must peel to the sparse triangular form)");
         return lutldpc_decoder_encode_random(c->C->device_handle(), seed, stream, frame0, B, codewords);
     });
 }

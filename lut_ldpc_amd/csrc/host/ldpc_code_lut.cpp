@@ -25,10 +25,49 @@ namespace {
 }  // namespace
 
 // ------------------------------------------------------------------ LDPC_Generator_Systematic
-void LDPC_Generator_Systematic::construct(LDPC_Parity *H) {
+// The sparse form: the last M columns of H peel completely.  Columns are renamed first as the dense construction would order
+// them ([0 .. K-1, N-1, N-2, .. K]: its pivots are exactly these columns, in descending order), so the CSR speaks the new order.
+bool LDPC_Generator_Systematic::construct_sparse(LDPC_Parity *H, int &peeled) {
+    const int N = H->get_nvar(), M = H->get_ncheck(), K = N - M;
+    peeled = 0;
+    if (K < 1) return false;
+    std::vector<std::vector<int>> rows((size_t)M);
+    for (int r = 0; r < M; r++) for (int v : H->get_row(r)) rows[(size_t)r].push_back(v < K ? v : K + (N - 1 - v));
+    SparseRows S;
+    peeled = sparse_peel(N, K, rows, S);
+    if (peeled != M) return false;
+    std::vector<int> perm;            // new column j = old column perm[j]
+    for (int c = 0; c < K; c++) perm.push_back(c);
+    for (int c = N - 1; c >= K; c--) perm.push_back(c);
+    set_sparse(std::move(S));
+    H->permute_cols(perm);
+    return true;
+}
+
+void LDPC_Generator_Systematic::set_sparse(SparseRows &&S) {
+    int depth = 0;
+    if (S.cols.empty()) S.cols.reserve(1);          // (no terms: the pointer must still not be null)
+    const std::string err = sparse_order(S.K, S.R, S.row_ptr.data(), S.cols.data(), order_, depth);
+    if (!err.empty()) throw std::runtime_error("LDPC_Generator_Systematic: sparse form: " + err);
+    S_ = std::move(S);
+    K_ = S_.K; R_ = S_.R; N_ = K_ + R_;
+    A_.clear();
+    sparse_ = true; init_ = true;
+}
+
+void LDPC_Generator_Systematic::construct(LDPC_Parity *H, Form form) {
     const int N = H->get_nvar(), M = H->get_ncheck();
-    if ((double)N * (double)M > 6.4e8)
-        throw std::runtime_error("LDPC_Generator_Systematic: matrix too large for dense elimination; simulate with zero_codeword = true");
+    const bool too_large = (double)N * (double)M > 6.4e8;
+    if (form == SPARSE || too_large) {
+        int peeled = 0;
+        if (construct_sparse(H, peeled)) return;
+        const std::string why = "only " + std::to_string(peeled) + " of its last " + std::to_string(M) + " columns peel (a column peels when it has exactly one entry among "
+                                "the checks not yet removed), so its parity part is not triangular";
+        if (form == SPARSE) throw std::runtime_error("LDPC_Generator_Systematic: the matrix has no sparse triangular form: " + why);
+        throw std::runtime_error("LDPC_Generator_Systematic: matrix too large for dense elimination (N * M > 6.4e8) and without the sparse triangular form: " + why +
+                                 "; simulate with zero_codeword = true");
+    }
+    sparse_ = false; S_ = SparseRows(); order_.clear();
     const size_t W = ((size_t)N + 63) / 64;
     std::vector<uint64_t> A((size_t)M * W, 0);
     for (int r = 0; r < M; r++) for (int v : H->get_row(r)) A[(size_t)r * W + (size_t)(v >> 6)] ^= 1ull << (v & 63);
@@ -75,6 +114,7 @@ void LDPC_Generator_Systematic::encode(const bvec &input, bvec &output) const {
     for (int j = 0; j < K_; j++) if (input[(size_t)j]) u[(size_t)(j >> 6)] |= 1ull << (j & 63);
     output.assign((size_t)N_, 0);
     std::copy(input.begin(), input.end(), output.begin());
+    if (sparse_) { sparse_encode(K_, R_, S_.row_ptr.data(), S_.cols.data(), order_, output.data()); return; }
     for (int i = 0; i < R_; i++) {
         uint64_t acc = 0;
         for (size_t w = 0; w < WK; w++) acc ^= A_[(size_t)i * WK + w] & u[w];
@@ -84,6 +124,13 @@ void LDPC_Generator_Systematic::encode(const bvec &input, bvec &output) const {
 
 void LDPC_Generator_Systematic::save(const std::string &filename) const {
     it_file_writer f(filename, /*truncate=*/false);
+    if (sparse_) {
+        f.write("G_type", std::string("sparse_lutldpc"));
+        f.write("G_N", N_); f.write("G_K", K_); f.write("G_R", R_);
+        f.write("G_row_ptr", std::vector<int>(S_.row_ptr.begin(), S_.row_ptr.end()));
+        f.write("G_cols", std::vector<int>(S_.cols.begin(), S_.cols.end()));
+        return;
+    }
     f.write("G_type", std::string("systematic_lutldpc"));
     f.write("G_N", N_); f.write("G_K", K_); f.write("G_R", R_);
     std::vector<int> words;
@@ -93,7 +140,17 @@ void LDPC_Generator_Systematic::save(const std::string &filename) const {
 
 void LDPC_Generator_Systematic::load(const std::string &filename) {
     it_file_reader f(filename);
+    if (f.has("G_row_ptr") && f.has("G_cols")) {            // G_type "sparse_lutldpc"
+        SparseRows S;
+        S.K = f.get_int("G_K"); S.R = f.get_int("G_R");
+        const std::vector<int> rp = f.get_ivec("G_row_ptr"), cl = f.get_ivec("G_cols");
+        if (S.R < 0 || (int)rp.size() != S.R + 1 || rp.back() != (int)cl.size()) throw std::runtime_error("LDPC_Generator_Systematic::load(): malformed sparse generator");
+        S.row_ptr.assign(rp.begin(), rp.end()); S.cols.assign(cl.begin(), cl.end());
+        set_sparse(std::move(S));
+        return;
+    }
     if (!f.has("G_A")) { init_ = false; return; }
+    sparse_ = false; S_ = SparseRows(); order_.clear();
     N_ = f.get_int("G_N"); K_ = f.get_int("G_K"); R_ = f.get_int("G_R");
     const std::vector<int> words = f.get_ivec("G_A");
     A_.assign(words.size() / 2, 0);
@@ -380,15 +437,32 @@ lutldpc_decoder *LDPC_Code_LUT::device_handle() {
     // the generator (built, or loaded with G_A from a codec file) goes with the decoder: random codewords are made on the device
     dev_generator = false;
     if (device >= 0 && G_defined && G && G->is_initialized()) {
-        const int rc = lutldpc_decoder_set_generator(dev, G->get_K(), G->get_R(), G->get_A().data());
-        if (rc == LUTLDPC_OK) dev_generator = true;
-        else if (rc != LUTLDPC_ERR_UNSUPPORTED) hip_fail("LDPC_Code_LUT: uploading the generator failed");
+        if (G->is_sparse()) {
+            if (lutldpc_decoder_set_sparse_generator(dev, G->get_K(), G->get_R(), G->get_row_ptr().data(), G->get_cols().data()) != LUTLDPC_OK)
+                hip_fail("LDPC_Code_LUT: uploading the sparse generator failed");
+            dev_generator = true;
+        } else {
+            const int rc = lutldpc_decoder_set_generator(dev, G->get_K(), G->get_R(), G->get_A().data());
+            if (rc == LUTLDPC_OK) dev_generator = true;
+            else if (rc != LUTLDPC_ERR_UNSUPPORTED) hip_fail("LDPC_Code_LUT: uploading the generator failed");
+            else if (G->get_R() == nchk) {
+                // a dense generator beyond the dense device encoder: the same codewords through the sparse form, where H (already
+                // in the generator's column order) has it
+                SparseRows S;
+                if (sparse_peel(nvar, G->get_K(), chk_equ_idx, S) == nchk) {
+                    if (lutldpc_decoder_set_sparse_generator(dev, S.K, S.R, S.row_ptr.data(), S.cols.data()) != LUTLDPC_OK)
+                        hip_fail("LDPC_Code_LUT: uploading the sparse generator failed");
+                    dev_generator = true;
+                }
+            }
+        }
     }
     return dev;
 }
 
 void LDPC_Code_LUT::encode_packed(const uint32_t *info, int B, uint32_t *codewords) {
-    if (!has_device_generator()) throw std::logic_error("LDPC_Code_LUT::encode_packed(): no generator on the device (with_generator, at most 8192 information bits)");
+    if (!has_device_generator()) throw std::logic_error("LDPC_Code_LUT::encode_packed(): no generator on the device (with_generator; a dense generator holds at most 8192 information bits there, "
+                                                           "beyond that the parity part of H must peel to the sparse triangular form)");
     lutldpc_encode_io io{};
     io.out_first = 0; io.out_count = nvar;
     if (lutldpc_decoder_encode_packed(dev, &io, info, B, codewords) != LUTLDPC_OK) hip_fail("LDPC_Code_LUT::encode_packed()");

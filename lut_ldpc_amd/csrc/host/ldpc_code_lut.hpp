@@ -11,6 +11,7 @@
 #pragma once
 #include <ostream>
 #include "ldpc_parity.hpp"
+#include "sparse_generator.hpp"
 #include "lut_design.hpp"
 #include "lut_tree.hpp"
 
@@ -28,11 +29,17 @@ namespace lut_ldpc {
 // columns of H so that the first nvar - rank(H) positions carry the information bits.  The
 // column order IT++ would pick is not reproducible (its fork is absent); any valid
 // order gives the same code up to a bit permutation.
+//
+// Two forms.  Dense: the parity rows A of the reduced echelon form, for matrices small enough to eliminate (N * M <= 6.4e8).
+// Sparse (sparse_generator.hpp): for H = [A | T] whose last M columns peel completely, parity bit K+i = XOR of the other entries of
+// its defining check, solved by forward substitution; any size.  Where both exist they give the same column order
+// [0 .. K-1, N-1, N-2, .. K] and, T being invertible, the same codewords.
 class LDPC_Generator_Systematic {
 public:
+    enum Form { AUTO = 0, SPARSE = 2 };      // AUTO: dense where dense works, else sparse where H has it; SPARSE: sparse or an error
     LDPC_Generator_Systematic() = default;
-    explicit LDPC_Generator_Systematic(LDPC_Parity *H) { construct(H); }
-    void construct(LDPC_Parity *H);
+    explicit LDPC_Generator_Systematic(LDPC_Parity *H, Form form = AUTO) { construct(H, form); }
+    void construct(LDPC_Parity *H, Form form = AUTO);
     bool is_initialized() const { return init_; }
     void encode(const bvec &input, bvec &output) const;
     int get_ninfo() const { return K_; }
@@ -40,12 +47,22 @@ public:
     int get_K() const { return K_; }
     int get_R() const { return R_; }
     const std::vector<uint64_t> &get_A() const { return A_; }
+    // ... and of the sparse form (lutldpc_decoder_set_sparse_generator)
+    bool is_sparse() const { return sparse_; }
+    const std::vector<int32_t> &get_row_ptr() const { return S_.row_ptr; }
+    const std::vector<int32_t> &get_cols() const { return S_.cols; }
+    const std::vector<int32_t> &get_solve_order() const { return order_; }
     void save(const std::string &filename) const;      // appended to an existing .it file
     void load(const std::string &filename);
 private:
     bool init_ = false;
     int N_ = 0, K_ = 0, R_ = 0;
-    std::vector<uint64_t> A_;   // R_ rows of ceil(K_/64) words: parity_i = <A_i, info>
+    std::vector<uint64_t> A_;   // dense: R_ rows of ceil(K_/64) words: parity_i = <A_i, info>
+    bool sparse_ = false;
+    SparseRows S_;              // sparse: codeword bit K_+i = XOR of the codeword bits S_.cols[S_.row_ptr[i] ..)
+    std::vector<int32_t> order_;    // ... solved in this order
+    bool construct_sparse(LDPC_Parity *H, int &peeled);
+    void set_sparse(SparseRows &&S);
 };
 using LDPC_Generator = LDPC_Generator_Systematic;
 
@@ -94,8 +111,9 @@ public:
     void lut_decode_batch_dump(const uint8_t *cha, const uint8_t *msg0, int B, uint8_t *bits, int32_t *iters, int level, std::ostream &os);
     lutldpc_decoder *device_handle();        // creates the HIP decoder on first use (and uploads the generator, if any)
     void set_device(int device);             // default 0; -1 = host-only (set-up without a GPU)
-    // the device handle holds the generator: random codewords can be made on the device (false for generators of more
-    // than 8192 information bits, which stay on the host encoder)
+    // the device handle holds the generator: random codewords can be made on the device.  Sparse generators of any size; dense
+    // ones of at most 8192 information bits, and larger ones where H has the sparse form (derived for the device); the rest
+    // stay on the host encoder
     bool has_device_generator() { device_handle(); return dev_generator; }
     // the caller's data encoded on the device (lutldpc_decoder_encode_packed), host memory: info = [B][ceil(ninfo/32)] words, bit j of
     // word w = information bit 32w + j; codewords = [B][ceil(nvar/32)] words in the same bit order.  Throws std::logic_error where

@@ -236,6 +236,16 @@ class Decoder:
         buf = rows if R else np.zeros(1, np.uint64)                 # (R = 0: no row is read, the pointer must not be null)
         check(lib.lutldpc_decoder_set_generator(self._h, int(K), int(R), _p(buf, C.c_uint64)))
 
+    def set_sparse_generator(self, K, R, row_ptr, cols):
+        """The generator as a sparse triangular system (lutldpc_decoder_set_sparse_generator): codeword bit K+i = XOR of the codeword
+        bits cols[row_ptr[i]:row_ptr[i+1]], K + R = nvar, any K.  Replaces an earlier generator of either form."""
+        row_ptr = np.ascontiguousarray(row_ptr, np.int32)
+        cols = np.ascontiguousarray(cols, np.int32)
+        if row_ptr.size != R + 1:
+            raise ValueError("row_ptr must hold R + 1 entries")
+        buf = cols if cols.size else np.zeros(1, np.int32)          # (no terms: nothing is read, the pointer must not be null)
+        check(lib.lutldpc_decoder_set_sparse_generator(self._h, int(K), int(R), _p(row_ptr, C.c_int32), _p(buf, C.c_int32)))
+
     def encode_random(self, seed, stream, frame0, B, fetch=True, out=None):
         """The random codewords of frames frame0 .. frame0+B-1, uint8 [B, nvar]; fetch=False keeps them on the device only."""
         cw = _out(out, B, self.nvar, np.uint8, "out") if fetch else None
