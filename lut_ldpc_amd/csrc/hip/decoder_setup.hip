@@ -301,7 +301,7 @@ static int preload_code_objects(int device) {
     static std::vector<int> done;
     std::lock_guard<std::mutex> lock(mu);
     if (std::find(done.begin(), done.end(), device) != done.end()) return LUTLDPC_OK;
-    HIP_TRY(preload_stream_kernels()); HIP_TRY(preload_frontend_kernels());                             // the units that define kernels of their own
+    HIP_TRY(preload_stream_kernels()); HIP_TRY(preload_frontend_kernels()); HIP_TRY(preload_encode_kernels());                             // the units that define kernels of their own
     HIP_TRY((preload_fused<2, 0>())); HIP_TRY((preload_fused<2, 1>())); HIP_TRY((preload_fused<2, 2>())); HIP_TRY((preload_fused<2, 3>()));
     HIP_TRY((preload_vn_fast<TT_VAR, 1>())); HIP_TRY((preload_vn_fast<TT_VAR, 2>())); HIP_TRY((preload_vn_fast<TT_DEC, 2>()));
     HIP_TRY((preload_cn_fast<2>()));

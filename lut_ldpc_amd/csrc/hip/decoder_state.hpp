@@ -12,7 +12,9 @@
 //                          pass, graph replay, message trace   (kernels_generic.hpp)
 //   decoder_skew.hip       skewed two-half pipeline through pass_fused_kernel, compaction                     (kernels_compact.hpp)
 //   decoder_resident.hip   LDS-resident decoder (jit_resident.hpp)
-//   decoder_frontend.hip   channel sampler, encoders, error counters and their C-ABI entries   (kernels_frontend.hpp, kernels_encode.hpp, kernels_encode_sparse.hpp)
+//   decoder_frontend.hip   Monte-Carlo front end: channel sampler, error counters, sim_batch and sample_labels   (kernels_frontend.hpp)
+//   decoder_encode.hip     the generator record (dense or sparse), information bits -> code bits, the sent-bit rows of a batch
+//                          (from the encoder or from host bytes), C-ABI   (kernels_encode.hpp, kernels_encode_sparse.hpp)
 //   decoder_stats.hip      message-label histograms per dump: edge groups, the counted decode, C-ABI   (kernels_stats.hpp)
 //   decoder_events.hip     failed frames captured on the device: weights, selection, sorted error / syndrome lists, C-ABI   (kernels_events.hpp)
 //   decoder_layout.hip     frame-major <-> rows: labels in (bytes / nibbles), labels out, decided bits out                  (kernels_layout.hpp)
@@ -214,23 +216,25 @@ struct lutldpc_decoder {
     DevBuf<int32_t> d_map;
     DevBuf<uint8_t> d_codewords;                      // upload staging of sent_rows_from_host; no kernel but its conversion reads it
     DevBuf<int32_t> d_stats;
-    // systematic generator of the random codewords made on the device (kernels_encode.hpp): gen_R parity rows over gen_K
-    // information bits, stored as whole 32-row tiles of gen_W32p = 4*ceil(K/128) dwords; d_sent: the sent-bit rows of a batch
-    bool gen_set = false;
-    int gen_K = 0, gen_R = 0, gen_W32p = 0;
-    DevBuf<uint32_t> d_gen;
-    DevBuf<uint8_t> d_sent;
-    // ... or its sparse triangular form (kernels_encode_sparse.hpp; gen_sparse, set by lutldpc_decoder_set_sparse_generator): the
-    // arrays of lut_ldpc::SparsePacked on the device, sp_Rp solve positions in whole blocks; d_enc_rows: the bit rows encode_packed
-    // works on with this form (its own: no entry of a decode reads or writes them)
-    struct SparseGen {
-        int Rp = 0, depth = 0, block = 0;
-        long long terms = 0;
-        DevBuf<int32_t> a_ptr, a_cols, order, e_ptr, e_cols;
-        DevBuf<uint64_t> inv;
-    } sp;
-    bool gen_sparse = false;
-    DevBuf<uint8_t> d_enc_rows;
+    // The systematic generator of the device encoder (decoder_encode.hip), R parity rows over K information bits, in the form it
+    // was set in; a setter builds a complete record and moves it here, which frees the buffers of the one it replaces.
+    // dense (lutldpc_decoder_set_generator, kernels_encode.hpp): the rows as whole 32-row tiles of W32p = 4*ceil(K/128) dwords.
+    // sparse (lutldpc_decoder_set_sparse_generator, kernels_encode_sparse.hpp): the arrays of lut_ldpc::SparsePacked on the device,
+    // Rp solve positions in whole blocks.
+    struct Generator {
+        enum Form { NONE = 0, DENSE, SPARSE } form = NONE;
+        int K = 0, R = 0;
+        struct { int W32p = 0; DevBuf<uint32_t> A; } dense;
+        struct Sparse {
+            int Rp = 0, depth = 0, block = 0;
+            long long terms = 0;
+            DevBuf<int32_t> a_ptr, a_cols, order, e_ptr, e_cols;
+            DevBuf<uint64_t> inv;
+        } sparse;
+    } gen;
+    // d_sent: the sent-bit rows of a batch; d_enc_rows: the bit rows encode_packed works on with the sparse form (its own: no entry
+    // of a decode reads or writes them)
+    DevBuf<uint8_t> d_sent, d_enc_rows;
     // compaction of the surviving frames (kernels_compact.hpp)
     DevBuf<int32_t> d_frame_of, d_perm, d_tmp3, d_ctl, d_slot_of, d_iters_tmp;
     DevBuf<int32_t> d_grp;                           // per frame group: every frame failed the probe of the test on the channel decisions
@@ -458,25 +462,32 @@ inline bool resident_active(const lutldpc_decoder *d) { return d->resident_ok &&
 int resident_plan_for(lutldpc_decoder *d, int G, lutldpc_decoder::ResidentPlan **out);
 int launch_resident(lutldpc_decoder *d, int G, int B);
 
-// ---- decoder_frontend.hip (home of the kernels of kernels_frontend.hpp and kernels_encode.hpp)
+// ---- decoder_frontend.hip (home of the kernels of kernels_frontend.hpp)
 hipError_t preload_frontend_kernels();
 int fill_cells(const lutldpc_channel_cells *c, const lutldpc_decoder *d, ChannelCells &C);
 // sampler -> d_cha_t / d_msg0_t; sent_rows: the sent bits as sent-bit rows (device), null = all-zero codeword
 int sample_tiles(lutldpc_decoder *d, const ChannelCells &C, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *sent_rows);
-int encode_tiles(lutldpc_decoder *d, uint64_t seed, uint32_t stream, uint64_t frame0, int B);       // random codewords -> d_sent
-// the sent bits of a batch in their one device form: *rows = d_sent filled by the encoder (device_codewords) or from the caller's
-// frame-major bytes (codewords, host), or null = all-zero codeword
-int sent_rows_of(lutldpc_decoder *d, const uint8_t *codewords, bool device_codewords, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
-                 const uint8_t **rows);
 // lutldpc_decoder_sim_batch / _random; req != null: the capture of decoder_events.hip on top (lutldpc_decoder_sim_batch_events)
 int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *codewords,
                    bool device_codewords, int K_info, int32_t *frame_stats, uint8_t *cha_out, uint8_t *bits_out, lutldpc_event_request *req = nullptr);
 
+// ---- decoder_encode.hip (home of the kernels of kernels_encode.hpp and kernels_encode_sparse.hpp)
+hipError_t preload_encode_kernels();
+// the entries that encode: LUTLDPC_ERR_STATE with the entry's own text unless the handle has a generator
+inline int require_generator(const lutldpc_decoder *d, const char *text) { return d->gen.form ? LUTLDPC_OK : fail(LUTLDPC_ERR_STATE, text); }
+// random codewords of frames frame0 .. frame0+B-1 -> d_sent (sent-bit rows of bpad(B) frames; pad frames zero)
+int encode_tiles(lutldpc_decoder *d, uint64_t seed, uint32_t stream, uint64_t frame0, int B);
+// host frame-major codewords of B frames (bytes 0 / 1: bit 0 counts) -> d_codewords (upload staging) -> *rows = d_sent;
+// codewords = null: *rows = null, the all-zero codeword
+int sent_rows_from_host(lutldpc_decoder *d, const uint8_t *codewords, int B, const uint8_t **rows);
+// the sent bits of a batch in their one device form: *rows = d_sent filled by the encoder (device_codewords) or from the caller's
+// frame-major bytes (codewords, host), or null = all-zero codeword.  Sampler, error counters, histograms and the capture read it.
+int sent_rows_of(lutldpc_decoder *d, const uint8_t *codewords, bool device_codewords, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
+                 const uint8_t **rows);
+
 // ---- decoder_stats.hip (home of the kernels of kernels_stats.hpp)
 hipError_t preload_stats_kernels();
 int hist_dump(lutldpc_decoder *d);           // one dump of a counted decode: the message rows into d->trace.hist (decode_tiles_launch)
-// host frame-major codewords (bytes 0 / 1) -> d_codewords -> *rows = d_sent; codewords = null: *rows = null (all-zero codeword)
-int sent_rows_from_host(lutldpc_decoder *d, const uint8_t *codewords, int B, const uint8_t **rows);
 
 // ---- decoder_events.hip (home of the kernels of kernels_events.hpp)
 hipError_t preload_events_kernels();

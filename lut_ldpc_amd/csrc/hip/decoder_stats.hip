@@ -87,22 +87,6 @@ static bool decode_moves_labels(const lutldpc_decoder *d, int G) {
     return !resident_active(d) && d->opt.skew && d->skew_ok && d->psc && compaction_on(d, G);
 }
 
-// host frame-major codewords of B frames (bytes 0 / 1: bit 0 counts) -> d_codewords (upload staging) -> *rows = d_sent (sent-bit
-// rows of bpad(B) frames); codewords = null: *rows = null, the all-zero codeword
-int sent_rows_from_host(lutldpc_decoder *d, const uint8_t *codewords, int B, const uint8_t **rows) {
-    *rows = nullptr;
-    if (!codewords) return LUTLDPC_OK;
-    const int G = d->bpad(B) / d->tile(), N = d->nvar;
-    const size_t n_bytes = (size_t)G * N * (d->pack == 2 ? sent_row_bytes<2>() : sent_row_bytes<1>());
-    HIP_TRY(d->d_codewords.alloc((size_t)B * N)); HIP_TRY(d->d_sent.alloc(n_bytes));
-    HIP_TRY(hipMemcpyAsync(d->d_codewords.p, codewords, (size_t)B * N, hipMemcpyHostToDevice, d->stream));
-    Timed t(d, LUTLDPC_K_LAYOUT);
-    PACK_DISPATCH(d, launch_k(bytes_to_sent_rows_kernel<PK>, dim3((unsigned)((n_bytes + 255) / 256)), dim3(256), 0, d->stream, d->d_codewords.p, B, N, n_bytes, d->d_sent.p));
-    LAUNCH_CHECK();
-    *rows = d->d_sent.p;
-    return LUTLDPC_OK;
-}
-
 // restores the exit conditions and the trace sink of a handle on every way out of the counted pass
 struct CountedScope {
     lutldpc_decoder *d; int psc, pisc;
@@ -189,7 +173,7 @@ int lutldpc_decoder_sim_batch_histogram(lutldpc_decoder *d, const lutldpc_channe
                                         int64_t *hist, int64_t hist_cap, int32_t *n_dumps) {
     int nd = 0, rc;
     if ((rc = hist_check_args(d, B, level, mode, n_labels, hist, hist_cap, &nd, stream))) return rc;
-    if (device_codewords && !d->gen_set) return fail(LUTLDPC_ERR_STATE, "sim_batch_histogram: no generator set (lutldpc_decoder_set_generator)");
+    if (device_codewords && (rc = require_generator(d, "sim_batch_histogram: no generator set (lutldpc_decoder_set_generator)"))) return rc;
     ChannelCells C;
     if ((rc = fill_cells(cells, d, C))) return rc;
     const uint8_t *sent_rows = nullptr;

@@ -22,6 +22,48 @@ constexpr int kEncFrames = 64;                 // frames per workgroup (one per 
 constexpr int kEncTileRows = 32;               // parity rows per wave tile (the generator is padded to whole tiles)
 constexpr int kEncMaxInfoBits = 64 * 128;      // 64 Philox blocks per frame: 64 KiB of LDS per workgroup
 
+// 32 bits of 64 frames (x of lane l = the word of frame l) -> 32 rows of 64 bits: lane b < 32 returns row b
+__device__ __forceinline__ uint64_t ballot_rows(uint32_t x, int lane) {
+    uint64_t mine = 0;
+#pragma unroll
+    for (int b = 0; b < 32; b++) {
+        const uint64_t bal = __ballot((x >> b) & 1u);
+        mine = lane == b ? bal : mine;
+    }
+    return mine;
+}
+
+// Philox block c of frame f: the information bits 128c .. 128c + 127, word j = bits 128c + 32j ..
+struct InfoBlock { uint32_t w[4]; };
+__device__ __forceinline__ InfoBlock info_block(uint64_t f, int c, uint32_t stream, uint32_t seed_lo, uint32_t seed_hi) {
+    InfoBlock x = {{(uint32_t)f, (uint32_t)(f >> 32), (uint32_t)c, stream | 0x80000000u}};
+    Philox::gen(x.w, seed_lo, seed_hi);
+    return x;
+}
+
+// information word x of the frame of `lane` in u_lds ([c][lane] blocks of 16 bytes) read as dwords
+__device__ __forceinline__ int u_word_index(int x, int lane) { return ((x >> 2) * kEncFrames + lane) * 4 + (x & 3); }
+
+// acc[r] = the AND of row r of a 32-row tile with the lane's information bits, folded to one dword (its popcount is the parity
+// sum): row(r) = the first dword of row r in A, W128 blocks of four.  Wave-uniform rows: the a words come by scalar loads.
+template <class RowOf>
+__device__ __forceinline__ void tile_product(uint32_t (&acc)[kEncTileRows], const uint4 *u_lds, int W128, int lane, RowOf row) {
+#pragma unroll
+    for (int r = 0; r < kEncTileRows; r++) acc[r] = 0;
+    for (int c = 0; c < W128; c++) {
+        const uint4 u = u_lds[c * kEncFrames + lane];
+#pragma unroll
+        for (int r = 0; r < kEncTileRows; r++) {
+            const uint4 a = *reinterpret_cast<const uint4 *>(row(r) + 4 * c);
+            // acc ^ (a & u): truth table from acc = 0xF0, a = 0xCC, u = 0xAA
+            acc[r] = __builtin_amdgcn_bitop3_b32(acc[r], a.x, u.x, 0x78);
+            acc[r] = __builtin_amdgcn_bitop3_b32(acc[r], a.y, u.y, 0x78);
+            acc[r] = __builtin_amdgcn_bitop3_b32(acc[r], a.z, u.z, 0x78);
+            acc[r] = __builtin_amdgcn_bitop3_b32(acc[r], a.w, u.w, 0x78);
+        }
+    }
+}
+
 // grid (Bpad / 64, ny), 256 threads, dynamic LDS = ceil(K/128) * 64 * 16 bytes.
 // A: Rp = ceil(R/32)*32 rows of W32p = 4*ceil(K/128) dwords, zero beyond R rows / K bits.
 // Wave w of workgroup (x, y) takes the parity tiles t = 4y + w, 4y + w + 4ny, ... and the information words likewise.
@@ -29,6 +71,7 @@ __global__ __launch_bounds__(256) void encode_random_kernel(const uint32_t *__re
                                                             uint32_t stream, uint64_t frame0, int B, int N, int group_frames, uint8_t *__restrict__ sent)
 {
     extern __shared__ uint4 u_lds[];                                   // [c][lane]
+    const uint32_t *u_words = reinterpret_cast<const uint32_t *>(u_lds);
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform: the A addresses below go to scalar loads)
     const int W128 = (K + 127) >> 7, W32 = (K + 31) >> 5, T = (R + kEncTileRows - 1) / kEncTileRows;
@@ -36,9 +79,8 @@ __global__ __launch_bounds__(256) void encode_random_kernel(const uint32_t *__re
     const int fl = fb + lane;
     const uint64_t f = frame0 + (uint64_t)fl;
     for (int c = wv; c < W128; c += 4) {
-        uint32_t x[4] = {(uint32_t)f, (uint32_t)(f >> 32), (uint32_t)c, stream | 0x80000000u};
-        Philox::gen(x, seed_lo, seed_hi);
-        u_lds[c * kEncFrames + lane] = fl < B ? make_uint4(x[0], x[1], x[2], x[3]) : make_uint4(0u, 0u, 0u, 0u);
+        const InfoBlock x = info_block(f, c, stream, seed_lo, seed_hi);
+        u_lds[c * kEncFrames + lane] = fl < B ? make_uint4(x.w[0], x.w[1], x.w[2], x.w[3]) : make_uint4(0u, 0u, 0u, 0u);
     }
     __syncthreads();
     const int RB = sent_row_bytes<1>() * (group_frames / 256);        // 32 * PACK
@@ -46,13 +88,7 @@ __global__ __launch_bounds__(256) void encode_random_kernel(const uint32_t *__re
     const int step = (int)gridDim.y * 4, first = (int)blockIdx.y * 4 + wv;
     // information rows: bit b of word w = node 32w + b
     for (int w = first; w < W32; w += step) {
-        const uint32_t x = reinterpret_cast<const uint32_t *>(&u_lds[(w >> 2) * kEncFrames + lane])[w & 3];
-        uint64_t mine = 0;
-#pragma unroll
-        for (int b = 0; b < 32; b++) {
-            const uint64_t bal = __ballot((x >> b) & 1u);
-            mine = lane == b ? bal : mine;
-        }
+        const uint64_t mine = ballot_rows(u_words[u_word_index(w, lane)], lane);
         const int v = 32 * w + lane;
         if (lane < 32 && v < K) *reinterpret_cast<uint64_t *>(sent + ((size_t)g * N + v) * RB + byte0) = mine;
     }
@@ -60,20 +96,7 @@ __global__ __launch_bounds__(256) void encode_random_kernel(const uint32_t *__re
     for (int t = first; t < T; t += step) {
         const uint32_t *At = A + (size_t)t * kEncTileRows * W32p;
         uint32_t acc[kEncTileRows];
-#pragma unroll
-        for (int r = 0; r < kEncTileRows; r++) acc[r] = 0;
-        for (int c = 0; c < W128; c++) {
-            const uint4 u = u_lds[c * kEncFrames + lane];
-#pragma unroll
-            for (int r = 0; r < kEncTileRows; r++) {
-                const uint4 a = *reinterpret_cast<const uint4 *>(At + (size_t)r * W32p + 4 * c);
-                // acc ^ (a & u): truth table from acc = 0xF0, a = 0xCC, u = 0xAA
-                acc[r] = __builtin_amdgcn_bitop3_b32(acc[r], a.x, u.x, 0x78);
-                acc[r] = __builtin_amdgcn_bitop3_b32(acc[r], a.y, u.y, 0x78);
-                acc[r] = __builtin_amdgcn_bitop3_b32(acc[r], a.z, u.z, 0x78);
-                acc[r] = __builtin_amdgcn_bitop3_b32(acc[r], a.w, u.w, 0x78);
-            }
-        }
+        tile_product(acc, u_lds, W128, lane, [&](int r) { return At + (size_t)r * W32p; });
         uint64_t mine = 0;
 #pragma unroll
         for (int r = 0; r < kEncTileRows; r++) {
@@ -106,7 +129,7 @@ __global__ __launch_bounds__(256) void encode_bits_kernel(const uint32_t *__rest
                                                           size_t in_stride, int B, int out_first, int out_count, uint32_t *__restrict__ out)
 {
     extern __shared__ uint4 u_lds[];                                   // [c][lane]
-    uint32_t *u_words = reinterpret_cast<uint32_t *>(u_lds);           // word x of lane l: u_words[((x >> 2) * 64 + l) * 4 + (x & 3)]
+    uint32_t *u_words = reinterpret_cast<uint32_t *>(u_lds);
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform: the A addresses below go to scalar loads)
     const int W128 = (K + 127) >> 7, W32 = (K + 31) >> 5, Rp = (R + kEncTileRows - 1) / kEncTileRows * kEncTileRows;
@@ -121,7 +144,7 @@ __global__ __launch_bounds__(256) void encode_bits_kernel(const uint32_t *__rest
         for (int x = lane; x < 4 * W128; x += 64) {
             uint32_t v = 0;
             if (live && x < W32) v = src[x] & (x == W32 - 1 ? last_mask : 0xFFFFFFFFu);
-            u_words[((x >> 2) * kEncFrames + j) * 4 + (x & 3)] = v;
+            u_words[u_word_index(x, j)] = v;
         }
     }
     __syncthreads();
@@ -131,8 +154,8 @@ __global__ __launch_bounds__(256) void encode_bits_kernel(const uint32_t *__rest
         uint32_t word = 0;
         if (c0 < K) {                                                  // information bits c0 .. : words x0, x0 + 1 shifted down by s
             const int x0 = c0 >> 5, s = c0 & 31;
-            const uint32_t lo = u_words[((x0 >> 2) * kEncFrames + lane) * 4 + (x0 & 3)];
-            const uint32_t hi = (s && x0 + 1 < W32) ? u_words[(((x0 + 1) >> 2) * kEncFrames + lane) * 4 + ((x0 + 1) & 3)] : 0u;
+            const uint32_t lo = u_words[u_word_index(x0, lane)];
+            const uint32_t hi = (s && x0 + 1 < W32) ? u_words[u_word_index(x0 + 1, lane)] : 0u;
             word = s ? (lo >> s) | (hi << (32 - s)) : lo;
         }
         const int jlo = c0 < K ? K - c0 : 0;                           // bit of the first parity row of this word (>= 32: none)
@@ -142,19 +165,8 @@ __global__ __launch_bounds__(256) void encode_bits_kernel(const uint32_t *__rest
             uint32_t acc[kEncTileRows];
             uint32_t roff[kEncTileRows];                               // row i of the tile in A; past the tile: a row in bounds, masked below
 #pragma unroll
-            for (int i = 0; i < kEncTileRows; i++) { acc[i] = 0; roff[i] = (uint32_t)min(r0 + i, Rp - 1) * (uint32_t)W32p; }
-            for (int c = 0; c < W128; c++) {
-                const uint4 u = u_lds[c * kEncFrames + lane];
-#pragma unroll
-                for (int i = 0; i < kEncTileRows; i++) {
-                    const uint4 a = *reinterpret_cast<const uint4 *>(A + roff[i] + 4 * c);
-                    // acc ^ (a & u): truth table from acc = 0xF0, a = 0xCC, u = 0xAA
-                    acc[i] = __builtin_amdgcn_bitop3_b32(acc[i], a.x, u.x, 0x78);
-                    acc[i] = __builtin_amdgcn_bitop3_b32(acc[i], a.y, u.y, 0x78);
-                    acc[i] = __builtin_amdgcn_bitop3_b32(acc[i], a.z, u.z, 0x78);
-                    acc[i] = __builtin_amdgcn_bitop3_b32(acc[i], a.w, u.w, 0x78);
-                }
-            }
+            for (int i = 0; i < kEncTileRows; i++) roff[i] = (uint32_t)min(r0 + i, Rp - 1) * (uint32_t)W32p;
+            tile_product(acc, u_lds, W128, lane, [&](int i) { return A + roff[i]; });
             uint32_t par = 0;
 #pragma unroll
             for (int i = 0; i < kEncTileRows; i++) par |= (uint32_t)(__builtin_popcount(acc[i]) & 1) << i;
@@ -176,6 +188,23 @@ __global__ __launch_bounds__(256) void sent_rows_to_bytes_kernel(const uint8_t *
     const int f = (int)(i / (size_t)N), v = (int)(i % (size_t)N);
     const int g = f / (256 * PACK), fo = f % (256 * PACK);
     out[i] = (uint8_t)((rows[((size_t)g * N + v) * sent_row_bytes<PACK>() + (fo >> 3)] >> (fo & 7)) & 1u);
+}
+
+// frame-major codewords [B][N] (bytes 0 / 1) -> sent-bit rows: the inverse of sent_rows_to_bytes_kernel.  One thread per byte of
+// the rows (eight frames of one node); pad frames get zeros.
+template <int PACK>
+__global__ __launch_bounds__(256) void bytes_to_sent_rows_kernel(const uint8_t *__restrict__ cw, int B, int N, size_t n_bytes, uint8_t *__restrict__ rows)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_bytes) return;
+    constexpr int RB = sent_row_bytes<PACK>();
+    const size_t row = i / RB;                                        // g * N + v
+    const int g = (int)(row / (size_t)N), v = (int)(row % (size_t)N), f0 = g * 256 * PACK + (int)(i % RB) * 8;
+    uint32_t b = 0;
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+        if (f0 + k < B) b |= (uint32_t)(cw[(size_t)(f0 + k) * N + v] & 1u) << k;
+    rows[i] = (uint8_t)b;
 }
 
 }  // namespace lutldpc

@@ -16,24 +16,13 @@
 //
 // The index lists are wave-uniform wherever one wave works on one row (phase A); in phase B a lane owns (row k of the block, dword).
 #pragma once
-#include "kernels_frontend.hpp"
+#include "kernels_encode.hpp"
 
 namespace lutldpc {
 
-constexpr int kSparseBlockRows = 64;          // = lut_ldpc::kSparseBlock (decoder_frontend.hip asserts it)
+constexpr int kSparseBlockRows = 64;          // = lut_ldpc::kSparseBlock (decoder_encode.hip asserts it)
 constexpr int kSparseSliceDwords = 4;         // a workgroup of phase B owns 128 frames: 4 dwords of every row
 constexpr int kRowsWordChunk = 8;             // consecutive 32-bit words per wave step of the row <-> word kernels
-
-// 32 bits of 64 frames (x of lane l = the word of frame l) -> 32 rows of 64 bits: lane b < 32 returns row b
-__device__ __forceinline__ uint64_t ballot_rows(uint32_t x, int lane) {
-    uint64_t mine = 0;
-#pragma unroll
-    for (int b = 0; b < 32; b++) {
-        const uint64_t bal = __ballot((x >> b) & 1u);
-        mine = lane == b ? bal : mine;
-    }
-    return mine;
-}
 
 // grid (Bpad / 64, ny), 256 threads.  Wave w of workgroup (x, y) takes the Philox blocks c = 4y + w, 4y + w + 4ny, ...
 // Frames >= B get zeros.  rows: at least (Bpad / group_frames) * N * RB bytes.
@@ -48,11 +37,10 @@ __global__ __launch_bounds__(256) void info_rows_random_kernel(int K, uint32_t s
     const int RB = 32 * (group_frames / 256);
     const int g = fb / group_frames, byte0 = (fb % group_frames) >> 3;
     for (int c = (int)blockIdx.y * 4 + wv; c < W128; c += (int)gridDim.y * 4) {
-        uint32_t x[4] = {(uint32_t)f, (uint32_t)(f >> 32), (uint32_t)c, stream | 0x80000000u};
-        Philox::gen(x, seed_lo, seed_hi);
+        const InfoBlock x = info_block(f, c, stream, seed_lo, seed_hi);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            const uint64_t mine = ballot_rows(fl < B ? x[j] : 0u, lane);
+            const uint64_t mine = ballot_rows(fl < B ? x.w[j] : 0u, lane);
             const int v = 128 * c + 32 * j + lane;
             if (lane < 32 && v < K) *reinterpret_cast<uint64_t *>(rows + ((size_t)g * N + v) * RB + byte0) = mine;
         }

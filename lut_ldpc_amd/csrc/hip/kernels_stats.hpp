@@ -88,21 +88,4 @@ __global__ __launch_bounds__(256) void last_dump_kernel(const int32_t *__restric
     last_dump[f] = v;
 }
 
-// frame-major codewords [B][N] (bytes 0 / 1) -> sent-bit rows: the inverse of sent_rows_to_bytes_kernel.  One thread per byte of
-// the rows (eight frames of one node); pad frames get zeros.
-template <int PACK>
-__global__ __launch_bounds__(256) void bytes_to_sent_rows_kernel(const uint8_t *__restrict__ cw, int B, int N, size_t n_bytes, uint8_t *__restrict__ rows)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_bytes) return;
-    constexpr int RB = sent_row_bytes<PACK>();
-    const size_t row = i / RB;                                        // g * N + v
-    const int g = (int)(row / (size_t)N), v = (int)(row % (size_t)N), f0 = g * 256 * PACK + (int)(i % RB) * 8;
-    uint32_t b = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++)
-        if (f0 + k < B) b |= (uint32_t)(cw[(size_t)(f0 + k) * N + v] & 1u) << k;
-    rows[i] = (uint8_t)b;
-}
-
 }  // namespace lutldpc
