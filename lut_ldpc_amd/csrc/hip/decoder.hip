@@ -114,8 +114,6 @@ static const Knob kKnobs[] = {
     KNOB_F("LUTLDPC_JIT", use_jit, "1: run-time generated kernels for shapes the compile-time path does not cover (jit.hpp)"),
     KNOB_I("LUTLDPC_PACK", pack, 1, 1, "1: byte rows even where every alphabet has <= 16 labels (unset: nibble rows there; on them the compile-time variable kernels of degree >= 3 read the root table as packed 64-bit rows, describe(): root_rows)"),
     KNOB_F("LUTLDPC_CHK_FULL", chk_full_labels, "1: generated check kernels on full-label tables; 0: on (sign, magnitude) tables as the reference walks them"),
-    KNOB_F("LUTLDPC_COMPOSE", use_compose, "1: exact table composition for the resident kernel's trees (measured slower: LDS bank conflicts, see compile_all)"),
-    KNOB_I("LUTLDPC_COMPOSE_SPACE", compose_space, 0, 65536, "largest composed table, entries"),
     KNOB_F("LUTLDPC_CHAIN", use_chain, "1: degree-2 nodes between neighbouring checks of a wave are updated inside the check pass (build_fast_index)"),
     KNOB_F("LUTLDPC_LATE_HARD", late_hard, "1: decided bits of early-terminated frames recovered once, at the end, from their frozen messages; 0: stored by every variable pass"),
     KNOB_F("LUTLDPC_FIRST_FROM_NODES", first_from_nodes, "1: the first check pass reads the initial-message rows; 0: init_edges_kernel copies them to the edge rows first"),
@@ -135,7 +133,6 @@ static const Knob kKnobs[] = {
     KNOB_F("LUTLDPC_GRAPH", use_graph, "1: repeated decodes replayed as one hipGraph launch"),
     // ---- compaction of the surviving frames (kernels_compact.hpp)
     KNOB_F("LUTLDPC_COMPACT", use_compact, "1 / 0: on / off (unset: automatic, long iterations only -- compaction_on)"),
-    KNOB_F("LUTLDPC_COMPACT_KEEP", compact_keep, "1: frames that left keep their rows, bits recovered once at the end; 0: recovered at the check point, rows dropped"),
     KNOB_I("LUTLDPC_COMPACT_FIRST", compact_first, 1, INT_MAX, "first iteration with a check point"),
     KNOB_I("LUTLDPC_COMPACT_EVERY", compact_every, 1, INT_MAX, "iterations between check points (unset: 2)"),
     KNOB_R("LUTLDPC_COMPACT_MARGIN", REAL_BELOW, compact_margin, 0, 100, "permute when the remaining iterations pay for it by this factor (0: whenever a group falls idle)"),
@@ -391,13 +388,12 @@ int64_t lutldpc_decoder_device_bytes(lutldpc_decoder *d) {
 }
 const char *lutldpc_decoder_describe(lutldpc_decoder *d) { return d ? d->describe.c_str() : ""; }
 
-// kind + 16: the program of the same tree after table composition (compose_tree)
 // kind + 32 (checks): the program over full labels the generated check kernels run (chk_full_label_program)
 static const Program *find_prog(lutldpc_decoder *d, int kind, int set, int cls) {
-    const bool full = kind == TT_CHK + 32, comp = !full && (kind & 16) != 0;
-    const TreeClassPlan *c = d->tree_class(full ? TT_CHK : kind & 15, set, cls);
+    const bool full = kind == TT_CHK + 32;
+    const TreeClassPlan *c = d->tree_class(full ? TT_CHK : kind, set, cls);
     if (!c || (full && c->full.tab.bytes == 0)) return nullptr;
-    return full ? &c->full.prog : comp ? &c->composed.prog : &c->base.prog;
+    return full ? &c->full.prog : &c->base.prog;
 }
 int lutldpc_selftest_program_eval(lutldpc_decoder *d, int kind, int set, int cls, const int32_t *in, int n_in, int32_t *out, int n_out) {
     if (!d || !in || !out) return fail(LUTLDPC_ERR_ARG, "NULL argument");

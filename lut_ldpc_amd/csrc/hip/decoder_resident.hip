@@ -24,13 +24,13 @@ ResidentSpec resident_spec(const lutldpc_decoder *d, int S, int NT) {
     }
     for (auto &c : d->vclass) R.vcls.push_back({c.deg, (int)c.nodes.size(), c.tidx_off, 0});
     for (auto &c : d->cclass) R.ccls.push_back({c.deg, (int)c.nodes.size(), c.tidx_off, c.tnidx_off});
-    // the composed forms; checks over full labels where that form exists (one instruction per look-up)
+    // the trees as they are; checks over full labels where that form exists (one instruction per look-up)
     const size_t ns = d->tree_plans[TT_VAR].size();
     R.var.assign(ns, {}); R.dec.assign(ns, {}); R.chk.assign(ns, {});
     for (size_t s = 0; s < ns; s++) {
-        for (auto &c : d->tree_set(TT_VAR, (int)s)->cls) R.var[s].push_back(&c.composed);
-        for (auto &c : d->tree_set(TT_DEC, (int)s)->cls) R.dec[s].push_back(&c.composed);
-        for (size_t c = 0; c < d->tree_set(TT_CHK, (int)s)->cls.size(); c++) R.chk[s].push_back(d->chk_form((int)s, (int)c, true));
+        for (auto &c : d->tree_set(TT_VAR, (int)s)->cls) R.var[s].push_back(&c.base);
+        for (auto &c : d->tree_set(TT_DEC, (int)s)->cls) R.dec[s].push_back(&c.base);
+        for (size_t c = 0; c < d->tree_set(TT_CHK, (int)s)->cls.size(); c++) R.chk[s].push_back(d->chk_form((int)s, (int)c));
     }
     return R;
 }

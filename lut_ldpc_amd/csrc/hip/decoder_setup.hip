@@ -178,28 +178,21 @@ static void add_root_rows(lutldpc_decoder *d, FastClassPlan &f, int deg) {
     while (d->all_tables.size() & 3) d->all_tables.push_back(0);
 }
 
-// Compile the trees of one kind of tree set s into one form of every degree class, then the checks' full-label form of it.
-// Base forms: the trees as they are, with their look-ups (all_ops) and the balanced-tree plans.
-// Composed forms: after exact table composition (compose_tree), for the generated LDS-resident kernel.  Off by default
-// (LUTLDPC_COMPOSE=1), measured on MI355X (tools/resident_probe.py): a 4 KB table spreads its 1024 dwords over 32 banks 32 deep --
-// the three-input look-ups run into 3-4-way bank conflicts where a 256-byte table has at most two dwords per bank -- and the halved
-// look-up count does not pay for it: (3,6) N=10000 1.72 -> 1.24 M codewords/s with composition.
-static int add_forms(lutldpc_decoder *d, int kind, int s, bool composed) {
+// Compile the trees of one kind of tree set s -- the trees as they are, with their look-ups (all_ops) and the balanced-tree
+// plans -- into the base form of every degree class, then the checks' full-label form of it.
+static int add_forms(lutldpc_decoder *d, int kind, int s) {
     const std::vector<Tree> &trees = (kind == TT_CHK ? d->chk_trees : d->var_trees)[(size_t)s];
     const std::vector<NodeClass> &cls = kind == TT_CHK ? d->cclass : d->vclass;
     TreeSetPlan &S = *d->tree_set(kind, s);
-    if (!composed) S.cls.assign(cls.size(), TreeClassPlan());
+    S.cls.assign(cls.size(), TreeClassPlan());
     for (size_t i = 0; i < cls.size(); i++) {
         if (cls[i].tree_class >= (int)trees.size()) return fail(LUTLDPC_ERR_ARG, "tree set is missing a degree class");
         const Tree &t = trees[(size_t)cls[i].tree_class];
         TreeClassPlan &c = S.cls[i];
-        ProgramForm &f = composed ? c.composed : c.base;
+        ProgramForm &f = c.base;
         std::string e;
-        if (!(composed ? compile_program(compose_tree(t, kind, d->opt.use_compose ? (uint64_t)d->opt.compose_space : 0), kind, cls[i].deg, f.prog, e)
-                       : compile_program(t, kind, cls[i].deg, f.prog, e)))
-            return fail(LUTLDPC_ERR_UNSUPPORTED, (composed ? "composed tree, degree " : "degree ") + std::to_string(cls[i].deg) + ": " + e);
+        if (!compile_program(t, kind, cls[i].deg, f.prog, e)) return fail(LUTLDPC_ERR_UNSUPPORTED, "degree " + std::to_string(cls[i].deg) + ": " + e);
         append_tables(d, f, false);
-        if (composed) { f.prog.node_tabs.clear(); continue; }      // (they point into the temporary tree)
         if (interp_slot_bytes(f.prog) > 60 * 1024) return fail(LUTLDPC_ERR_UNSUPPORTED, "node program needs more than 60 KiB of LDS slots");     // (the interpreter's)
         c.op_off = (int)d->all_ops.size();
         d->all_ops.insert(d->all_ops.end(), f.prog.ops.begin(), f.prog.ops.end());
@@ -210,12 +203,12 @@ static int add_forms(lutldpc_decoder *d, int kind, int s, bool composed) {
             if (kind == TT_VAR) add_root_rows(d, c.fast, cls[i].deg);
         }
     }
-    if (!composed) S.valid = true;
+    S.valid = true;
     for (size_t i = 0; i < cls.size() && kind == TT_CHK && d->opt.chk_full_labels; i++) {
         ProgramForm f;
-        if (!chk_full_label_program((composed ? S.cls[i].composed : S.cls[i].base).prog, f.prog) || f.prog.tables.empty()) continue;
+        if (!chk_full_label_program(S.cls[i].base.prog, f.prog) || f.prog.tables.empty()) continue;
         append_tables(d, f, true);
-        (composed ? S.cls[i].composed_full : S.cls[i].full) = std::move(f);
+        S.cls[i].full = std::move(f);
     }
     return LUTLDPC_OK;
 }
@@ -250,10 +243,8 @@ int compile_all(lutldpc_decoder *d) {
         const int vkind = !d->var_trees[(size_t)s].empty() && d->var_trees[(size_t)s][0].type == TT_DEC ? TT_DEC : TT_VAR;
         // the order in which the forms reach the blobs is the layout of the blobs
         int rc;
-        if ((rc = add_forms(d, vkind, s, false))) return rc;
-        if (!d->min_lut && (rc = add_forms(d, TT_CHK, s, false))) return rc;
-        if ((rc = add_forms(d, vkind, s, true))) return rc;
-        if (!d->min_lut && (rc = add_forms(d, TT_CHK, s, true))) return rc;
+        if ((rc = add_forms(d, vkind, s))) return rc;
+        if (!d->min_lut && (rc = add_forms(d, TT_CHK, s))) return rc;
     }
     return LUTLDPC_OK;
 }
@@ -325,7 +316,7 @@ static void build_jit(lutldpc_decoder *d) {
             for (size_t i = 0; i < S.cls.size(); i++) {
                 if (kind != TT_CHK && fast_covers(d, S.cls[i].fast, kind, cls[i].deg)) continue;
                 std::string src, log;
-                const bool full = kind == TT_CHK && d->chk_form((int)s, (int)i, false) == &S.cls[i].full;
+                const bool full = kind == TT_CHK && d->chk_form((int)s, (int)i) == &S.cls[i].full;
                 if (!jit_class_source(d, full ? TT_CHK + 32 : kind, s, i, src, log)) { d->jit_log = log; continue; }
                 JitKernel *k = jit_get(d->device, src, log);
                 if (!k) { d->jit_log = "generated-kernel registry full"; continue; }

@@ -134,17 +134,14 @@ static int launch_compaction(lutldpc_decoder *d, HalfRange h, int hf, int ii) {
     if (n <= 0) return LUTLDPC_OK;
     uint8_t *pending = d->d_vfail.p + (size_t)((ii + 1) & 1) * kVfailSlots * d->Bcap;      // flags already raised for the next test
     int32_t *ctl = d->d_ctl.p + 4 * hf;
-    const bool late = late_hard_active(d, true, nullptr);
-    // keep: the frames that left keep their frozen rows (moved behind the active ones), their decided bits are recovered once
-    // at the end of the decode like without compaction; otherwise (LUTLDPC_COMPACT_KEEP=0) they are recovered at the check point
-    // and the rows dropped
-    const bool keep = late && d->opt.compact_keep;
+    // keep (the decided bits are recovered late): the frames that left keep their frozen rows, moved behind the active ones, and
+    // their bits are recovered once at the end of the decode like without compaction.  Otherwise every variable pass has stored
+    // the bits already: only the active frames' rows move, the decided-bit rows are permuted along, the rest is dropped
+    const bool keep = late_hard_active(d, true, nullptr);
     launch_k(compact_decide_kernel, dim3(1), dim3(1024), 0, d->stream, d->d_state.p, s0, n, T, ctl, d->max_iters - 1 - ii, (float)d->opt.compact_margin,
                        d->opt.compact_margin > 0 ? (float)d->opt.compact_min_share : 0.0f, keep ? 1 : 0);
-    // (not keep) the decided bits of the frames that left since the last permutation, before their messages are dropped
-    if (!keep) if (int rc = launch_late_hard(d, true, h.g0, h.G, ctl)) return rc;
     launch_k(compact_apply_kernel, dim3(1), dim3(1024), 0, d->stream, d->d_state.p, d->d_iters.p, d->d_frame_of.p, pending, d->Bcap, s0, n,
-                       d->d_perm.p, d->d_tmp3.p + (size_t)3 * s0, ctl, (late && !keep) ? 1 : 0);
+                       d->d_perm.p, d->d_tmp3.p + (size_t)3 * s0, ctl);
     // (the grid is fixed and small: an empty check point must cost microseconds)
     auto rows = [&](uint8_t *a, int na, uint8_t *b, int nb, int gather) {
         const unsigned blocks = std::min<unsigned>(kPermuteBlocks, (unsigned)((na + nb + kPermuteRows - 1) / kPermuteRows));

@@ -117,9 +117,6 @@ struct TreeClassPlan {
     ProgramForm base;               // the tree as the reference walks it: interpreter and generated streaming kernels
     int op_off = 0;                 // ... and where its look-ups sit in all_ops
     ProgramForm full;               // checks only: over full labels (chk_full_label_program), for the generated check kernels
-    // after exact table composition (compose_tree): fewer, larger look-ups; what the generated LDS-resident kernel runs.
-    // opt.use_compose = 0: the original trees.  composed_full: checks only, as `full`
-    ProgramForm composed, composed_full;
     FastClassPlan fast;             // variable / decision classes: balanced-tree plan of the compile-time kernel
     const JitKernel *jit = nullptr; // generated streaming kernel (jit.hpp, build_jit), null = none
 };
@@ -141,13 +138,12 @@ struct lutldpc_decoder {
         int vn_edges_per_wave = 16, cn_edges_per_wave = 0;     // check side: 0 = automatic (cn_epw)
         int first_from_nodes = 1;
         int use_jit = 1;
-        int use_compose = 0, compose_space = 4096;
         int chk_full_labels = 1;
         int use_chain = 1;
         int use_resident = 1, resident_force_S = 0, resident_force_NT = 0, resident_U = 0, resident_xcd = 1, resident_fm = 1;
         int resident_flag_reduce = -1, resident_cn_persistent = -1, resident_waves_eu = 0;      // -1 = automatic (resident_spec)
         int place_candidates = 16;
-        int use_compact = -1, compact_keep = 1, compact_first = 8, compact_every = 0;           // use: -1 = automatic, every: 0 = automatic
+        int use_compact = -1, compact_first = 8, compact_every = 0;             // use: -1 = automatic, every: 0 = automatic
         double compact_margin = 1.0, compact_min_share = 0.35;
         int use_graph = 1;                                     // also cleared by decode_tiles when a capture fails
         int fused_prio = 0;
@@ -177,11 +173,10 @@ struct lutldpc_decoder {
         return s && cls >= 0 && (size_t)cls < s->cls.size() ? &s->cls[(size_t)cls] : nullptr;
     }
     // the form a generated check kernel runs: over full labels where that form exists, else (sign, magnitude) as the reference
-    const ProgramForm *chk_form(int set, int cls, bool composed) const {
+    const ProgramForm *chk_form(int set, int cls) const {
         const TreeClassPlan *c = tree_class(TT_CHK, set, cls);
         if (!c) return nullptr;
-        const ProgramForm &f = composed ? c->composed_full : c->full;
-        return f.tab.bytes > 0 ? &f : composed ? &c->composed : &c->base;
+        return c->full.tab.bytes > 0 ? &c->full : &c->base;
     }
     TreeSetPlan *tree_set(int kind, int set) { return const_cast<TreeSetPlan *>(const_cast<const lutldpc_decoder *>(this)->tree_set(kind, set)); }
     TreeClassPlan *tree_class(int kind, int set, int cls) { return const_cast<TreeClassPlan *>(const_cast<const lutldpc_decoder *>(this)->tree_class(kind, set, cls)); }
@@ -441,7 +436,7 @@ inline PassBufs pass_bufs(const lutldpc_decoder *d) {
             d->d_fast_idx.p, d->d_msg0_t.p};
 }
 bool late_hard_active(const lutldpc_decoder *d, bool skewed, bool *chain_skip);
-int launch_late_hard(lutldpc_decoder *d, bool skewed, int g0, int G, const int32_t *ctl);
+int launch_late_hard(lutldpc_decoder *d, bool skewed, int g0, int G);
 int decode_tiles(lutldpc_decoder *d, int B);
 int decode_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d_msg0, int B, uint8_t *d_out_bits, int32_t *d_out_iters);
 

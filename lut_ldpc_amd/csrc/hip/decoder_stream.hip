@@ -107,7 +107,7 @@ ClassParams lut_cn_class_params(const lutldpc_decoder *d, int set, size_t ci, Ha
     const bool interp = pass_kernel(d, TT_CHK, set, (int)ci, nz) == KERNEL_INTERPRETER;
     ClassParams P = class_params(d, 0, c, (int)c.nodes.size(), c.idx_off, interp ? d->opt.nodes_per_block : d->npw_cn(c.deg), groups, nz, check);
     // the class blob: of the form the kernel was generated for, or the tree as the reference walks it
-    const TabRef tab = interp ? d->tree_class(TT_CHK, set, (int)ci)->base.tab : d->chk_form(set, (int)ci, false)->tab;
+    const TabRef tab = interp ? d->tree_class(TT_CHK, set, (int)ci)->base.tab : d->chk_form(set, (int)ci)->tab;
     P.tab_off[0] = tab.off; P.tab_len[0] = tab.bytes;
     return P;
 }
@@ -230,7 +230,7 @@ static int launch_pass(lutldpc_decoder *d, int set, int G, int nz, int check, in
 // Are the decided bits of early-terminated frames recovered at the end (hard_from_frozen_kernel) instead of being stored by
 // every variable pass?  Min-sum checks, one message alphabet, and -- in the skewed pipeline -- chain fusion on in every
 // iteration or in none (the nodes it updates get their bits from the check pass).  `chain_skip`: those nodes are skipped by
-// the recovery.  (Compaction drops the messages of finished frames: its check points run the recovery first.)
+// the recovery.  (Compaction then moves the frozen rows of finished frames along: launch_compaction.)
 bool late_hard_active(const lutldpc_decoder *d, bool skewed, bool *chain_skip) {
     if (chain_skip) *chain_skip = false;
     if (!d->opt.late_hard || !d->psc || !d->min_lut) return false;
@@ -252,22 +252,20 @@ bool chain_active(const lutldpc_decoder *d, int set) {
 }
 
 // Decided bits of the frames that left through the exit test, read off their frozen messages (hard_from_frozen_kernel) and, for
-// the nodes updated inside the check pass, off the parity equations (chain_hard_kernel): groups g0 .. g0+G-1; ctl: a compaction
-// check point's control words (the kernels return when it does not permute) or NULL at the end of the decode.
-int launch_late_hard(lutldpc_decoder *d, bool skewed, int g0, int G, const int32_t *ctl) {
+// the nodes updated inside the check pass, off the parity equations (chain_hard_kernel): groups g0 .. g0+G-1, at the end of the decode.
+int launch_late_hard(lutldpc_decoder *d, bool skewed, int g0, int G) {
     bool chain_skip = false;
     if (!late_hard_active(d, skewed, &chain_skip) || G <= 0) return LUTLDPC_OK;
-    const unsigned gx = ctl ? 1024u : 2048u;
-    PACK_DISPATCH(d, launch_k(hard_from_frozen_kernel<PK>, dim3(std::min<unsigned>(gx, (unsigned)((d->nvar + 3) / 4)), (unsigned)G), dim3(256), 0, d->stream, d->d_msgs.p, d->d_hard.p,
+    PACK_DISPATCH(d, launch_k(hard_from_frozen_kernel<PK>, dim3(std::min<unsigned>(2048u, (unsigned)((d->nvar + 3) / 4)), (unsigned)G), dim3(256), 0, d->stream, d->d_msgs.p, d->d_hard.p,
                                         reinterpret_cast<const uint32_t *>(d->d_state.p), d->d_vn_ptr.p, chain_skip ? d->d_chain_internal.p : nullptr, d->nvar, d->E,
-                                        d->Nq_Msg[0] / 2, g0, ctl));
+                                        d->Nq_Msg[0] / 2, g0));
     if (chain_skip)
         for (size_t i = 0; i < d->cclass.size(); i++) {
             if (d->cclass[i].chain_off < 0) continue;
             const int n = (int)d->cclass[i].nodes.size(), npw = d->npw_cn_class(i), runs = (n + npw - 1) / npw;
             PACK_DISPATCH(d, launch_k(chain_hard_kernel<PK>, dim3(std::min<unsigned>(512u, (unsigned)((runs + 3) / 4)), (unsigned)G), dim3(256), 0, d->stream, d->d_hard.p,
                                                 reinterpret_cast<const uint32_t *>(d->d_state.p), d->d_fast_idx.p + d->cclass[i].idx_off, d->d_fast_idx.p + d->cclass[i].chain_off,
-                                                d->d_edge_vn.p, n, d->cclass[i].deg, npw, d->nvar, g0, ctl));
+                                                d->d_edge_vn.p, n, d->cclass[i].deg, npw, d->nvar, g0));
         }
     LAUNCH_CHECK();
     return LUTLDPC_OK;
@@ -363,8 +361,8 @@ static int decode_tiles_launch(lutldpc_decoder *d, int B) {
     }
     {   // decided bits of the frames that left through the exit test, from their frozen messages (see late_hard_active)
         Timed t(d, LUTLDPC_K_LAYOUT);
-        if ((rc = launch_late_hard(d, skewed, 0, G, nullptr))) return rc;
-        if (skewed && d->psc && d->pisc && compaction_on(d, G) && late_hard_active(d, true, nullptr) && d->opt.compact_keep) {
+        if ((rc = launch_late_hard(d, skewed, 0, G))) return rc;
+        if (skewed && d->psc && d->pisc && compaction_on(d, G) && late_hard_active(d, true, nullptr)) {
             // frames that passed the test on the channel decisions may have been moved by a permutation: their decided-bit rows
             // did not travel (no other decided bit exists during the iterations), their channel rows did -- write the bits again
             PACK_DISPATCH(d, launch_k(hard_from_labels_masked_kernel<PK>, dim3(std::min<unsigned>(1024u, (unsigned)((N + 3) / 4)), (unsigned)G), dim3(256), 0, d->stream,

@@ -41,7 +41,6 @@ constexpr int kWave = 64;
 
 // frame states
 constexpr uint32_t ST_ACTIVE = 0, ST_DONE_PSC = 1, ST_DONE_PISC = 2, ST_PAD = 3;
-constexpr uint32_t ST_DONE_SAVED = 4;   // left through the exit test, decided bits already recovered into the hard rows (compaction)
 
 // ---- packing ------------------------------------------------------------------------------------
 // half h of a row dword as four frames, one per byte

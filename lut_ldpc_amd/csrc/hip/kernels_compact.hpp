@@ -8,19 +8,20 @@
 // `frame_of[slot]` remembers where each frame came from, and at the end of the decode the decided bits and
 // iteration codes are put back into the original order.
 //
-// Default flow (rows kept): the message and channel rows of EVERY frame of the groups that were live move -- the
-// frames that just left keep their frozen rows behind the active ones (frames that left earlier sit further back; a
-// stable partition never touches them) -- so the decided bits are recovered once at the end of the decode, exactly
-// as without compaction, and no decided-bit row exists (or moves) before that.
+// One rule picks the flow (launch_compaction): the rows of finished frames are kept exactly when their decided bits are
+// recovered late (late_hard_active: min-sum checks, one message alphabet, LUTLDPC_LATE_HARD=1).
+// Rows kept: the message and channel rows of EVERY frame of the groups that were live move -- the frames that just
+// left keep their frozen rows behind the active ones (frames that left earlier sit further back; a stable partition
+// never touches them) -- so the decided bits are recovered once at the end of the decode, exactly as without
+// compaction, and no decided-bit row exists (or moves) before that.
 // One permutation = compact_apply_kernel (one block per half: prefix sum, small per-slot arrays) +
 // permute_rows_kernel over the E message rows and the N channel rows (one launch).
-// Earlier flow (LUTLDPC_COMPACT_KEEP=0, also used when the decided bits are stored by every variable pass): the
-// decided bits of the frames that left since the last permutation are recovered at the check point
-// (hard_from_frozen_kernel, frames marked ST_DONE_SAVED), only the ACTIVE frames' rows move, and the N decided-bit
-// rows are permuted along.
+// Rows dropped (every variable pass stores the decided bits: LUT checks, changing alphabets, LUTLDPC_LATE_HARD=0): the
+// bits of a finished frame are in the decided-bit rows already, so only the ACTIVE frames' rows move, and the N
+// decided-bit rows are permuted along in a second launch.
 //
 // Whether a permutation pays is decided ON THE DEVICE at every check point (the launch sequence is a fixed hipGraph): it
-// reads and rewrites the rows of the live groups -- about  1.3 x live  group-iterations (earlier flow:
+// reads and rewrites the rows of the live groups -- about  1.3 x live  group-iterations (rows dropped:
 // 0.7 (live + new) + 0.3 GH) -- and saves  (live - new) groups x remaining iterations.  compact_decide_kernel permutes
 // only when a sizeable share of the live groups falls idle at once and the saving exceeds the cost; otherwise the
 // other kernels of the check point return at once (5 us each).
@@ -62,22 +63,18 @@ __global__ __launch_bounds__(1024) void compact_decide_kernel(const uint8_t *__r
     }
 }
 
-// Check point, step 3 (one block; step 2 is hard_from_frozen_kernel on the frames that left since the last permutation):
-// slots [s0, s0 + n): perm[new] = old (absolute slot numbers), active frames first (stable).  Applies the permutation to
-// state / iters / frame_of and to the pending flag buffer (its kVfailSlots copies are ORed into copy 0).  Frames that left
-// through the exit test are marked ST_DONE_SAVED first: their decided bits are in the hard rows now, their messages may go.
-// tmp: 3 * n int32 of scratch.
+// Check point, step 2 (one block): slots [s0, s0 + n): perm[new] = old (absolute slot numbers), active frames first (stable).
+// Applies the permutation to state / iters / frame_of and to the pending flag buffer (its kVfailSlots copies are ORed into
+// copy 0).  tmp: 3 * n int32 of scratch.
 __global__ __launch_bounds__(1024) void compact_apply_kernel(uint8_t *__restrict__ state, int32_t *__restrict__ iters, int32_t *__restrict__ frame_of,
                                                               uint8_t *__restrict__ vfail_pending, int vfail_stride, int s0, int n,
-                                                              int32_t *__restrict__ perm, int32_t *__restrict__ tmp, const int32_t *__restrict__ ctl, int mark_saved)
+                                                              int32_t *__restrict__ perm, int32_t *__restrict__ tmp, const int32_t *__restrict__ ctl)
 {
     __shared__ int wsum[16];
     __shared__ int base_act, base_rest;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     if (ctl[1]) return;                                       // nothing to gain at this check point
     if (t == 0) { base_act = 0; base_rest = ctl[0]; }
-    if (mark_saved)
-        for (int i = t; i < n; i += 1024) if (state[s0 + i] == ST_DONE_PSC) state[s0 + i] = ST_DONE_SAVED;
     __syncthreads();
     // stable partition, 1024 slots at a time
     for (int c0 = 0; c0 < n; c0 += 1024) {

@@ -289,14 +289,12 @@ __global__ __launch_bounds__(256) void hard_from_labels_masked_kernel(const uint
 // (chk_update_minsum, :355-402: sign_msg = sign_prod ^ own sign, sign_prod = 0), i.e. the unanimous sign of the variable
 // node: bit v = (label on the node's first edge < nz).  Exact for min-sum check updates with one message alphabet; the
 // nodes updated inside the check pass (chain fusion, `skip`) keep the bits that pass stored for them.
-// g0: first frame group of the launch (grid.y groups from there); ctl: when given (a compaction check point), ctl[1] != 0
-// means "no permutation at this check point": nothing to save yet.
+// g0: first frame group of the launch (grid.y groups from there).
 template <int PACK>
 __global__ __launch_bounds__(256) void hard_from_frozen_kernel(const uint8_t *__restrict__ msgs, uint8_t *__restrict__ hard,
                                                                const uint32_t *__restrict__ state_w, const int32_t *__restrict__ vn_ptr,
-                                                               const uint8_t *__restrict__ skip, int N, int E, int nz, int g0, const int32_t *__restrict__ ctl)
+                                                               const uint8_t *__restrict__ skip, int N, int E, int nz, int g0)
 {
-    if (ctl && ctl[1]) return;
     const int lane = threadIdx.x & 63, g = g0 + blockIdx.y;
     // which frames of this lane left through the exit test: the same for every node of the group
     uint32_t m[PACK], any = 0;
@@ -304,7 +302,7 @@ __global__ __launch_bounds__(256) void hard_from_frozen_kernel(const uint8_t *__
     for (int h = 0; h < PACK; h++) { m[h] = swar_zero_mask(state_w[frame_word<PACK>(g, lane, h)] ^ (ST_DONE_PSC * 0x01010101u)); any |= m[h]; }
     if (wave_all_zero(any)) return;
     const uint32_t smask = pack_masks<PACK>(m);
-    // a small fixed grid walks the nodes (a check point that does not permute must cost microseconds)
+    // a small fixed grid walks the nodes
     const int w0 = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), step = (int)gridDim.x * 4;
 #pragma unroll 4
     for (int v = w0; v < N; v += step) {
@@ -329,9 +327,8 @@ __global__ __launch_bounds__(256) void hard_from_frozen_kernel(const uint8_t *__
 template <int PACK>
 __global__ __launch_bounds__(256) void chain_hard_kernel(uint8_t *__restrict__ hard, const uint32_t *__restrict__ state_w, const int32_t *__restrict__ edges,
                                                          const int32_t *__restrict__ links, const int32_t *__restrict__ edge_vn, int n_nodes, int deg, int npw, int N,
-                                                         int g0, const int32_t *__restrict__ ctl)
+                                                         int g0)
 {
-    if (ctl && ctl[1]) return;
     const int lane = threadIdx.x & 63, g = g0 + blockIdx.y;
     uint32_t m[PACK], any = 0;
 #pragma unroll

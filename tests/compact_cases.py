@@ -24,16 +24,13 @@ K_INFO, R_GEN = K - 1, M + 1
 #      happens whenever it frees a group
 BASE = {"LUTLDPC_RESIDENT": "0", "LUTLDPC_COMPACT": "1", "LUTLDPC_COMPACT_FIRST": "2", "LUTLDPC_COMPACT_EVERY": "2", "LUTLDPC_COMPACT_MARGIN": "0"}
 CHECK_POINTS = [cp for cp in range(2, ITERS, 2) if cp < ITERS - 2]
-#      variant -> knobs beside BASE: the frames that left keep / drop their rows, nibble / byte rows, decided bits late / every pass
+#      variant -> knobs beside BASE: nibble / byte rows, decided bits late (the frames that left keep their rows) / stored by every
+#      pass (they drop them)
 VARIANTS = {
-    "base": {"LUTLDPC_COMPACT_KEEP": "1"},
-    "pack1": {"LUTLDPC_COMPACT_KEEP": "1", "LUTLDPC_PACK": "1"},
-    "keep0": {"LUTLDPC_COMPACT_KEEP": "0"},
-    "keep0_pack1": {"LUTLDPC_COMPACT_KEEP": "0", "LUTLDPC_PACK": "1"},
-    "late0": {"LUTLDPC_COMPACT_KEEP": "1", "LUTLDPC_LATE_HARD": "0"},
-    "late0_pack1": {"LUTLDPC_COMPACT_KEEP": "1", "LUTLDPC_LATE_HARD": "0", "LUTLDPC_PACK": "1"},
-    "keep0_late0": {"LUTLDPC_COMPACT_KEEP": "0", "LUTLDPC_LATE_HARD": "0"},
-    "keep0_late0_pack1": {"LUTLDPC_COMPACT_KEEP": "0", "LUTLDPC_LATE_HARD": "0", "LUTLDPC_PACK": "1"},
+    "base": {},
+    "pack1": {"LUTLDPC_PACK": "1"},
+    "late0": {"LUTLDPC_LATE_HARD": "0"},
+    "late0_pack1": {"LUTLDPC_LATE_HARD": "0", "LUTLDPC_PACK": "1"},
 }
 FULL_MATRIX = ("base", "pack1")            # every entry; the other variants: the decode entries and sim_batch
 OTHER = tuple(v for v in VARIANTS if v not in FULL_MATRIX)

@@ -54,7 +54,7 @@ for c in range(cases):
         N = min(N, 700)
         B = int(rng.integers(4, 66)) * 512 - int(rng.integers(0, 400))
         os.environ.update(LUTLDPC_COMPACT="1", LUTLDPC_COMPACT_MARGIN="0", LUTLDPC_COMPACT_FIRST=str(int(rng.integers(1, 5))),
-                          LUTLDPC_COMPACT_EVERY=str(int(rng.integers(1, 4))), LUTLDPC_COMPACT_KEEP=str(int(rng.integers(0, 2))))
+                          LUTLDPC_COMPACT_EVERY=str(int(rng.integers(1, 4))))
     free_frames = rng.integers(0, B, 3)
     sig = float(rng.uniform(0.45, 0.9))
     snr_off = float(rng.uniform(-0.3, 1.5))
@@ -129,7 +129,6 @@ for c in range(cases):
         os.environ["LUTLDPC_RESIDENT_S"] = str(int(r3.integers(1, 9)))
         os.environ["LUTLDPC_RESIDENT_NT"] = str(int(r3.choice([256, 512, 768, 1024])))
         os.environ["LUTLDPC_RESIDENT"] = "2"
-        os.environ["LUTLDPC_COMPOSE"] = str(int(r3.integers(0, 2)))
     try:
         dec = product_decoder(cd)
     except Exception as e:
@@ -137,7 +136,7 @@ for c in range(cases):
     try:
         for psc, pisc in [(True, True), (True, False), (False, False)]:
             it = compare(cd, dec, cha, msg, psc, pisc, flat=COMPACT)
-        print(f"case {c}: N={N} M={M} dv={sorted(set(dv.tolist()))} dc={sorted(set(dc.tolist()))} nq={nqc}/{nqm} I={I} B={B} bucket={dec.describe()['fused_bucket']} skew={dec.describe()['skewed_pipeline']} resident={dec.describe()['resident']}{(' geom ' + os.environ['LUTLDPC_RESIDENT_S'] + 'x' + os.environ['LUTLDPC_RESIDENT_NT'] + ' compose ' + os.environ['LUTLDPC_COMPOSE']) if GEOM else ''} {extra if extra else ''} nq_msg={sorted(set(nq_vec.tolist()))} {('compaction ' + str(dec.describe()['compaction']) + ' first/every/keep ' + os.environ['LUTLDPC_COMPACT_FIRST'] + '/' + os.environ['LUTLDPC_COMPACT_EVERY'] + '/' + os.environ['LUTLDPC_COMPACT_KEEP']) if COMPACT else ''} ok, iteration codes {sorted(set(it.tolist()))[:5]}")
+        print(f"case {c}: N={N} M={M} dv={sorted(set(dv.tolist()))} dc={sorted(set(dc.tolist()))} nq={nqc}/{nqm} I={I} B={B} bucket={dec.describe()['fused_bucket']} skew={dec.describe()['skewed_pipeline']} resident={dec.describe()['resident']}{(' geom ' + os.environ['LUTLDPC_RESIDENT_S'] + 'x' + os.environ['LUTLDPC_RESIDENT_NT']) if GEOM else ''} {extra if extra else ''} nq_msg={sorted(set(nq_vec.tolist()))} {('compaction ' + str(dec.describe()['compaction']) + ' first/every ' + os.environ['LUTLDPC_COMPACT_FIRST'] + '/' + os.environ['LUTLDPC_COMPACT_EVERY']) if COMPACT else ''} ok, iteration codes {sorted(set(it.tolist()))[:5]}")
     except AssertionError as e:
         bad += 1
         print(f"case {c}: MISMATCH N={N} M={M} dv={dvc} nq={nqc}/{nqm} I={I} B={B}: {str(e)[:200]}")

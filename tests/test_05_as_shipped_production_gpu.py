@@ -26,12 +26,14 @@ def _ira_codec(K, M, dv, max_iters, sig):
 def test_ira_code_chain_fusion_with_compaction(monkeypatch, K, M, dv, bucket, sig, keep):
     """A dual-diagonal code (check degrees 8 and 14: first and middle bucket of the fused kernel), compaction forced on with a
     check point every second iteration and no cost margin (frames move several times per decode), nine and ten frame groups
-    (halves of 5 + 4 / 5 + 5, ragged last group), both row flows (the frames that left keep their rows / drop them), all three
-    exit modes, EVERY frame against the oracle.  Some frames are noise-free: they pass the test on the channel decisions and are
-    moved by the first permutation like every other finished frame."""
+    (halves of 5 + 4 / 5 + 5, ragged last group), both row flows (keep = 1: the decided bits are recovered late and the frames that
+    left keep their rows; keep = 0: LUTLDPC_LATE_HARD=0, every variable pass stores the bits and they drop them), all three exit modes,
+    EVERY frame against the oracle.  Some frames are noise-free: they pass the test on the channel decisions and are moved by the
+    first permutation like every other finished frame."""
     monkeypatch.setenv("LUTLDPC_RESIDENT", "0")              # the streaming path: this small code would otherwise be decoded out of LDS
     monkeypatch.setenv("LUTLDPC_COMPACT", "1")
-    monkeypatch.setenv("LUTLDPC_COMPACT_KEEP", keep)
+    if keep == "0":
+        monkeypatch.setenv("LUTLDPC_LATE_HARD", "0")
     monkeypatch.setenv("LUTLDPC_COMPACT_FIRST", "2")
     monkeypatch.setenv("LUTLDPC_COMPACT_EVERY", "2")
     monkeypatch.setenv("LUTLDPC_COMPACT_MARGIN", "0")

@@ -2,7 +2,7 @@
 kernel -- all iterations of src/LDPC_Code_LUT.cpp:259-353 inside, sets of 8 frames retired one by one.  The default path for the
 small BASELINE configurations (C1, C2, C5); here its own shapes: every workgroup geometry (sets per workgroup x threads), batches
 that are not a multiple of a set or of a frame group, frames that pass the test on the channel decisions, byte rows, non-uniform
-alphabets with reused LUT stages, CHKTREE check updates, table composition on and off.  Bit-exact against the oracle."""
+alphabets with reused LUT stages, CHKTREE check updates.  Bit-exact against the oracle."""
 import numpy as np
 import pytest
 
@@ -38,21 +38,6 @@ def test_resident_geometries_and_shapes(name, B, snr, geom, monkeypatch):
     it = compare(cd, dec, cha, msg, True, True)
     assert (it == 0).sum() >= 1
     compare(cd, dec, cha, msg, True, False)
-    compare(cd, dec, cha, msg, False, False)
-    dec.close()
-
-
-@pytest.mark.parametrize("name,B,snr", [("n500_q4", 700, 1.9), ("reg36_n10000_q4", 300, 1.9), ("c5_chklut", 100, 4.2)])
-def test_resident_with_table_composition(name, B, snr, monkeypatch):
-    """LUTLDPC_COMPOSE=1: the node programs of the composed trees (three-input look-ups into 4 KB tables: fewer look-ups, more bank
-    conflicts -- measured slower, off by default) -- same bits, same iteration codes."""
-    monkeypatch.setenv("LUTLDPC_COMPOSE", "1")
-    monkeypatch.setenv("LUTLDPC_RESIDENT", "2")                # (wide CHKTREE checks go through the streaming kernels unless forced)
-    cd = oracle_codec(name)
-    dec = product_decoder(cd)
-    assert dec.describe()["resident"] == 1
-    cha, msg, _ = awgn_labels(cd, B, snr, seed=5, mode=1 if name.startswith("c5") else 0)
-    compare(cd, dec, cha, msg, True, True)
     compare(cd, dec, cha, msg, False, False)
     dec.close()
 

@@ -153,12 +153,13 @@ def test_decode_at_every_alphabet_matches_oracle(name, snr, modes, path, monkeyp
     dec.close()
 
 
-@pytest.mark.parametrize("keep", ["0", "1"])
-def test_chain_fusion_and_compaction_with_a_shrinking_alphabet(keep, monkeypatch):
+@pytest.mark.parametrize("late", ["0", "1"])
+def test_chain_fusion_and_compaction_with_a_shrinking_alphabet(late, monkeypatch):
     """Dual-diagonal code, schedule 8 8 8 8 4 4 4 2: chain fusion loads each iteration's degree-2 root table, compaction of the
-    surviving frames forced at every second iteration (check points across the alphabet changes), ten frame groups."""
+    surviving frames forced at every second iteration (check points across the alphabet changes), ten frame groups.  The alphabet
+    changes, so every variable pass stores the decided bits and the frames that left drop their rows whatever LUTLDPC_LATE_HARD says."""
     monkeypatch.setenv("LUTLDPC_RESIDENT", "0")
-    for k, v in (("COMPACT", "1"), ("COMPACT_FIRST", "2"), ("COMPACT_EVERY", "2"), ("COMPACT_MARGIN", "0"), ("COMPACT_KEEP", keep)):
+    for k, v in (("COMPACT", "1"), ("COMPACT_FIRST", "2"), ("COMPACT_EVERY", "2"), ("COMPACT_MARGIN", "0"), ("LATE_HARD", late)):
         monkeypatch.setenv("LUTLDPC_" + k, v)
     K, M = 1600, 400
     cd = designed_codec("test15-ira-ex8421", lambda path: write_ira_alist(path, K, M, 3, seed=K), sigma=0.5, max_iters=8, nq_msg=[8, 8, 8, 8, 4, 4, 4, 2])

@@ -182,7 +182,7 @@ def test_compaction_path(monkeypatch):
     """A dual-diagonal code at nine frame groups with compaction forced on as in tests/test_05: frames move between rows during
     the decode; the capture reads the rows after they are back in the caller's order."""
     from helpers import awgn_labels, designed_codec, write_ira_alist
-    for k, v in (("LUTLDPC_RESIDENT", "0"), ("LUTLDPC_COMPACT", "1"), ("LUTLDPC_COMPACT_KEEP", "1"), ("LUTLDPC_COMPACT_FIRST", "2"),
+    for k, v in (("LUTLDPC_RESIDENT", "0"), ("LUTLDPC_COMPACT", "1"), ("LUTLDPC_COMPACT_FIRST", "2"),
                  ("LUTLDPC_COMPACT_EVERY", "2"), ("LUTLDPC_COMPACT_MARGIN", "0")):
         monkeypatch.setenv(k, v)
     K, M, sig, I = 840, 420, 0.62, 16

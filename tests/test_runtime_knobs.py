@@ -88,3 +88,20 @@ def test_chain_fusion_switch(clean_env):
     d = _describe("dvbs2_q4_i6")
     assert d["chain_nodes"] == 0 and not any(c["chain_nodes"] for c in d["cn_classes"])
     assert all(c["nodes_per_wave"] == 42 // c["deg"] for c in d["cn_classes"])
+
+
+def test_removed_knobs_change_nothing(clean_env):
+    """LUTLDPC_COMPOSE, LUTLDPC_COMPOSE_SPACE and LUTLDPC_COMPACT_KEEP selected variants that measured slower and are gone with
+    their code: setting them leaves describe() and the generated resident sources as a clean environment gives them."""
+    def snapshot():
+        out = [_describe("n500_q4")]
+        for name, G in (("reg36_n1000_mixed", 1), ("c5_chklut", 2)):
+            dec = product_decoder(oracle_codec(name), device=-1)
+            out.append(dec.resident_source(G))
+            dec.close()
+        return out
+
+    clean = snapshot()
+    for k, v in (("LUTLDPC_COMPOSE", "1"), ("LUTLDPC_COMPOSE_SPACE", "64"), ("LUTLDPC_COMPACT_KEEP", "0")):
+        clean_env.setenv(k, v)
+    assert snapshot() == clean

@@ -137,10 +137,10 @@ def test_compaction_with_many_groups(env, B, monkeypatch):
 
 
 def test_compaction_that_drops_the_rows_of_finished_frames(monkeypatch):
-    """LUTLDPC_COMPACT_KEEP=0: the earlier flow -- decided bits recovered at every permuting check point, only the active frames'
-    rows moved, decided-bit rows permuted along."""
+    """LUTLDPC_LATE_HARD=0: every variable pass stores the decided bits, so a permutation moves only the active frames' rows and
+    permutes the decided-bit rows along."""
     monkeypatch.setenv("LUTLDPC_COMPACT", "1")
-    monkeypatch.setenv("LUTLDPC_COMPACT_KEEP", "0")
+    monkeypatch.setenv("LUTLDPC_LATE_HARD", "0")
     monkeypatch.setenv("LUTLDPC_COMPACT_FIRST", "3")
     monkeypatch.setenv("LUTLDPC_COMPACT_EVERY", "2")
     monkeypatch.setenv("LUTLDPC_COMPACT_MARGIN", "0")

@@ -8,7 +8,7 @@ OUTDIR/<sha256>.hip holds one distinct text each, OUTDIR/index.txt one line `con
 `resident` lines carry the frame groups G and SxNT in the set / class columns (hash `refused`: resident_pick declined).
 OUTDIR/describe.txt holds describe() of every configuration without its build stamp and source hash (its "static" section carries
 sizes and CRC-32s of the op, table and index blobs), OUTDIR/program_stats.txt one line per (kind, set, class) that answers
-Decoder.program_stats, kinds 0 / 1 / 2, + 16 (composed) and 33.
+Decoder.program_stats, kinds 0 / 1 / 2 and 33.
 --compile runs hiprtc (gfx950, the options of jit_compile) on every distinct text and stores OUTDIR/<sha256>.co.
 The LUTLDPC_* knobs of the environment apply, LUTLDPC_LIB selects another build: call it once per setting to sweep them."""
 import ctypes as C
@@ -44,7 +44,7 @@ for name, codec in codecs:
     desc = {k: v for k, v in dec.describe().items() if k not in ("build", "kernel_sources")}
     describes.append(f"{name} {json.dumps(desc, sort_keys=True)}")
     n_cls = max(len(desc["vn_classes"]), len(desc["cn_classes"]))
-    for kind in (0, 1, 2, 16, 17, 18, 33):
+    for kind in (0, 1, 2, 33):
         for s in range(cd.n_sets()):
             for cls in range(n_cls):
                 try:
