@@ -146,6 +146,11 @@ int lutldpc_decoder_decode_batch_trace(lutldpc_decoder *d, const uint8_t *cha, c
  * messages by mode (0 = CONT: quant_nonlin(llr, qb_Msg); 1 = QCHA: cha2msg_map[label]),
  * then lut_decode.  llr[B*nvar] double, host memory.  out_bits holds all nvar bits per
  * frame; the systematic part is the first nvar - rank(H) of them (:225).
+ * The quantiser is the one of lutldpc_decoder_decode_llr_packed below, on float64.  The boundary arrays are taken as the caller
+ * holds them, sorted or not: the label is the number of LEADING boundaries below x on ANY array (the loop of quant_nonlin stops at
+ * the first boundary that x does not exceed; a NaN boundary stops every x), which the entry turns into the plain count over the
+ * running maxima.  Mode 0 ignores a given map; mode 1 ignores qb_Msg and n_qb_Msg, and a cha2msg_map entry outside
+ * [0, Nq_Msg[0]) is LUTLDPC_ERR_ARG (no label outside its alphabet reaches the decoder).
  */
 int lutldpc_decoder_decode_llr_batch(lutldpc_decoder *d, const double *llr, int B,
                                      const double *qb_Cha, int n_qb_Cha,
@@ -154,10 +159,11 @@ int lutldpc_decoder_decode_llr_batch(lutldpc_decoder *d, const double *llr, int 
                                      uint8_t *out_bits, int32_t *out_iters);
 
 /*
- * lutldpc_decoder_decode_llr_batch for receivers: the same quantisation and decode, bit for bit, for soft values as a demapper
+ * lutldpc_decoder_decode_llr_batch for receivers: the same quantiser and decode, bit for bit, for soft values as a demapper
  * holds them -- float64, float32, float16 or int8 with a scale, in host memory or already on the device -- and a window of the
  * decided bits out at one bit each.  The values are quantised straight into both label row sets (no frame-major labels in
- * between), the decode is that of every other batch entry.
+ * between), the decode is that of every other batch entry.  Unlike that entry this one refuses boundaries that are not
+ * non-decreasing or hold NaN, and a map in mode 0.
  *   llr        [B][frame_stride] elements of io->dtype; host memory (io->on_device = 0) or device memory (1), aligned to its element
  *              size.  Elements nvar .. frame_stride-1 of a frame are never read.
  *   out_words  [B][ceil(out_count/32)] uint32 as lutldpc_decoder_decode_batch_packed, or NULL

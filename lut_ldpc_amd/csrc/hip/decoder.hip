@@ -182,12 +182,13 @@ lutldpc_decoder::~lutldpc_decoder() {
 }
 
 // ----------------------------------------------------------------------------- decode entries
-// frame-major labels of B frames in d_in_cha / d_in_msg (uploaded, or quantised there) -> decided bits and iteration codes on the
-// host.  decode_device leaves the bits in the staging buffer in either of its branches; synchronises.
+// frame-major labels of B frames in d_in_cha / d_in_msg (labels_from_host) -> decided bits and iteration codes on the host.
+// decode_device leaves the bits in the staging buffer in either of its branches; synchronises.  The dumps of a traced decode
+// ([B][E] each, trace_dump) leave through the same buffer before the bits do: it is sized for them here, where its pointer is taken.
 static int decode_staged_labels(lutldpc_decoder *d, int B, uint8_t *out_bits, int32_t *out_iters) {
     const size_t n = (size_t)B * (size_t)d->nvar;
-    HIP_TRY(d->d_out_bits.alloc(n)); HIP_TRY(d->d_out_iters.alloc((size_t)B));
-    int rc = decode_device(d, d->d_in_cha.p, d->d_in_msg.p, B, d->d_out_bits.p, d->d_out_iters.p);
+    HIP_TRY(d->d_out_bits.alloc(d->trace.level > 1 ? (size_t)B * (size_t)d->E : n));
+    int rc = decode_device(d, d->d_in_cha.p, d->d_in_msg.p, B, d->d_out_bits.p);
     if (rc || (rc = copy_to_host(d, out_bits, d->d_out_bits.p, n)) || (rc = iters_to_host(d, out_iters, B))) return rc;
     HIP_TRY(hipStreamSynchronize(d->stream));
     return LUTLDPC_OK;
@@ -308,7 +309,8 @@ int lutldpc_decoder_decode_batch_device(lutldpc_decoder *d, const uint8_t *d_cha
                                         uint8_t *d_out_bits, int32_t *d_out_iters, int sync) {
     if (!d || !d_cha || !d_msg0 || !d_out_bits || !d_out_iters) return fail(LUTLDPC_ERR_ARG, "NULL argument");
     int rc = batch_entry(d, B);
-    if (rc || (rc = decode_device(d, d_cha, d_msg0, B, d_out_bits, d_out_iters))) return rc;
+    if (rc || (rc = decode_device(d, d_cha, d_msg0, B, d_out_bits))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_out_iters, d->d_iters.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToDevice, d->stream));
     if (sync) HIP_TRY(hipStreamSynchronize(d->stream));
     return LUTLDPC_OK;
 }
@@ -316,7 +318,7 @@ int lutldpc_decoder_decode_batch_device(lutldpc_decoder *d, const uint8_t *d_cha
 int lutldpc_decoder_decode_batch(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0, int B, uint8_t *out_bits, int32_t *out_iters) {
     if (!d || !cha || !msg0 || !out_bits || !out_iters) return fail(LUTLDPC_ERR_ARG, "NULL argument");
     int rc = batch_entry(d, B);
-    if (rc || (rc = labels_from_host(d, cha, msg0, B))) return rc;
+    if (rc || (rc = labels_from_host(d, cha, msg0, B, (size_t)d->nvar))) return rc;
     return decode_staged_labels(d, B, out_bits, out_iters);
 }
 
@@ -333,30 +335,9 @@ int lutldpc_decoder_decode_batch_trace(lutldpc_decoder *d, const uint8_t *cha, c
     if (trace_cap < need) return fail(LUTLDPC_ERR_ARG, "trace buffer too small: " + std::to_string(need) + " bytes needed");
     TraceScope scope(d);
     d->trace.level = level; d->trace.host = trace; d->trace.cap = (size_t)trace_cap; d->trace.n = 0; d->trace.B = B;
-    if ((rc = labels_from_host(d, cha, msg0, B)) == LUTLDPC_OK) rc = decode_staged_labels(d, B, out_bits, out_iters);
+    if ((rc = labels_from_host(d, cha, msg0, B, (size_t)d->nvar)) == LUTLDPC_OK) rc = decode_staged_labels(d, B, out_bits, out_iters);
     if (n_dumps) *n_dumps = d->trace.n;
     return rc;
-}
-
-int lutldpc_decoder_decode_llr_batch(lutldpc_decoder *d, const double *llr, int B, const double *qb_Cha, int n_qb_Cha,
-                                     const double *qb_Msg, int n_qb_Msg, int mode, const int32_t *map,
-                                     uint8_t *out_bits, int32_t *out_iters) {
-    if (!d || !llr || !qb_Cha || !out_bits || !out_iters) return fail(LUTLDPC_ERR_ARG, "NULL argument");
-    int rc = batch_entry(d, B);
-    if (rc) return rc;
-    if (n_qb_Cha != d->Nq_Cha - 1) return fail(LUTLDPC_ERR_ARG, "qb_Cha must hold Nq_Cha-1 boundaries");
-    if (mode == 0 && (!qb_Msg || n_qb_Msg != d->Nq_Msg[0] - 1)) return fail(LUTLDPC_ERR_ARG, "qb_Msg must hold Nq_Msg[0]-1 boundaries");
-    if (mode == 1 && !map) return fail(LUTLDPC_ERR_ARG, "QCHA mode needs cha2msg_map");
-    if (mode != 0 && mode != 1) return fail(LUTLDPC_ERR_ARG, "initial_message_mode must be 0 (CONT) or 1 (QCHA)");   // src/LDPC_Code_LUT.cpp:218-220
-    size_t n = (size_t)B * (size_t)d->nvar;
-    HIP_TRY(d->d_llr.alloc(n)); HIP_TRY(d->d_in_cha.alloc(n)); HIP_TRY(d->d_in_msg.alloc(n));
-    HIP_TRY(d->d_qb_cha.alloc((size_t)n_qb_Cha)); HIP_TRY(d->d_qb_msg.alloc((size_t)(n_qb_Msg > 0 ? n_qb_Msg : 1))); HIP_TRY(d->d_map.alloc((size_t)d->Nq_Cha));
-    HIP_TRY(hipMemcpyAsync(d->d_llr.p, llr, n * sizeof(double), hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(hipMemcpyAsync(d->d_qb_cha.p, qb_Cha, sizeof(double) * (size_t)n_qb_Cha, hipMemcpyHostToDevice, d->stream));
-    if (mode == 0) HIP_TRY(hipMemcpyAsync(d->d_qb_msg.p, qb_Msg, sizeof(double) * (size_t)n_qb_Msg, hipMemcpyHostToDevice, d->stream));
-    else HIP_TRY(hipMemcpyAsync(d->d_map.p, map, sizeof(int32_t) * (size_t)d->Nq_Cha, hipMemcpyHostToDevice, d->stream));
-    if ((rc = launch_quantize_llr(d, n, n_qb_Cha, n_qb_Msg, mode))) return rc;
-    return decode_staged_labels(d, B, out_bits, out_iters);
 }
 
 void *lutldpc_decoder_stream(lutldpc_decoder *d) { return d ? (void *)d->stream.s : nullptr; }
@@ -383,7 +364,7 @@ int lutldpc_decoder_reset_profile(lutldpc_decoder *d) {
 int64_t lutldpc_decoder_device_bytes(lutldpc_decoder *d) {
     if (!d) return 0;
     return (int64_t)(d->d_msgs.bytes() + d->d_cha_t.bytes() + d->d_msg0_t.bytes() + d->d_hard.bytes() + d->d_state.bytes() + d->d_vfail.bytes() +
-                     d->d_iters.bytes() + d->d_in_cha.bytes() + d->d_in_msg.bytes() + d->d_out_bits.bytes() + d->d_out_iters.bytes() + d->d_llr.bytes() + d->d_llr_in.bytes() +
+                     d->d_iters.bytes() + d->d_in_cha.bytes() + d->d_in_msg.bytes() + d->d_out_bits.bytes() + d->d_host_in.bytes() +
                      d->d_ops.bytes() + d->d_tables.bytes() + d->d_cn_vn.bytes());
 }
 const char *lutldpc_decoder_describe(lutldpc_decoder *d) { return d ? d->describe.c_str() : ""; }

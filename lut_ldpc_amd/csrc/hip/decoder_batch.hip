@@ -201,15 +201,17 @@ int tiles_from_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d
     if ((rc = launch_labels_in(d, d_cha, (size_t)d->nvar, false, d->d_cha_t.p, nullptr, nullptr, B, G, d->Nq_Cha - 1))) return rc;
     return launch_labels_in(d, d_msg0, (size_t)d->nvar, false, d->d_msg0_t.p, nullptr, nullptr, B, G, d->Nq_Msg[0] - 1);
 }
-int labels_from_host(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0, int B) {
-    const size_t n = (size_t)B * (size_t)d->nvar;
-    HIP_TRY(d->d_in_cha.alloc(n)); HIP_TRY(d->d_in_msg.alloc(n));
+int labels_from_host(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0, int B, size_t stride) {
+    const size_t n = (size_t)B * stride;
+    HIP_TRY(d->d_in_cha.alloc(n));
     HIP_TRY(hipMemcpyAsync(d->d_in_cha.p, cha, n, hipMemcpyHostToDevice, d->stream));
+    if (!msg0) return LUTLDPC_OK;
+    HIP_TRY(d->d_in_msg.alloc(n));
     HIP_TRY(hipMemcpyAsync(d->d_in_msg.p, msg0, n, hipMemcpyHostToDevice, d->stream));
     return LUTLDPC_OK;
 }
 int tiles_from_host(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0, int B) {
-    if (int rc = labels_from_host(d, cha, msg0, B)) return rc;
+    if (int rc = labels_from_host(d, cha, msg0, B, (size_t)d->nvar)) return rc;
     return tiles_from_device(d, d->d_in_cha.p, d->d_in_msg.p, B);
 }
 

@@ -206,9 +206,9 @@ int lutldpc_decoder_encode_packed(lutldpc_decoder *d, const lutldpc_encode_io *i
     if (d->gen.form == Generator::SPARSE) HIP_TRY(d->d_enc_rows.alloc(bit_rows_bytes(d, B)));
     if (!dev) {         // the whole batch, gaps included, up to the last word read
         const size_t words = (size_t)(B - 1) * src.stride + (size_t)W32;
-        HIP_TRY(d->d_llr_in.alloc((words + 1) / 2));
-        HIP_TRY(hipMemcpyAsync(d->d_llr_in.p, info, words * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
-        src.words = reinterpret_cast<const uint32_t *>(d->d_llr_in.p);
+        HIP_TRY(d->d_host_in.alloc((words + 1) / 2));
+        HIP_TRY(hipMemcpyAsync(d->d_host_in.p, info, words * sizeof(uint32_t), hipMemcpyHostToDevice, d->stream));
+        src.words = reinterpret_cast<const uint32_t *>(d->d_host_in.p);
         HIP_TRY(d->d_out_words.alloc((size_t)B * (size_t)Wout));
         win.out = d->d_out_words.p;
     }

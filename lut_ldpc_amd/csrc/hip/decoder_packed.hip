@@ -21,14 +21,8 @@ extern "C" int lutldpc_decoder_decode_batch_packed(lutldpc_decoder *d, const lut
     int rc = check_out_window(d, io->out_first, io->out_count);
     if (rc || (rc = batch_entry(d, B))) return rc;
     // labels in: one staging buffer per array the caller sends
-    const size_t stride = nibbles ? ((size_t)N + 1) / 2 : (size_t)N, n = (size_t)B * stride;
-    HIP_TRY(d->d_in_cha.alloc(n));
-    HIP_TRY(hipMemcpyAsync(d->d_in_cha.p, cha, n, hipMemcpyHostToDevice, d->stream));
-    if (msg0) {
-        HIP_TRY(d->d_in_msg.alloc(n));
-        HIP_TRY(hipMemcpyAsync(d->d_in_msg.p, msg0, n, hipMemcpyHostToDevice, d->stream));
-    }
-    if ((rc = ensure_batch(d, B))) return rc;
+    const size_t stride = nibbles ? ((size_t)N + 1) / 2 : (size_t)N;
+    if ((rc = labels_from_host(d, cha, msg0, B, stride)) || (rc = ensure_batch(d, B))) return rc;
     const int G = d->bpad(B) / d->tile();
     {
         Timed t(d, LUTLDPC_K_LAYOUT);

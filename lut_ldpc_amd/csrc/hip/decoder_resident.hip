@@ -106,14 +106,15 @@ int resident_plan_for(lutldpc_decoder *d, int G, lutldpc_decoder::ResidentPlan *
     return LUTLDPC_OK;
 }
 
-int launch_resident(lutldpc_decoder *d, int G, int B) {
+int launch_resident(lutldpc_decoder *d, int G, int B, const FrameMajorIO *fm) {
     lutldpc_decoder::ResidentPlan *pl = nullptr;
     if (int rc = resident_plan_for(d, G, &pl)) return rc;
     Timed t(d, LUTLDPC_K_RESIDENT);
     ResidentArgs A{};
     A.cha = d->d_cha_t.p; A.msg0 = d->d_msg0_t.p; A.hard = d->d_hard.p; A.state = d->d_state.p; A.iters = d->d_iters.p;
     A.tables = d->d_tables.p; A.idx = d->d_fast_idx.p; A.n_sets = 64 * G; A.max_iters = d->max_iters; A.psc = d->psc; A.pisc = d->pisc;
-    A.B = B; A.fm_cha = d->fm_cha; A.fm_msg0 = d->fm_msg0; A.fm_bits = d->fm_bits; A.lim_cha = d->Nq_Cha - 1; A.lim_msg = d->Nq_Msg[0] - 1;
+    A.B = B; A.lim_cha = d->Nq_Cha - 1; A.lim_msg = d->Nq_Msg[0] - 1;
+    if (fm) { A.fm_cha = fm->cha; A.fm_msg0 = fm->msg0; A.fm_bits = fm->bits; }
     void *args[] = {&A};
     const unsigned blocks = (unsigned)((64 * G + pl->S - 1) / pl->S);
     HIP_TRY(hipModuleLaunchKernel(pl->k->fn, blocks, 1, 1, (unsigned)pl->NT, 1, 1, 0, d->stream, args, nullptr));

@@ -19,7 +19,7 @@
 //   decoder_events.hip     failed frames captured on the device: weights, selection, sorted error / syndrome lists, C-ABI   (kernels_events.hpp)
 //   decoder_layout.hip     frame-major <-> rows: labels in (bytes / nibbles), labels out, decided bits out                  (kernels_layout.hpp)
 //   decoder_packed.hip     packed label input and bit-packed output of the host-side batch decode, C-ABI
-//   decoder_llr.hip        float64 / float32 / float16 / int8 soft values from host or device memory into both row sets, C-ABI (kernels_llr.hpp, llr_cells.hpp)
+//   decoder_llr.hip        float64 / float32 / float16 / int8 soft values from host or device memory into both row sets, C-ABI of both LLR entries (kernels_llr.hpp, llr_cells.hpp)
 #pragma once
 #include "../../../include/lut_ldpc_hip.h"
 #include "kernels_common.hpp"
@@ -204,11 +204,8 @@ struct lutldpc_decoder {
     DevBuf<uint8_t> d_msgs, d_cha_t, d_msg0_t, d_hard, d_state, d_vfail;
     DevBuf<int32_t> d_iters;
     DevBuf<uint8_t> d_in_cha, d_in_msg, d_out_bits;   // frame-major staging for the host entry points
-    DevBuf<int32_t> d_out_iters;
     DevBuf<uint32_t> d_out_words;                     // decode_batch_packed: [B][ceil(out_count/32)] decided bits, one each (encode_packed: codeword bits)
-    DevBuf<double> d_llr, d_qb_cha, d_qb_msg;
-    DevBuf<uint64_t> d_llr_in;                        // decode_llr_packed: host values of any element type, staged as they came (encode_packed: host information words)
-    DevBuf<int32_t> d_map;
+    DevBuf<uint64_t> d_host_in;                       // raw host input of any element type, staged as it came: the soft values of the LLR entries, the information words of encode_packed
     DevBuf<uint8_t> d_codewords;                      // upload staging of sent_rows_from_host; no kernel but its conversion reads it
     DevBuf<int32_t> d_stats;
     // The systematic generator of the device encoder (decoder_encode.hip), R parity rows over K information bits, in the form it
@@ -254,7 +251,6 @@ struct lutldpc_decoder {
         unsigned long long *hist = nullptr; const uint8_t *sent = nullptr; const int32_t *last_dump = nullptr; int n_labels = 0, n_dumps = 0;
     };
     Trace trace;
-    DevBuf<uint8_t> d_trace;
     // edge grouping of the histograms (lutldpc_decoder_set_edge_groups): the edges sorted by group, where every group's run
     // begins, and the runs cut into chunks {first, count, group} of hist_chunk_edges edges (decoder_stats.hip:
     // upload_edge_groups; 0 = not cut / uploaded yet).  hist_edges empty = never set (one group)
@@ -272,10 +268,6 @@ struct lutldpc_decoder {
     } ev;
     // LDS-resident decoder (jit_resident.hpp): codes whose edge messages fit the LDS of a compute unit are decoded by ONE generated
     // kernel per decode -- all iterations inside, no HBM traffic between the labels and the decided bits.
-    // frame-major label / bit buffers of the current decode_device call, handed to the resident kernel (it reads and writes them
-    // itself: no transposes); null = rows
-    const uint8_t *fm_cha = nullptr, *fm_msg0 = nullptr;
-    uint8_t *fm_bits = nullptr;
     struct ResidentPlan { int S = 0, NT = 0, lds = 0; const JitKernel *k = nullptr; };
     std::map<int, ResidentPlan> resident_plans;       // by frame groups
     std::string resident_log;
@@ -384,10 +376,11 @@ int check_batch_buffers(const lutldpc_decoder *d, int Bpad);
 // stream: the Philox stream of the entries that sample or encode (lutldpc_check_stream: >= 2^31 is LUTLDPC_ERR_ARG too).
 int device_entry(lutldpc_decoder *d);
 int batch_entry(lutldpc_decoder *d, int B, uint32_t stream = 0);
-// labels in: frame-major labels of B frames -> d_cha_t / d_msg0_t.  labels_from_host uploads them to d_in_cha / d_in_msg and stops
-// there (decode_device decides whether rows are needed), tiles_from_host goes on to the rows.
+// labels in: frame-major labels of B frames -> d_cha_t / d_msg0_t.  labels_from_host uploads them, `stride` bytes per frame, to
+// d_in_cha / d_in_msg (msg0 = null: the channel labels alone) and stops there (decode_device decides whether rows are needed),
+// tiles_from_host goes on to the rows.
 int tiles_from_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d_msg0, int B);
-int labels_from_host(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0, int B);
+int labels_from_host(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0, int B, size_t stride);
 int tiles_from_host(lutldpc_decoder *d, const uint8_t *cha, const uint8_t *msg0, int B);
 // results out, asynchronous on the decoder's stream.  Rows are staged through d_out_bits (copies on one stream are ordered: a
 // caller may fetch several row sets one after the other).
@@ -405,7 +398,6 @@ hipError_t preload_stream_kernels();
 // frames f0 .. f1-1 (both multiples of 256); default: the whole padded batch
 // `sel`: which of the two flag buffers the exit test reads and clears (always 0 outside the skewed pipeline)
 int launch_state(lutldpc_decoder *d, int B, int Bpad, int mode, int value, int f0 = 0, int f1 = -1, int sel = 0);
-int launch_quantize_llr(lutldpc_decoder *d, size_t n, int n_qb_Cha, int n_qb_Msg, int mode);
 bool chain_active(const lutldpc_decoder *d, int set);
 // The kernel that runs degree class `cls` of a pass of `kind` (TT_VAR, TT_CHK, TT_DEC) with tree set `set` and sign threshold nz
 // (ClassParams::nz): the only place that chooses.  Launches, class parameters, describe() and skew_eligible ask here.
@@ -437,8 +429,11 @@ inline PassBufs pass_bufs(const lutldpc_decoder *d) {
 }
 bool late_hard_active(const lutldpc_decoder *d, bool skewed, bool *chain_skip);
 int launch_late_hard(lutldpc_decoder *d, bool skewed, int g0, int G);
-int decode_tiles(lutldpc_decoder *d, int B);
-int decode_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d_msg0, int B, uint8_t *d_out_bits, int32_t *d_out_iters);
+// The frame-major label / bit buffers of a decode_device call (the C-ABI's own layout, [B][nvar] bytes, device), handed down to
+// the resident kernel, which reads and writes them itself: no transposes.  No record = rows, as every other caller has them.
+struct FrameMajorIO { const uint8_t *cha, *msg0; uint8_t *bits; };
+int decode_tiles(lutldpc_decoder *d, int B, const FrameMajorIO *fm = nullptr);
+int decode_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d_msg0, int B, uint8_t *d_out_bits);
 
 // ---- decoder_skew.hip (home of the kernels of kernels_compact.hpp; pass_fused_kernel through launch_fused)
 // Half A = groups [0, GA), half B = [GA, G)
@@ -455,7 +450,7 @@ bool resident_eligible(const lutldpc_decoder *d);
 bool resident_pick(const lutldpc_decoder *d, int G, int &S_out, int &NT_out, int &lds_out);
 inline bool resident_active(const lutldpc_decoder *d) { return d->resident_ok && d->opt.use_resident; }
 int resident_plan_for(lutldpc_decoder *d, int G, lutldpc_decoder::ResidentPlan **out);
-int launch_resident(lutldpc_decoder *d, int G, int B);
+int launch_resident(lutldpc_decoder *d, int G, int B, const FrameMajorIO *fm = nullptr);
 
 // ---- decoder_frontend.hip (home of the kernels of kernels_frontend.hpp)
 hipError_t preload_frontend_kernels();

@@ -277,27 +277,18 @@ static int trace_dump(lutldpc_decoder *d) {
     if (T.hist) return hist_dump(d);               // the sink is a histogram on the device (decoder_stats.hip): nothing is copied
     const size_t one = (size_t)T.B * (size_t)d->E;
     if ((size_t)(T.n + 1) * one > T.cap) return fail(LUTLDPC_ERR_ARG, "trace buffer too small");
-    const int G = d->bpad(T.B) / d->tile();
-    HIP_TRY(d->d_trace.alloc(one));
-    if (int rc = launch_transpose_out(d, d->d_msgs.p, d->d_trace.p, T.B, G, d->E)) return rc;
-    LAUNCH_CHECK();
-    HIP_TRY(hipMemcpyAsync(T.host + (size_t)T.n * one, d->d_trace.p, one, hipMemcpyDeviceToHost, d->stream));
+    // rows_to_host stages through d_out_bits, whose pointer the caller of this decode may hold already (decode_staged_labels sizes
+    // it for a dump): never let it move here
+    if (d->d_out_bits.n < one) return fail(LUTLDPC_ERR_STATE, "trace: the staging buffer was not sized for a dump");
+    if (int rc = rows_to_host(d, d->d_msgs.p, T.host + (size_t)T.n * one, T.B, d->E)) return rc;
     HIP_TRY(hipStreamSynchronize(d->stream));
     T.n++;
     return LUTLDPC_OK;
 }
 
-// d_llr -> frame-major labels in d_in_cha / d_in_msg (lutldpc_decoder_decode_llr_batch)
-int launch_quantize_llr(lutldpc_decoder *d, size_t n, int n_qb_Cha, int n_qb_Msg, int mode) {
-    launch_k(quantize_llr_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d->stream, d->d_llr.p, n, d->d_qb_cha.p, n_qb_Cha,
-                       d->d_qb_msg.p, n_qb_Msg, mode, d->d_map.p, d->d_in_cha.p, d->d_in_msg.p);
-    LAUNCH_CHECK();
-    return LUTLDPC_OK;
-}
-
 // Core: decode the B frames whose labels are already in tile layout (d_cha_t / d_msg0_t).
 // Leaves the decided bits in d_hard (tile layout) and the iteration codes in d_iters.
-static int decode_tiles_launch(lutldpc_decoder *d, int B) {
+static int decode_tiles_launch(lutldpc_decoder *d, int B, const FrameMajorIO *fm = nullptr) {
     int rc;
     const int Bpad = d->bpad(B), G = Bpad / d->tile();
     const int N = d->nvar, E = d->E, I = d->max_iters;
@@ -307,7 +298,7 @@ static int decode_tiles_launch(lutldpc_decoder *d, int B) {
     if ((rc = launch_state(d, B, Bpad, 0, 0))) return rc;
     const bool tracing = d->trace.level > 1;
     if (resident_active(d) && !tracing) {         // the whole of lut_decode in one launch, messages in LDS (jit_resident.hpp)
-        if ((rc = launch_resident(d, G, B))) return rc;
+        if ((rc = launch_resident(d, G, B, fm))) return rc;
         if (d->profiling && d->ev_live.size() > 8192) prof_fold(d);
         return LUTLDPC_OK;
     }
@@ -387,15 +378,15 @@ static int decode_tiles_launch(lutldpc_decoder *d, int B) {
 // second call with the same key on, the sequence is replayed as ONE hipGraph launch (the first call runs
 // plainly and fills the item-table cache, whose uploads may not happen inside a capture).  Short codes
 // are launch-bound, for them this is worth ~20 %.  Off while kernel events are being recorded.
-int decode_tiles(lutldpc_decoder *d, int B) {
+int decode_tiles(lutldpc_decoder *d, int B, const FrameMajorIO *fm) {
     if (int rc = check_batch_buffers(d, d->bpad(B))) return rc;
     if (resident_active(d) && !d->trace.hist) {   // generate / compile / load outside any stream capture (a counted decode streams)
         lutldpc_decoder::ResidentPlan *pl = nullptr;
         if (int rc = resident_plan_for(d, d->bpad(B) / d->tile(), &pl)) return rc;
     }
-    // (the resident decoder is ONE launch plus the state kernel: nothing to gain from a graph, and the frame-major pointers of the
-    // caller would be frozen into it)
-    if (!d->opt.use_graph || d->profiling || d->trace.level > 1 || resident_active(d)) return decode_tiles_launch(d, B);
+    // (the resident decoder is ONE launch plus the state kernel: nothing to gain from a graph.  It is never captured into one, which
+    // is why a caller's frame-major pointers, fm, may enter its launch: a graph would freeze them.  No other path reads fm.)
+    if (!d->opt.use_graph || d->profiling || d->trace.level > 1 || resident_active(d)) return decode_tiles_launch(d, B, fm);
     const std::array<int, 4> key = {B, d->psc, d->pisc, d->max_iters};
     if (d->graphs.size() > 32 && !d->graphs.count(key)) d->drop_graphs();      // callers with ever-changing batch sizes: bound the cache
     auto &slot = d->graphs[key];
@@ -422,22 +413,15 @@ int decode_tiles(lutldpc_decoder *d, int B) {
 }
 
 // The batched lut_decode (src/LDPC_Code_LUT.cpp:259-353) on device-resident frame-major labels (after the entry's batch_entry).
-int decode_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d_msg0, int B, uint8_t *d_out_bits, int32_t *d_out_iters) {
+int decode_device(lutldpc_decoder *d, const uint8_t *d_cha, const uint8_t *d_msg0, int B, uint8_t *d_out_bits) {
     // the LDS-resident decoder reads the frame-major labels and writes the frame-major bits itself
     const bool direct = resident_active(d) && d->opt.resident_fm && d->trace.level <= 1;
     int rc = direct ? ensure_batch(d, B) : tiles_from_device(d, d_cha, d_msg0, B);
     if (rc) return rc;
-    const int G = d->bpad(B) / d->tile();
-    if (direct) { d->fm_cha = d_cha; d->fm_msg0 = d_msg0; d->fm_bits = d_out_bits; }
-    rc = decode_tiles(d, B);
-    d->fm_cha = d->fm_msg0 = nullptr; d->fm_bits = nullptr;
-    if (rc) return rc;
-    {
-        Timed t(d, LUTLDPC_K_LAYOUT);
-        if (!direct && (rc = launch_transpose_out(d, d->d_hard.p, d_out_bits, B, G))) return rc;
-        HIP_TRY(hipMemcpyAsync(d_out_iters, d->d_iters.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToDevice, d->stream));
-    }
-    return LUTLDPC_OK;
+    const FrameMajorIO fm = {d_cha, d_msg0, d_out_bits};
+    if ((rc = decode_tiles(d, B, direct ? &fm : nullptr)) || direct) return rc;
+    Timed t(d, LUTLDPC_K_LAYOUT);
+    return launch_transpose_out(d, d->d_hard.p, d_out_bits, B, d->bpad(B) / d->tile());
 }
 
 #pragma GCC visibility pop

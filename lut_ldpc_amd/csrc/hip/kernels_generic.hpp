@@ -436,23 +436,4 @@ __global__ __launch_bounds__(256) void frame_state_kernel(uint8_t *__restrict__ 
     else iters[f] = vf ? -value : value;
 }
 
-// quant_nonlin (src/common.cpp:120-138) for the decode(vec llr) entry: label = number of
-// leading boundaries strictly below x; mode 0: msg label from qb_msg, mode 1: map[cha label]
-__global__ __launch_bounds__(256) void quantize_llr_kernel(const double *__restrict__ llr, size_t n, const double *__restrict__ qb_cha,
-                                                           int n_cha, const double *__restrict__ qb_msg, int n_msg, int mode,
-                                                           const int32_t *__restrict__ map, uint8_t *__restrict__ cha, uint8_t *__restrict__ msg)
-{
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const double x = llr[i];
-    int a = 0;
-    for (int k = 0; k < n_cha; k++) { if (x > qb_cha[k]) a++; else break; }
-    cha[i] = (uint8_t)a;
-    if (mode == 0) {
-        int m = 0;
-        for (int k = 0; k < n_msg; k++) { if (x > qb_msg[k]) m++; else break; }
-        msg[i] = (uint8_t)m;
-    } else msg[i] = (uint8_t)map[a];
-}
-
 }  // namespace lutldpc

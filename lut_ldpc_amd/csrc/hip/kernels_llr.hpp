@@ -1,4 +1,4 @@
-// kernels_llr.hpp -- the layout kernel of lutldpc_decoder_decode_llr_packed (decoder_llr.hip): frame-major soft values quantised
+// kernels_llr.hpp -- the layout kernel of the two LLR entries (decoder_llr.hip): frame-major soft values quantised
 // straight into both label row sets, read once.  Block order, tile and the whole store side (rows_from_tile) are the shared ones of
 // kernels_layout.hpp; only the load side is this kernel's own.  What goes through the tile here is the CELL of a value
 // (llr_cells.hpp), one byte, from which two wave-held tables give both labels.

@@ -1,8 +1,9 @@
-// llr_cells.hpp -- host half of lutldpc_decoder_decode_llr_packed (decoder_llr.hip): the quantiser boundaries of a call turned into
-// what the label kernel compares and looks up.  No device code.
+// llr_cells.hpp -- host half of the two LLR entries (decoder_llr.hip): the quantiser boundaries of a call turned into what the
+// label kernel compares and looks up.  No device code.
 //
 // quant_nonlin (src/common.cpp:120-129) gives a value x the label #{leading k : x > b[k]}; for non-decreasing boundaries (anything
-// else is refused here) that is the plain count #{k : x > b[k]}.  The kernel never widens x.  For an input type T and a boundary
+// else is refused by llr_cell_table; the float64 entry brings its arrays into that form first, leading_count_bounds) that is the
+// plain count #{k : x > b[k]}.  The kernel never widens x.  For an input type T and a boundary
 // b let b_T be the largest value of T that is <= b (-inf where b lies below -max(T), max(T) where it lies above, +inf for +inf):
 // no value of T lies in (b_T, b], so for every x of type T, NaN and the infinities included, x > b exactly when x > b_T.
 // Rounding down is monotone, so the b_T are non-decreasing as well.
@@ -53,6 +54,19 @@ inline int quant_count(double x, const double *b, int n) {
     int k = 0;
     while (k < n && x > b[k]) k++;
     return k;
+}
+
+// quant_nonlin on ANY boundary array, for the float64 entry (lutldpc_decoder_decode_llr_batch), which takes what its callers hold:
+// the loop stops at the first boundary that x does not exceed, and x > max(b[0..k]) holds exactly when x exceeds every one of
+// b[0..k], so the leading count over b is the plain count over its running maxima; a NaN boundary stops every x, as +inf does.
+// A non-decreasing array free of NaN comes back as it is.
+inline std::vector<double> leading_count_bounds(const double *b, int n) {
+    std::vector<double> m(b, b + n);
+    for (int k = 0; k < n; k++) {
+        if (std::isnan(m[(size_t)k])) m[(size_t)k] = HUGE_VAL;
+        if (k > 0 && m[(size_t)k] < m[(size_t)k - 1]) m[(size_t)k] = m[(size_t)k - 1];
+    }
+    return m;
 }
 
 // The checks of the entry that need no decoder and no pointer to the values, then the tables.  Returns "" or what is wrong.

@@ -91,6 +91,48 @@ def test_llr_decode_matches_oracle_and_the_float64_entry(name, B):
     dec.close()
 
 
+def spoiled(q):
+    """Designed boundaries (15 or 31 here) with two adjacent entries swapped at a third of the array and the third from the end
+    replaced by NaN."""
+    q = q.copy()
+    i = len(q) // 3
+    q[[i, i + 1]] = q[[i + 1, i]]
+    q[len(q) - 3] = np.nan
+    return q
+
+
+@pytest.mark.parametrize("name,B", [("n33", lc.CASES["n33"]["tile"] + 1), ("byte_q5", 257)])
+def test_float64_entry_counts_the_leading_boundaries_of_any_array(name, B):
+    """decode_llr_batch takes boundary arrays as its callers hold them: quant_nonlin stops at the first boundary that x does not
+    exceed (the oracle's loop has the break), whatever comes after it -- a smaller boundary or NaN.  Every frame, bits and codes,
+    against the oracle's decode of the oracle's labels; a map entry outside the message alphabet is refused."""
+    cd = lc.codec(name)
+    dec = product_decoder(cd)
+    dec.set_exit_conditions(cd.max_iters, True, False)
+    cd.set_exit_conditions(cd.max_iters, True, False)
+    qc, qm, mp = lc.quantiser(name)
+    sc, sm = spoiled(qc), spoiled(qm)
+    x = lc.values(name, "f64")[0][:B]
+    for mode in (0, 1):
+        cha, msg = lc.ref_labels(x, sc, sm, mp, mode)
+        assert (cha != lc.want_labels(name, "f64", mode)[0][:B]).any()          # the spoiled entries matter
+        assert len(np.unique(cha)) < len(qc) + 1                               # ... labels behind them are out of reach
+        wb, wi = cd.lut_decode_batch_flat(cha, msg)
+        lc.check_mix(name, wi, False, B)
+        bits, it = dec.decode_llr_batch(x, sc, sm if mode == 0 else None, mode, mp if mode == 1 else None)
+        assert (it == wi).all(), (name, mode, np.flatnonzero(it != wi)[:8])
+        assert (bits == wb).all(), (name, mode, np.argwhere(bits != wb)[:4].tolist())
+    if name == "n33":
+        bad = mp.copy()
+        bad[len(bad) // 2] = len(qm) + 1                                       # = Nq_Msg[0]
+        with pytest.raises(L.LutLdpcError, match="cha2msg_map entry outside") as e:
+            dec.decode_llr_batch(x[:2], qc, None, 1, bad)
+        assert e.value.code == ERR_ARG
+        bits, it = dec.decode_llr_batch(x, sc, None, 1, mp)                    # the handle decodes as before
+        assert (it == wi).all() and (bits == wb).all()
+    dec.close()
+
+
 @pytest.mark.parametrize("name", list(lc.CASES))
 def test_windows_of_the_decided_bits(name):
     cd = lc.codec(name)

@@ -3,7 +3,7 @@
 first-slice entry lutldpc_decoder_decode_llr_batch (float64 from host memory, a byte per decided bit back).
 Per workload (DVB-S2 at 8192 frames: the float64 batch is 4.2 GB; the (3,6) N = 10000 code at 4096), in ONE process, as-shipped
 exit conditions (psc and pisc), 0.4 dB above the design point, initial messages = cha2msg_map of the channel labels (QCHA):
-  llr_batch     lutldpc_decoder_decode_llr_batch on float64 (the parent's path)
+  llr_batch     lutldpc_decoder_decode_llr_batch on float64, a byte per decided bit back (the same quantiser as the rows below)
   host f64 .. host i8   the new entry on host float64 / float32 / float16 / int8 (scale = 1.25 max|qb| / 127), data bits out
   dev f32, dev f16      the new entry on tensors that already live in HBM, data bits left there
   device        lutldpc_decoder_decode_batch_device on label buffers in HBM: no transfer, no quantiser -- the ceiling
