@@ -68,6 +68,56 @@ int lutldpc_bp_decode_llr_batch(lutldpc_bp_decoder *d, const double *llr, int B,
 /* LDPC_Code::bp_decode(QLLRvec) for B frames on quantised input (host); any int32 is accepted and clipped to +-QMAX. */
 int lutldpc_bp_decode_qllr_batch(lutldpc_bp_decoder *d, const int32_t *qllr, int B, uint8_t *out_bits, int32_t *out_iters, int32_t *out_qllr);
 
+/*
+ * The device front end: channel, decode and error counters of a batch on the device, four counters per frame come back.
+ *
+ * A received value x reaches the decoder only as to_qllr(4x/N0) and as the slicer's sign, so the channel is described by CELLS of
+ * the real line, as the LUT front end describes it (lutldpc_channel_cells, include/lut_ldpc_hip.h): one 64-bit uniform u per code
+ * bit is compared with the integer cumulative cell probabilities, no transcendental runs on the device, and everything after the
+ * thresholds is integer arithmetic.
+ *   cell of a sample  = number of thresholds <= u
+ *   decoder input     = qllr[cell] when 0 was sent, -qllr[cell] when 1 was sent (the value is mirrored)
+ *   uncoded error     = slicer_neg[cell], whichever bit was sent
+ * Uniforms: Philox4x32-10, key = seed, counter = (frame lo, frame hi, bit pair p, stream); u = c[1]<<32 | c[0] for node 2p,
+ * c[3]<<32 | c[2] for node 2p+1 -- the uniforms of lutldpc_decoder_sim_batch.  The device front end and the host front end
+ * (lutldpc_awgn_llr: Box-Muller in doubles, counter word 3 = stream | 0x40000000) are two different random streams; the device one
+ * is the stream of the LUT front end: frame f of a [BP] run sees the received values of frame f of a [LUT] run with the same seed
+ * and stream, each through its own quantiser.
+ */
+#define LUTLDPC_BP_MAX_CELLS (1 << 21)
+
+typedef struct {
+    int32_t n_cells;             /* 1 .. LUTLDPC_BP_MAX_CELLS                                          */
+    const uint64_t *thr;         /* n_cells-1, non-decreasing: floor(2^64 * P(cell <= j | bit 0 sent)) */
+    const int32_t  *qllr;        /* n_cells: the QLLR of the cell when 0 was sent; |q| <= QMAX         */
+    const uint8_t  *slicer_neg;  /* n_cells: 1 = x <= 0 (the slicer decides 1)                         */
+} lutldpc_bp_cells;
+
+/* The table of x ~ N(1, N0/2) for to_qllr with d1 / d4 (host only, no handle).  Cell k = (t_k-1, t_k] with t_k = (k + 0.5) N0 /
+ * (4 2^d1) carries QLLR k; the cells beyond +-QMAX merge into +-QMAX; one more threshold at x = 0 splits QLLR 0 into a negative and
+ * a non-negative half; leading cells of mass 0 and trailing cells past a threshold of 2^64 - 1 are dropped.  The cumulative
+ * probability of a threshold is the one of the LUT front end's table (the nearer tail through erfc, then the running maximum), so
+ * the threshold at x = 0 is the same integer in both tables.  *n_cells receives the number of cells of the table, also when cap
+ * is short.  LUTLDPC_ERR_ARG: bad d1 / d4 / N0, NULL n_cells, cap < cells (the message names the count; nothing but *n_cells is
+ * written), a NULL array with cap >= cells; LUTLDPC_ERR_UNSUPPORTED: more than LUTLDPC_BP_MAX_CELLS cells (about 20 dB at d1 = 12). */
+int lutldpc_bp_awgn_cells(int d1, int d4, double N0, int cap, int32_t *n_cells, uint64_t *thr, int32_t *qllr, uint8_t *slicer_neg);
+
+/* Validates the table and uploads it with its slice index; replaces the previous table, a refused call leaves it in place.
+ * ERR_ARG: NULL handle / cells / member, n_cells out of range, descending thresholds, |q| > QMAX; then ERR_STATE: host-only handle. */
+int lutldpc_bp_set_cells(lutldpc_bp_decoder *d, const lutldpc_bp_cells *cells);
+/* What the sampler feeds the decoder for frames frame0 .. frame0+B-1 of `stream`: qllr_out host B*nvar frame-major, uncoded_out host
+ * B or NULL.  codewords: host B*nvar sent bits (bit 0 of a byte counts) or NULL for the all-zero codeword.  For tests and stimuli. */
+int lutldpc_bp_sample_qllr(lutldpc_bp_decoder *d, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *codewords,
+                           int32_t *qllr_out, int32_t *uncoded_out);
+/* Sampler + bp_decode + counters.  frame_stats host B*4 = {bp_decode return value, frame error 0/1, data bit errors over the first
+ * K_info nodes, uncoded errors over all nodes} as in lutldpc_decoder_sim_batch; qllr_out (the decoder's input) and bits_out (LLRout
+ * < 0), host B*nvar, or NULL.
+ * Errors of both entries, in this order: NULL handle or B <= 0: ERR_ARG; a NULL mandatory pointer, K_info outside 0 .. nvar, a
+ * stream above LUTLDPC_STREAM_MAX (lutldpc_check_stream): ERR_ARG; a host-only handle, then no table set: ERR_STATE.  A refused
+ * call writes nothing. */
+int lutldpc_bp_sim_batch(lutldpc_bp_decoder *d, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *codewords,
+                         int K_info, int32_t *frame_stats, int32_t *qllr_out, uint8_t *bits_out);
+
 #ifdef __cplusplus
 }
 #endif

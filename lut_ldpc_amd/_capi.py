@@ -102,6 +102,21 @@ class _ccp(C.POINTER(ChannelCells)):
         return C.POINTER(ChannelCells).from_param(obj)
 
 
+class BPCells(C.Structure):
+    """lutldpc_bp_cells (include/lut_ldpc_bp.h): the cell table of the [BP] decoder's device front end."""
+    _fields_ = [("n_cells", C.c_int32), ("thr", _u64p), ("qllr", _ip), ("slicer_neg", _u8p)]
+
+    @classmethod
+    def from_table(cls, t):
+        """From a dict {"thr": uint64[n - 1], "qllr": int32[n], "neg": uint8[n]} (bp.awgn_cells).  The arrays stay alive on the
+        instance; a table of one cell gets a placeholder threshold (the pointer must not be NULL)."""
+        thr = np.ascontiguousarray(t["thr"], np.uint64)
+        keep = [thr if len(thr) else np.zeros(1, np.uint64), np.ascontiguousarray(t["qllr"], np.int32), np.ascontiguousarray(t["neg"], np.uint8)]
+        cells = cls(len(keep[1]), keep[0].ctypes.data_as(_u64p), keep[1].ctypes.data_as(_ip), keep[2].ctypes.data_as(_u8p))
+        cells._keep = keep
+        return cells
+
+
 # every function include/*.h declares -> (result, arguments)
 _SIGNATURES = {
     "lutldpc_decoder_encode_packed": (C.c_int, [_vp, C.POINTER(EncodeIO), _vp, C.c_int, _vp]),
@@ -196,6 +211,10 @@ _SIGNATURES = {
     "lutldpc_bp_logexp_table": (C.c_int, [_vp, _ip, C.c_int]),
     "lutldpc_bp_decode_llr_batch": (C.c_int, [_vp, _dp, C.c_int, _u8p, _ip, _ip]),
     "lutldpc_bp_decode_qllr_batch": (C.c_int, [_vp, _ip, C.c_int, _u8p, _ip, _ip]),
+    "lutldpc_bp_awgn_cells": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_int, _ip, _u64p, _ip, _u8p]),
+    "lutldpc_bp_set_cells": (C.c_int, [_vp, C.POINTER(BPCells)]),
+    "lutldpc_bp_sample_qllr": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p, _ip, _ip]),
+    "lutldpc_bp_sim_batch": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p, C.c_int, _ip, _ip, _u8p]),
     "lutldpc_awgn_llr": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.c_double, _u8p, _dp, _ip]),
 }
 for _name, (_res, _args) in _SIGNATURES.items():

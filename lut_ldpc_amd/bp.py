@@ -6,7 +6,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._capi import lib, check
+from ._capi import lib, check, last_error, BPCells, LutLdpcError, ERR_ARG
 
 _vp = C.c_void_p
 
@@ -55,6 +55,52 @@ class BPDecoder:
 
     def decode_qllr_batch(self, qllr, want_qllr=False):
         return self._decode(lib.lutldpc_bp_decode_qllr_batch, np.ascontiguousarray(qllr, np.int32), C.c_int32, want_qllr)
+
+    # ---- device front end (include/lut_ldpc_bp.h): cell sampler -> bp_decode -> error counters, all on the device
+    def set_cells(self, cells):
+        """The channel's cell table: a dict {"thr", "qllr", "neg"} as awgn_cells returns it, or a _capi.BPCells."""
+        c = cells if isinstance(cells, BPCells) else BPCells.from_table(cells)
+        check(lib.lutldpc_bp_set_cells(self._h, C.byref(c)))
+
+    @staticmethod
+    def _codewords(codewords, B, N):
+        if codewords is None:
+            return None, None
+        cw = np.ascontiguousarray(codewords, np.uint8)
+        if cw.shape != (B, N):
+            raise ValueError("codewords must be [B, nvar]")
+        return cw, _p(cw, C.c_uint8)
+
+    def sample_qllr(self, seed, stream, frame0, B, codewords=None):
+        """What the sampler feeds the decoder for frames frame0 .. frame0+B-1: (qllr [B, nvar] int32, uncoded errors [B] int32)."""
+        q, unc = np.empty((B, self.nvar), np.int32), np.empty(B, np.int32)
+        cw, cwp = self._codewords(codewords, B, self.nvar)
+        check(lib.lutldpc_bp_sample_qllr(self._h, int(seed), int(stream), int(frame0), int(B), cwp, _p(q, C.c_int32), _p(unc, C.c_int32)))
+        return q, unc
+
+    def sim_batch(self, seed, stream, frame0, B, K_info, codewords=None, want_qllr=False, want_bits=False):
+        """{bp_decode return value, frame error, data bit errors over the first K_info nodes, uncoded errors} [B, 4] int32 of frames
+        frame0 .. frame0+B-1 (sampler + decode + counters on the device); with want_qllr / want_bits a tuple (stats[, qllr][, bits])."""
+        stats = np.empty((B, 4), np.int32)
+        q = np.empty((B, self.nvar), np.int32) if want_qllr else None
+        bits = np.empty((B, self.nvar), np.uint8) if want_bits else None
+        cw, cwp = self._codewords(codewords, B, self.nvar)
+        check(lib.lutldpc_bp_sim_batch(self._h, int(seed), int(stream), int(frame0), int(B), cwp, int(K_info), _p(stats, C.c_int32),
+                                       _p(q, C.c_int32) if want_qllr else None, _p(bits, C.c_uint8) if want_bits else None))
+        out = (stats,) + ((q,) if want_qllr else ()) + ((bits,) if want_bits else ())
+        return out if len(out) > 1 else stats
+
+
+def awgn_cells(N0, d1=12, d4=28):
+    """The cell table of x ~ N(1, N0/2) for to_qllr(4x/N0) (lutldpc_bp_awgn_cells): {"thr": uint64[n - 1], "qllr": int32[n],
+    "neg": uint8[n]}.  Host only."""
+    n = C.c_int32(0)
+    rc = lib.lutldpc_bp_awgn_cells(int(d1), int(d4), float(N0), 0, C.byref(n), None, None, None)      # the count: cap 0 is always short
+    if rc != ERR_ARG or n.value < 1:
+        raise LutLdpcError(rc, last_error())
+    thr, q, neg = np.zeros(max(n.value - 1, 1), np.uint64), np.zeros(n.value, np.int32), np.zeros(n.value, np.uint8)
+    check(lib.lutldpc_bp_awgn_cells(int(d1), int(d4), float(N0), n.value, C.byref(n), _p(thr, C.c_uint64), _p(q, C.c_int32), _p(neg, C.c_uint8)))
+    return {"thr": thr[:n.value - 1], "qllr": q, "neg": neg}
 
 
 def awgn_llr(seed, stream, frame0, B, N, N0, codewords=None):

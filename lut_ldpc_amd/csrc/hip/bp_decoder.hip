@@ -10,28 +10,15 @@
 // the running right sum on the way down (5 row accesses per edge instead of 2, no scratch memory for degree-32 checks).
 // Algorithmic bytes per iteration and frame: check pass 2*E*4, variable pass (2*E + 2*N)*4 -- about 16x the nibble-row LUT
 // decoder, which is the point of the comparison.
-#include "../../../include/lut_ldpc_hip.h"
-#include "../../../include/lut_ldpc_bp.h"
-#include "kernels_common.hpp"      // launch_k: every kernel argument segment <= 128 bytes
-
-#include <hip/hip_runtime.h>
+#include "bp_state.hpp"
 
 #include <cmath>
 #include <cstring>
 #include <memory>
-#include <string>
-#include <vector>
 
-extern "C" void lutldpc_set_last_error(const char *msg);
+using namespace lutldpc_bp;
 
 namespace {
-
-int bp_fail(int code, const std::string &msg) { lutldpc_set_last_error(msg.c_str()); return code; }
-#define BP_TRY(expr)                                                                                    \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return bp_fail(LUTLDPC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 constexpr int kMaxTable = 2048;
 
@@ -182,40 +169,17 @@ __global__ __launch_bounds__(256) void bp_vn_kernel(const int32_t *__restrict__ 
         for (int e = e0; e < e1; e++) mvc[(size_t)e * Bp + f] = bp_clip(s - mcv[(size_t)e * Bp + f], qmax);
     }
 }
-// rows -> frame-major bits (LLRout < 0) and, optionally, LLRout itself
+// rows -> frame-major bits (LLRout < 0) and / or the values themselves (either may be null)
 __global__ __launch_bounds__(256) void bp_store_kernel(const int32_t *__restrict__ rows, uint8_t *__restrict__ bits, int32_t *__restrict__ q, int B, int N, int Bpad)
 {
     const int f = blockIdx.y * 256 + threadIdx.x;
     if (f >= B) return;
     for (int v = blockIdx.x; v < N; v += gridDim.x) {
         const int x = rows[(size_t)v * Bpad + f];
-        bits[(size_t)f * N + v] = x < 0 ? 1 : 0;
+        if (bits) bits[(size_t)f * N + v] = x < 0 ? 1 : 0;
         if (q) q[(size_t)f * N + v] = x;
     }
 }
-
-template <class T>
-struct Buf {
-    T *p = nullptr; size_t n = 0;
-    hipError_t alloc(size_t c) { if (c <= n) return hipSuccess; release(); hipError_t e = hipMalloc((void **)&p, c * sizeof(T)); if (e == hipSuccess) n = c; else p = nullptr; return e; }
-    hipError_t upload(const std::vector<T> &h) { hipError_t e = alloc(h.size() ? h.size() : 1); if (e != hipSuccess || h.empty()) return e; return hipMemcpy(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice); }
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-
-}  // namespace
-
-struct lutldpc_bp_decoder {
-    int nvar = 0, nchk = 0, E = 0, d1 = 12, d2 = 300, d3 = 7, d4 = 28, qmax = 0;
-    int max_iters = 50, psc = 1, pisc = 0, device = -1;
-    std::vector<int32_t> vn_ptr, cn_ptr, cn_idx, cn_vn, table;
-    hipStream_t stream = nullptr;
-    Buf<int32_t> d_vn_ptr, d_cn_ptr, d_cn_idx, d_cn_vn, d_table, d_mvc, d_mcv, d_in, d_out, d_iters, d_q_in, d_q_out;
-    Buf<double> d_llr;
-    Buf<uint8_t> d_active, d_bits;
-    Buf<uint32_t> d_fail;
-};
-
-namespace {
 
 int to_qllr_host(const lutldpc_bp_decoder *d, double l) {
     const double v = std::floor(0.5 + std::ldexp(1.0, d->d1) * l);
@@ -223,6 +187,21 @@ int to_qllr_host(const lutldpc_bp_decoder *d, double l) {
     if (v >= (double)d->qmax) return d->qmax;
     if (v <= -(double)d->qmax) return -d->qmax;
     return (int)v;
+}
+
+}  // namespace
+
+namespace lutldpc_bp {
+
+int alloc_rows(lutldpc_bp_decoder *d, int Bpad) {
+    BP_TRY(d->d_mvc.alloc((size_t)d->E * Bpad)); BP_TRY(d->d_mcv.alloc((size_t)d->E * Bpad));
+    BP_TRY(d->d_in.alloc((size_t)d->nvar * Bpad)); BP_TRY(d->d_out.alloc((size_t)d->nvar * Bpad));
+    BP_TRY(d->d_iters.alloc((size_t)Bpad)); BP_TRY(d->d_active.alloc((size_t)Bpad)); BP_TRY(d->d_fail.alloc((size_t)Bpad));
+    return LUTLDPC_OK;
+}
+
+void store_rows(lutldpc_bp_decoder *d, const int32_t *rows, uint8_t *bits, int32_t *q, int B, int Bpad) {
+    lutldpc::launch_k(bp_store_kernel, dim3((unsigned)std::min(d->nvar, 4096), (unsigned)(Bpad / 256)), dim3(256), 0, d->stream, rows, bits, q, B, d->nvar, Bpad);
 }
 
 int decode_rows(lutldpc_bp_decoder *d, int B, int Bpad) {
@@ -248,6 +227,10 @@ int decode_rows(lutldpc_bp_decoder *d, int B, int Bpad) {
     return LUTLDPC_OK;
 }
 
+}  // namespace lutldpc_bp
+
+namespace {
+
 int decode_common(lutldpc_bp_decoder *d, const double *llr, const int32_t *q, int B, uint8_t *out_bits, int32_t *out_iters, int32_t *out_qllr) {
     if (!d || (!llr && !q) || !out_bits || !out_iters) return bp_fail(LUTLDPC_ERR_ARG, "NULL argument");
     if (d->device < 0) return bp_fail(LUTLDPC_ERR_STATE, "BP decoder was created without a device (host-only handle)");
@@ -255,9 +238,7 @@ int decode_common(lutldpc_bp_decoder *d, const double *llr, const int32_t *q, in
     BP_TRY(hipSetDevice(d->device));
     const int Bpad = (B + 255) / 256 * 256;
     const size_t n = (size_t)B * d->nvar;
-    BP_TRY(d->d_mvc.alloc((size_t)d->E * Bpad)); BP_TRY(d->d_mcv.alloc((size_t)d->E * Bpad));
-    BP_TRY(d->d_in.alloc((size_t)d->nvar * Bpad)); BP_TRY(d->d_out.alloc((size_t)d->nvar * Bpad));
-    BP_TRY(d->d_iters.alloc((size_t)Bpad)); BP_TRY(d->d_active.alloc((size_t)Bpad)); BP_TRY(d->d_fail.alloc((size_t)Bpad));
+    if (int rc = alloc_rows(d, Bpad)) return rc;
     BP_TRY(d->d_bits.alloc(n));
     if (out_qllr) BP_TRY(d->d_q_out.alloc(n));
     const unsigned gy = (unsigned)(Bpad / 256), gxN = (unsigned)std::min(d->nvar, 4096);
@@ -271,7 +252,7 @@ int decode_common(lutldpc_bp_decoder *d, const double *llr, const int32_t *q, in
         lutldpc::launch_k(bp_load_kernel, dim3(gxN, gy), dim3(256), 0, d->stream, (const double *)nullptr, d->d_q_in.p, d->d_in.p, B, d->nvar, Bpad, 1.0, d->qmax);
     }
     if (int rc = decode_rows(d, B, Bpad)) return rc;
-    lutldpc::launch_k(bp_store_kernel, dim3(gxN, gy), dim3(256), 0, d->stream, d->d_out.p, d->d_bits.p, out_qllr ? d->d_q_out.p : nullptr, B, d->nvar, Bpad);
+    store_rows(d, d->d_out.p, d->d_bits.p, out_qllr ? d->d_q_out.p : nullptr, B, Bpad);
     BP_TRY(hipMemcpyAsync(out_bits, d->d_bits.p, n, hipMemcpyDeviceToHost, d->stream));
     BP_TRY(hipMemcpyAsync(out_iters, d->d_iters.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, d->stream));
     if (out_qllr) BP_TRY(hipMemcpyAsync(out_qllr, d->d_q_out.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, d->stream));
@@ -330,6 +311,7 @@ int lutldpc_bp_destroy(lutldpc_bp_decoder *d) {
         d->d_vn_ptr.release(); d->d_cn_ptr.release(); d->d_cn_idx.release(); d->d_cn_vn.release(); d->d_table.release(); d->d_mvc.release(); d->d_mcv.release();
         d->d_in.release(); d->d_out.release(); d->d_iters.release(); d->d_q_in.release(); d->d_q_out.release(); d->d_llr.release(); d->d_active.release();
         d->d_bits.release(); d->d_fail.release();
+        d->d_thr.release(); d->d_attr.release(); d->d_first.release(); d->d_cw.release(); d->d_unc.release(); d->d_stats.release();
         if (d->stream) (void)hipStreamDestroy(d->stream);
     }
     delete d;

@@ -51,6 +51,21 @@ lutldpc_channel_cells ChannelCellTable::view() const {
     return v;
 }
 
+// floor(2^64 * P(x <= t | +1 sent)), x ~ N(1, sigma^2): evaluated from the nearer tail, then never below the threshold before it
+uint64_t cumulative_threshold(double t, double sigma, uint64_t previous) {
+    const double two64 = 18446744073709551616.0;
+    const double z = (t - 1.0) / sigma;
+    uint64_t thr;
+    if (z <= 0) {
+        const double w = 0.5 * std::erfc(-z * 0.70710678118654752440) * two64;
+        thr = w >= two64 ? UINT64_MAX : (uint64_t)w;
+    } else {
+        const double w = 0.5 * std::erfc(z * 0.70710678118654752440) * two64;
+        thr = UINT64_MAX - (w >= two64 ? UINT64_MAX : (uint64_t)w);
+    }
+    return thr < previous ? previous : thr;
+}
+
 ChannelCellTable make_channel_cells(double N0, const vec &qb_Cha, const vec &qb_Msg, int mode, const ivec &map) {
     // thresholds in the domain of the received value x: LLR = 4x/N0 > b  <=>  x > b*N0/4
     struct T { double t; bool is_cha, is_msg; };
@@ -66,7 +81,6 @@ ChannelCellTable make_channel_cells(double N0, const vec &qb_Cha, const vec &qb_
     const int n = (int)th.size();
     const int Nq_Cha = (int)qb_Cha.size() + 1, Nq_Msg = mode == 0 ? (int)qb_Msg.size() + 1 : 0;
     const double sigma = std::sqrt(N0 / 2);
-    const double two64 = 18446744073709551616.0;
     ChannelCellTable C;
     int lc = 0, lm = 0;
     for (int j = 0; j <= n; j++) {      // cell j = (th[j-1], th[j]]
@@ -76,17 +90,7 @@ ChannelCellTable make_channel_cells(double N0, const vec &qb_Cha, const vec &qb_
         C.cha_m.push_back((uint8_t)(Nq_Cha - 1 - lc));
         C.msg_m.push_back((uint8_t)(mode == 0 ? Nq_Msg - 1 - lm : map.at((size_t)(Nq_Cha - 1 - lc))));
         if (j == n) break;
-        // P(x <= t | +1 sent), x ~ N(1, sigma^2); evaluated from the nearer tail
-        const double z = (th[(size_t)j].t - 1.0) / sigma;
-        uint64_t thr;
-        if (z <= 0) {
-            const double w = 0.5 * std::erfc(-z * 0.70710678118654752440) * two64;
-            thr = w >= two64 ? UINT64_MAX : (uint64_t)w;
-        } else {
-            const double w = 0.5 * std::erfc(z * 0.70710678118654752440) * two64;
-            thr = UINT64_MAX - (w >= two64 ? UINT64_MAX : (uint64_t)w);
-        }
-        if (!C.thr.empty() && thr < C.thr.back()) thr = C.thr.back();
+        const uint64_t thr = cumulative_threshold(th[(size_t)j].t, sigma, C.thr.empty() ? 0 : C.thr.back());
         C.thr.push_back(thr);
         if (th[(size_t)j].is_cha) lc++;
         if (th[(size_t)j].is_msg) lm++;
@@ -97,6 +101,46 @@ ChannelCellTable make_channel_cells(double N0, const vec &qb_Cha, const vec &qb_
 ChannelCellTable channel_cells_at(const LDPC_Code_LUT &C, double snr_db) {
     const int mode = C.get_initial_message_mode() == LDPC_Code_LUT::QCHA ? 1 : 0;
     return make_channel_cells(noise_n0(snr_db, C.get_rate()), C.get_qb_Cha(), C.get_qb_Msg(), mode, C.get_Nq_Cha_2_Nq_Msg_map());
+}
+
+// include/lut_ldpc_bp.h: lutldpc_bp_awgn_cells.  Thresholds T_k = (k + 0.5) N0 / (4 2^d1), k = -QMAX .. QMAX-1, between the cells
+// of QLLR k and k + 1, and Z at x = 0 between T_-1 and T_0.  The kept range is found by bisection on the cumulative threshold
+// (ascending in k), so the work is that of the cells kept, not of the 2^d4 the clip allows.
+int64_t bp_awgn_cell_count(int d1, int d4, double N0, int64_t *k_first, int64_t *k_last, bool *zero_split) {
+    const int64_t qmax = ((int64_t)1 << (d4 - 1)) - 1;
+    const double sigma = std::sqrt(N0 / 2), step = N0 / (4 * std::ldexp(1.0, d1));
+    const auto cum = [&](int64_t k) { return cumulative_threshold(((double)k + 0.5) * step, sigma, 0); };
+    // A: the first k whose threshold is positive (QMAX if none); L: the last k whose threshold is below 2^64 - 1 (-QMAX-1 if none)
+    int64_t lo = -qmax, hi = qmax;
+    while (lo < hi) { const int64_t mid = lo + (hi - lo) / 2; if (cum(mid) > 0) hi = mid; else lo = mid + 1; }
+    const int64_t A = lo;
+    lo = -qmax - 1; hi = qmax - 1;
+    while (lo < hi) { const int64_t mid = lo + (hi - lo + 1) / 2; if (cum(mid) < UINT64_MAX) lo = mid; else hi = mid - 1; }
+    const int64_t L = std::max(lo, A - 1);                         // cells A .. L + 1
+    const uint64_t z = cumulative_threshold(0.0, sigma, 0);
+    *k_first = A; *k_last = L;
+    *zero_split = A <= 0 && 0 <= L + 1 && z > 0 && z < UINT64_MAX;
+    return L + 1 - A + 1 + (*zero_split ? 1 : 0);
+}
+
+BpCellTable make_bp_awgn_cells(int d1, int d4, double N0) {
+    int64_t A, L; bool split;
+    const int64_t n = bp_awgn_cell_count(d1, d4, N0, &A, &L, &split);
+    if (n > LUTLDPC_BP_MAX_CELLS) throw std::length_error("the AWGN cell table needs " + std::to_string(n) + " cells, more than LUTLDPC_BP_MAX_CELLS");
+    const double sigma = std::sqrt(N0 / 2), step = N0 / (4 * std::ldexp(1.0, d1));
+    BpCellTable C;
+    C.thr.reserve((size_t)n); C.qllr.reserve((size_t)n); C.neg.reserve((size_t)n);
+    const auto cell = [&](int64_t q, double upper, bool last) {     // the cell below threshold `upper`
+        C.qllr.push_back((int32_t)q); C.neg.push_back((uint8_t)((last ? q < 0 : upper <= 0.0) ? 1 : 0));
+        if (!last) C.thr.push_back(cumulative_threshold(upper, sigma, C.thr.empty() ? 0 : C.thr.back()));
+    };
+    for (int64_t k = A; k <= L; k++) {
+        if (k == 0 && split) cell(0, 0.0, false);
+        cell(k, ((double)k + 0.5) * step, false);
+    }
+    if (L + 1 == 0 && split) cell(0, 0.0, false);
+    cell(L + 1, 0.0, true);
+    return C;
 }
 
 void philox4x32_10(uint32_t (&c)[4], uint64_t seed) {
@@ -455,6 +499,10 @@ LDPC_BER_Sim_BP::LDPC_BER_Sim_BP(const std::string &params, const std::string &b
     llr_calc_d2 = ini.get("BP.qllr_table_size", 300);
     llr_calc_d3 = ini.get("BP.qllr_spacing_res", 7);
     llr_calc_d4 = ini.get("BP.qllr_total_res", 28);           // 8 * sizeof(QLLR) - 4
+    // build-side: where the channel and the error counters run.  host (default): Box-Muller in doubles on the host cores, as ever;
+    // device: the cell sampler of include/lut_ldpc_bp.h on the uniforms of the [LUT] back-end -- another random stream
+    front_end = ini.get("BP.front_end", "host");
+    if (front_end != "host" && front_end != "device") throw std::runtime_error("BP.front_end must be host or device");
 }
 
 LDPC_BER_Sim_BP::~LDPC_BER_Sim_BP() { if (dec) lutldpc_bp_destroy(dec); }
@@ -485,6 +533,18 @@ void LDPC_BER_Sim_BP::sim_batch(double snr, int snr_index, int64_t frame0, int B
     if (!zero_codeword && !encoder_set) throw std::runtime_error("Non zero codewords require the encoder to be set!");
     std::vector<unsigned char> codewords;
     if (!zero_codeword) codewords = random_codewords(*G, seed, (uint32_t)snr_index, (uint64_t)frame0, B, N, K);
+    if (front_end == "device") {
+        if (cells_snr_index != snr_index) {        // one table per SNR point
+            const BpCellTable cells = make_bp_awgn_cells(llr_calc_d1, llr_calc_d4, N0);
+            const lutldpc_bp_cells view = cells.view();
+            if (lutldpc_bp_set_cells(dec, &view) != LUTLDPC_OK) throw std::runtime_error(std::string("LDPC_BER_Sim::sim_snr_point(): ") + lutldpc_last_error());
+            cells_snr_index = snr_index;
+        }
+        if (lutldpc_bp_sim_batch(dec, seed, (uint32_t)snr_index, (uint64_t)frame0, B, codewords.empty() ? nullptr : codewords.data(), K,
+                                 reinterpret_cast<int32_t *>(stats), nullptr, nullptr) != LUTLDPC_OK)
+            throw std::runtime_error(std::string("LDPC_BER_Sim::sim_snr_point(): ") + lutldpc_last_error());
+        return;
+    }
     std::vector<double> llr((size_t)B * N);
     std::vector<int32_t> unc((size_t)B), iters((size_t)B);
     std::vector<uint8_t> bits((size_t)B * N);

@@ -9,7 +9,8 @@
 //     so the counters are exactly what a frame-by-frame loop over the same frames would give;
 //   * random numbers are Philox-addressed per (seed, SNR index, frame), see kernels_frontend.hpp;
 //   * the [BP] branch (IT++'s own BP decoder, src/LDPC_BER_Sim.cpp:157-244) is LDPC_BER_Sim_BP: the comparison decoder of
-//     include/lut_ldpc_bp.h on the device behind a host AWGN front end (PARITY UNPINNED: the IT++ fork is absent).
+//     include/lut_ldpc_bp.h on the device behind a host AWGN front end, or (BP.front_end = device) with its channel and error
+//     counters on the device as well (PARITY UNPINNED: the IT++ fork is absent).
 #pragma once
 #include "ldpc_code_lut.hpp"
 #include "lut_ldpc_hip.h"
@@ -48,6 +49,23 @@ struct ChannelCellTable {
 // N0: noise spectral density (variance N0/2 per dimension), boundaries in the LLR domain; mode as
 // LDPC_Code_LUT::initial_message_mode_t (QCHA derives the message label from the channel label)
 ChannelCellTable make_channel_cells(double N0, const vec &qb_Cha, const vec &qb_Msg, int initial_message_mode, const ivec &cha2msg_map);
+
+// floor(2^64 * P(x <= t)) for x ~ N(1, sigma^2), the nearer tail through erfc, raised to `previous` (the running maximum of a
+// table): the one routine behind every cumulative cell probability, of the LUT table above and of the [BP] table below
+uint64_t cumulative_threshold(double t, double sigma, uint64_t previous);
+
+// The [BP] front end's cells (include/lut_ldpc_bp.h: lutldpc_bp_cells, lutldpc_bp_awgn_cells): a cell per QLLR value of
+// to_qllr(4x/N0) with x ~ N(1, N0/2), QLLR 0 split at x = 0, zero-mass ends trimmed
+struct BpCellTable {
+    std::vector<uint64_t> thr;
+    std::vector<int32_t> qllr;
+    std::vector<uint8_t> neg;
+    lutldpc_bp_cells view() const { return lutldpc_bp_cells{(int32_t)qllr.size(), thr.data(), qllr.data(), neg.data()}; }
+};
+// the number of cells of that table without building it; the kept thresholds are k_first .. k_last (cells k_first .. k_last + 1)
+int64_t bp_awgn_cell_count(int d1, int d4, double N0, int64_t *k_first, int64_t *k_last, bool *zero_split);
+// throws std::length_error above LUTLDPC_BP_MAX_CELLS
+BpCellTable make_bp_awgn_cells(int d1, int d4, double N0);
 
 // N0 of an SNR point: Eb/N0 = SNRdB at unit bit energy (src/LDPC_BER_Sim.cpp:248)
 inline double noise_n0(double snr_db, double code_rate) { return std::pow(10.0, -snr_db / 10.0) / code_rate; }
@@ -189,10 +207,12 @@ public:
     void load() override;                                        // :157-244
     void sim_batch(double snr, int snr_index, int64_t frame0, int B, FrameStats *stats) override;
     int llr_calc_d1 = 12, llr_calc_d2 = 300, llr_calc_d3 = 7, llr_calc_d4 = 28;                // :75-78
+    std::string front_end = "host";  // BP.front_end (build-side): host = awgn_llr_frames + host counters, device = lutldpc_bp_sim_batch
     lutldpc_bp_decoder *decoder() { return dec; }
 
 private:
     lutldpc_bp_decoder *dec = nullptr;
+    int cells_snr_index = -1;        // the SNR point whose cell table the decoder holds (device front end)
 };
 
 // One run of a parameter file over several devices of a node (ber_sim_multi.cpp): `lanes` host threads per device, each with its

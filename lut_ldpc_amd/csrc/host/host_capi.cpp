@@ -316,6 +316,31 @@ int lutldpc_awgn_llr(uint64_t seed, uint32_t stream, uint64_t frame0, int B, int
     });
 }
 
+int lutldpc_bp_awgn_cells(int d1, int d4, double N0, int cap, int32_t *n_cells, uint64_t *thr, int32_t *qllr, uint8_t *slicer_neg) {
+    if (!n_cells || d1 < 0 || d1 > 24 || d4 < 8 || d4 > 29 || !(N0 > 0) || !(N0 < 1e300)) {
+        lutldpc_set_last_error("lutldpc_bp_awgn_cells: NULL n_cells, d1 outside 0 .. 24, d4 outside 8 .. 29 or N0 not positive and finite");
+        return LUTLDPC_ERR_ARG;
+    }
+    int64_t a, l; bool split;
+    const int64_t n = bp_awgn_cell_count(d1, d4, N0, &a, &l, &split);
+    if (n > LUTLDPC_BP_MAX_CELLS) {
+        lutldpc_set_last_error(("lutldpc_bp_awgn_cells: the table needs " + std::to_string(n) + " cells, more than LUTLDPC_BP_MAX_CELLS").c_str());
+        return LUTLDPC_ERR_UNSUPPORTED;
+    }
+    *n_cells = (int32_t)n;
+    if (cap < n || !thr || !qllr || !slicer_neg) {
+        lutldpc_set_last_error(("lutldpc_bp_awgn_cells: the table needs " + std::to_string(n) + " cells: cap is short or an array is NULL").c_str());
+        return LUTLDPC_ERR_ARG;
+    }
+    return guarded([&] {
+        const BpCellTable t = make_bp_awgn_cells(d1, d4, N0);
+        std::memcpy(thr, t.thr.data(), sizeof(uint64_t) * t.thr.size());
+        std::memcpy(qllr, t.qllr.data(), sizeof(int32_t) * t.qllr.size());
+        std::memcpy(slicer_neg, t.neg.data(), t.neg.size());
+        return LUTLDPC_OK;
+    });
+}
+
 struct lutldpc_bersim { std::unique_ptr<LDPC_BER_Sim> sim; };
 
 int lutldpc_bersim_create(const char *params_path, const char *base_dir, int seed, const char *custom_name, int device, lutldpc_bersim **out) {
