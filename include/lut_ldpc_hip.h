@@ -310,6 +310,36 @@ int lutldpc_decoder_sample_labels(lutldpc_decoder *d, const lutldpc_channel_cell
                                   uint64_t frame0, int B, const uint8_t *codewords, uint8_t *cha, uint8_t *msg0);
 
 /*
+ * Per-node channel classes of the sampler: punctured nodes (an erasure), known nodes (shortening, pilots), code bits of unequal
+ * reliability (the same channel at another SNR).  The handle keeps up to LUTLDPC_MAX_NODE_CLASSES cell tables and a class per
+ * node; the five entries that take `cells` -- sim_batch, sim_batch_random, sample_labels, sim_batch_histogram, sim_batch_events --
+ * sample with them when they are called with cells = NULL:
+ *   cells != NULL                      the caller's one table on every node, as ever; the handle's node channels are ignored
+ *   cells == NULL, node channels set   node v is sampled with tables[node_class[v]]
+ *   cells == NULL, none set            LUTLDPC_ERR_ARG (after the checks that come before the table: a host-only handle still
+ *                                      answers LUTLDPC_ERR_STATE)
+ * The sampling rule is that of one table, node by node: the 64-bit uniform of (frame, node v) does not depend on the table; the
+ * cell is the number of thresholds of tables[node_class[v]] that are <= it; labels, mirrored labels for a sent 1 and slicer_neg
+ * into frame_stats[3] as with one table.  The stop rule, K_info and the other columns of frame_stats are untouched: a caller who
+ * punctures accounts for the effective rate.
+ * set_node_channels: every table is checked as the `cells` of sim_batch (NULL member, n_cells 1..72, ascending thresholds, labels
+ *   inside the alphabets), every node_class[v] < n_classes: LUTLDPC_ERR_ARG; then a host-only handle: LUTLDPC_ERR_STATE.  The
+ *   tables, their bucket indices and the class bytes are copied to the device, into buffers the handle allocates once: setting
+ *   new tables per SNR point or per batch costs two small copies.  A call refused with LUTLDPC_ERR_ARG or LUTLDPC_ERR_STATE leaves
+ *   the earlier setting in place; after a LUTLDPC_ERR_HIP no classes are set.
+ *   n_classes = 0 or nc = NULL clears.  Clearing is a call like any other: on a host-only handle, which can never hold classes, it
+ *   too answers LUTLDPC_ERR_STATE (nothing was set, nothing changes) -- a caller that clears unconditionally may ignore that code.  describe() shows "node_channels": {"classes": n, "nodes": [nodes of every class]} while set.
+ *   The limit of 16 is what the sampler keeps in LDS: 16 * (576 + 288 + 1024) bytes.
+ */
+#define LUTLDPC_MAX_NODE_CLASSES 16
+typedef struct {
+    int32_t n_classes;                     /* 1 .. LUTLDPC_MAX_NODE_CLASSES; 0 clears */
+    const lutldpc_channel_cells *tables;   /* n_classes tables, each as sim_batch takes one */
+    const uint8_t *node_class;             /* nvar entries < n_classes; a class may have no node */
+} lutldpc_node_channels;
+int lutldpc_decoder_set_node_channels(lutldpc_decoder *d, const lutldpc_node_channels *nc);
+
+/*
  * Message-label histograms per dump, counted on the device (lut_ldpc_amd/csrc/hip/kernels_stats.hpp): the distribution of the
  * edge-message labels of a finite-length decode, to hold against the densities the LUT design assumed.
  *

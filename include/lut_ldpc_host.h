@@ -95,6 +95,19 @@ int lutldpc_codec_error_events(lutldpc_codec *c, double snr_db, uint64_t seed, u
 /* the channel cell table for that SNR (see lut_ldpc_hip.h): returns n_cells; arrays need 72 entries */
 int lutldpc_codec_channel_cells(lutldpc_codec *c, double snr_db, uint64_t *thr, uint8_t *cha, uint8_t *msg, uint8_t *neg,
                                 uint8_t *cha_m, uint8_t *msg_m);
+/* Per-node channel classes of the four entries above that sample (sim_batch, message_histogram, error_events, sample_labels):
+ * node v belongs to class node_class[v] (nvar entries, in the codec's column order), and class k sees the channel at snr_db +
+ * offset_db[k] dB: its table is the one lutldpc_codec_channel_cells gives for that SNR.  Two limits are exact: offset -inf is a
+ * punctured node (an erasure: two cells of probability 1/2, x = 0- and x = 0+, each with the labels of its side of 0), +inf a
+ * known bit (one cell, the top labels).  Nothing else is rescaled: N0 still comes from the SNR and the code's rate, so a caller who
+ * punctures accounts for the effective rate.  While classes are set, each of those entries builds the tables of its SNR point, sets
+ * them on the decoder (lutldpc_decoder_set_node_channels) and samples with them; set_node_channels itself only records them, on
+ * any codec.  n_classes = 0 clears (the arrays are not read).  ERR_ARG: n_classes outside 0 .. LUTLDPC_MAX_NODE_CLASSES, a NULL
+ * array, a NaN offset, an id >= n_classes. */
+int lutldpc_codec_set_node_channels(lutldpc_codec *c, const uint8_t *node_class, int n_classes, const double *offset_db);
+/* the cell table of class cls at that SNR, as lutldpc_codec_channel_cells returns the code's: returns n_cells; arrays need 72 entries */
+int lutldpc_codec_node_channel_cells(lutldpc_codec *c, double snr_db, int cls, uint64_t *thr, uint8_t *cha, uint8_t *msg, uint8_t *neg,
+                                     uint8_t *cha_m, uint8_t *msg_m);
 
 /* ber_sim: load() + run() [+ save()] of LDPC_BER_Sim_LUT for a parameter file (prog/ber_sim.cpp).
  * Returns the number of SNR points written to snr[cap] / counters[cap*5]

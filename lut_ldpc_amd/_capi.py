@@ -102,6 +102,22 @@ class _ccp(C.POINTER(ChannelCells)):
         return C.POINTER(ChannelCells).from_param(obj)
 
 
+class NodeChannels(C.Structure):
+    """lutldpc_node_channels (include/lut_ldpc_hip.h): the cell tables of the sampler's node classes and the class of every node."""
+    _fields_ = [("n_classes", C.c_int32), ("tables", C.POINTER(ChannelCells)), ("node_class", _u8p)]
+
+    @classmethod
+    def from_tables(cls, node_class, tables):
+        """From the class ids of the nodes and one table per class (dicts as Codec.channel_cells returns them, or ChannelCells).
+        Everything the pointers name stays alive on the instance."""
+        cells = [t if isinstance(t, ChannelCells) else ChannelCells.from_table(t) for t in tables]
+        arr = (ChannelCells * max(len(cells), 1))(*cells)
+        ids = np.ascontiguousarray(node_class, np.uint8)
+        nc = cls(len(cells), arr, ids.ctypes.data_as(_u8p))
+        nc._keep = (cells, arr, ids)
+        return nc
+
+
 class BPCells(C.Structure):
     """lutldpc_bp_cells (include/lut_ldpc_bp.h): the cell table of the [BP] decoder's device front end."""
     _fields_ = [("n_cells", C.c_int32), ("thr", _u64p), ("qllr", _ip), ("slicer_neg", _u8p)]
@@ -151,6 +167,7 @@ _SIGNATURES = {
     "lutldpc_decoder_sim_batch": (C.c_int, [_vp, _ccp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p, C.c_int, _ip, _u8p, _u8p]),
     "lutldpc_decoder_sample_labels": (C.c_int, [_vp, _ccp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p, _u8p, _u8p]),
     "lutldpc_decoder_sim_batch_random": (C.c_int, [_vp, _ccp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, _ip, _u8p, _u8p]),
+    "lutldpc_decoder_set_node_channels": (C.c_int, [_vp, C.POINTER(NodeChannels)]),
     "lutldpc_decoder_set_edge_groups": (C.c_int, [_vp, _ip, C.c_int]),
     "lutldpc_decoder_histogram_shape": (C.c_int, [_vp, C.c_int, _ip]),
     "lutldpc_decoder_histogram_batch": (C.c_int, [_vp, _u8p, _u8p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, _u8p, _ip, _i64p, C.c_int64, _ip]),
@@ -187,6 +204,8 @@ _SIGNATURES = {
     "lutldpc_codec_sample_labels": (C.c_int, [_vp, C.c_double, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, _u8p, _u8p, _u8p]),
     "lutldpc_codec_encode_random": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, _u8p]),
     "lutldpc_codec_channel_cells": (C.c_int, [_vp, C.c_double, _u64p, _u8p, _u8p, _u8p, _u8p, _u8p]),
+    "lutldpc_codec_set_node_channels": (C.c_int, [_vp, _u8p, C.c_int, _dp]),
+    "lutldpc_codec_node_channel_cells": (C.c_int, [_vp, C.c_double, C.c_int, _u64p, _u8p, _u8p, _u8p, _u8p, _u8p]),
     "lutldpc_ber_sim_run": (C.c_int, [_cp, _cp, C.c_int, _cp, C.c_int, C.c_int, C.c_int, _dp, _i64p, C.c_int]),
     "lutldpc_ber_sim_main": (C.c_int, [C.c_int, C.POINTER(C.c_char_p)]),
     "lutldpc_selftest_write_results_it": (C.c_int, [_cp, _dp, _i64p, C.c_int, C.c_int, C.c_int, C.c_double]),

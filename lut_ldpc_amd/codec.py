@@ -229,12 +229,33 @@ class Codec:
         first, count = (self.ninfo, self.rank) if parity_only else (0, self.nvar)
         return dec.encode_packed(data, first=first, count=count)
 
-    def channel_cells(self, snr_db):
+    def _cell_table(self, fn, *args):
         thr = np.zeros(72, np.uint64)
         arrs = [np.zeros(72, np.uint8) for _ in range(5)]
-        n = lib.lutldpc_codec_channel_cells(self._h, float(snr_db), _p(thr, C.c_uint64), *[_p(a, C.c_uint8) for a in arrs])
+        n = fn(self._h, *args, _p(thr, C.c_uint64), *[_p(a, C.c_uint8) for a in arrs])
         check(min(n, 0))
         return {"thr": thr[:n - 1], "cha": arrs[0][:n], "msg": arrs[1][:n], "neg": arrs[2][:n], "cha_m": arrs[3][:n], "msg_m": arrs[4][:n]}
+
+    def channel_cells(self, snr_db):
+        return self._cell_table(lib.lutldpc_codec_channel_cells, float(snr_db))
+
+    def set_node_channels(self, node_class, offsets_db=None):
+        """Per-node channel classes of sim_batch, message_histogram, error_events and sample_labels: node v belongs to class
+        node_class[v], class k sees the channel at snr_db + offsets_db[k] dB; -inf is a punctured node (an erasure), +inf a known
+        bit.  N0 still comes from the SNR and the code's rate: account for the effective rate of a punctured code yourself.
+        set_node_channels(None) clears."""
+        if node_class is None:
+            check(lib.lutldpc_codec_set_node_channels(self._h, None, 0, None))
+            return
+        ids = np.ascontiguousarray(node_class, np.uint8)
+        off = np.ascontiguousarray(offsets_db, np.float64)
+        if ids.shape != (self.nvar,) or off.ndim != 1:
+            raise ValueError("node_class must hold one class id per node, offsets_db one offset per class")
+        check(lib.lutldpc_codec_set_node_channels(self._h, _p(ids, C.c_uint8), len(off), _p(off, C.c_double)))
+
+    def node_channel_cells(self, snr_db, cls):
+        """The cell table of class `cls` at that SNR, as channel_cells returns the code's."""
+        return self._cell_table(lib.lutldpc_codec_node_channel_cells, float(snr_db), int(cls))
 
     def encode(self, info):
         info = np.ascontiguousarray(info, np.uint8)

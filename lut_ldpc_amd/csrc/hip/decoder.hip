@@ -81,6 +81,11 @@ void make_describe(lutldpc_decoder *d) {
           << kernels_of(TT_CHK, i, {"cn_minsum_fast_kernel", "lutldpc_jit_pass", d->min_lut ? "cn_minsum_generic_kernel" : "tree_pass_kernel<CHK>"}) << "\"}";
     }
     o << "],\"resident\":" << (resident_active(d) ? 1 : 0) << ",\"skewed_pipeline\":" << ((d->opt.skew && d->skew_ok) ? 1 : 0) << ",\"fused_bucket\":" << d->fused_bucket_id << ",\"compaction\":" << (d->opt.use_compact < 0 ? 2 : d->opt.use_compact) << ",\"compaction_min_groups\":" << compaction_min_groups(d) << ",\"chain_nodes\":" << (d->opt.use_chain ? d->n_chain_nodes : 0) << ",\"placement\":" << d->place_info;
+    if (const lutldpc_decoder::NodeChannels &nc = d->node_channels; nc.n > 0) {
+        o << ",\"node_channels\":{\"classes\":" << nc.n << ",\"nodes\":[";
+        for (int c = 0; c < nc.n; c++) o << (c ? "," : "") << nc.nodes[(size_t)c];
+        o << "]}";
+    }
     if (const lutldpc_decoder::Generator &gen = d->gen; gen.form != lutldpc_decoder::Generator::NONE) {
         o << ",\"generator\":{\"K\":" << gen.K << ",\"R\":" << gen.R;
         if (gen.form == lutldpc_decoder::Generator::SPARSE) o << ",\"form\":\"sparse\",\"terms\":" << gen.sparse.terms << ",\"block\":" << gen.sparse.block << ",\"depth\":" << gen.sparse.depth;

@@ -27,9 +27,14 @@ int fill_cells(const lutldpc_channel_cells *c, const lutldpc_decoder *d, Channel
     return LUTLDPC_OK;
 }
 
+int front_end_of(const lutldpc_channel_cells *cells, const lutldpc_decoder *d, FrontEnd &fe) {
+    fe.node_classes = !cells && d->node_channels.n > 0;
+    return fe.node_classes ? LUTLDPC_OK : fill_cells(cells, d, fe.C);
+}
+
 // sampler -> d_cha_t / d_msg0_t (tile layout); stats zeroed and slicer errors accumulated.  sent_rows: the sent bits of the
 // batch (sent_rows_of), null = all-zero codeword
-int sample_tiles(lutldpc_decoder *d, const ChannelCells &C, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *sent_rows) {
+int sample_tiles(lutldpc_decoder *d, const FrontEnd &fe, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *sent_rows) {
     int rc = ensure_batch(d, B);
     if (rc) return rc;
     const int Bpad = d->bpad(B), G = Bpad / d->tile(), N = d->nvar;
@@ -38,7 +43,20 @@ int sample_tiles(lutldpc_decoder *d, const ChannelCells &C, uint64_t seed, uint3
     Timed t(d, LUTLDPC_K_FRONTEND);
     const int ppt = 8, npairs = (N + 1) / 2;
     dim3 grid((unsigned)((npairs + 4 * ppt - 1) / (4 * ppt)), (unsigned)G);
-    DEV_PARAM(dC, d, C);
+    if (fe.node_classes) {
+        const lutldpc_decoder::NodeChannels &nc = d->node_channels;
+        if (nc.n < 1 || !nc.tables.p || !nc.node_class.p || nc.node_class.n < (size_t)N) return fail(LUTLDPC_ERR_STATE, "sampler: no node channels on the device");
+        const NodeClassTable *tables = reinterpret_cast<const NodeClassTable *>(nc.tables.p);
+        if (sent_rows)
+            PACK_DISPATCH(d, launch_k(sample_labels_classes_kernel<PK, true>, grid, dim3(256), 0, d->stream, tables, nc.node_class.p, (uint32_t)seed, (uint32_t)(seed >> 32), stream,
+                               frame0, B, N, sent_rows, d->d_cha_t.p, d->d_msg0_t.p, d->d_stats.p, ppt));
+        else
+            PACK_DISPATCH(d, launch_k(sample_labels_classes_kernel<PK>, grid, dim3(256), 0, d->stream, tables, nc.node_class.p, (uint32_t)seed, (uint32_t)(seed >> 32), stream,
+                               frame0, B, N, sent_rows, d->d_cha_t.p, d->d_msg0_t.p, d->d_stats.p, ppt));
+        LAUNCH_CHECK();
+        return LUTLDPC_OK;
+    }
+    DEV_PARAM(dC, d, fe.C);
     if (sent_rows)
         PACK_DISPATCH(d, launch_k(sample_labels_kernel<PK, true>, grid, dim3(256), 0, d->stream, dC, (uint32_t)seed, (uint32_t)(seed >> 32), stream, frame0, B, N,
                            sent_rows, d->d_cha_t.p, d->d_msg0_t.p, d->d_stats.p, ppt));
@@ -58,11 +76,11 @@ int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint6
     if (rc) return rc;
     if (K_info < 0 || K_info > d->nvar) return fail(LUTLDPC_ERR_ARG, "bad K_info");
     if (device_codewords && (rc = require_generator(d, "sim_batch_random: no generator set (lutldpc_decoder_set_generator)"))) return rc;
-    ChannelCells C;
-    if ((rc = fill_cells(cells, d, C))) return rc;
+    FrontEnd fe;
+    if ((rc = front_end_of(cells, d, fe))) return rc;
     const uint8_t *sent_rows = nullptr;
     if ((rc = sent_rows_of(d, codewords, device_codewords, seed, stream, frame0, B, &sent_rows))) return rc;
-    if ((rc = sample_tiles(d, C, seed, stream, frame0, B, sent_rows))) return rc;
+    if ((rc = sample_tiles(d, fe, seed, stream, frame0, B, sent_rows))) return rc;
     // the sampled labels, read back from the rows before the decode works on them: a decode that compacts leaves the channel rows
     // in slot order (launch_uncompaction brings back the decided bits and the iteration codes only)
     if (cha_out && (rc = rows_to_host(d, d->d_cha_t.p, cha_out, B))) return rc;
@@ -89,6 +107,49 @@ int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint6
 
 extern "C" {
 
+int lutldpc_decoder_set_node_channels(lutldpc_decoder *d, const lutldpc_node_channels *nc) {
+    if (!d) return fail(LUTLDPC_ERR_ARG, "NULL decoder");
+    const int n = nc ? nc->n_classes : 0;
+    if (n < 0 || n > LUTLDPC_MAX_NODE_CLASSES) return fail(LUTLDPC_ERR_ARG, "node channels: n_classes outside [0," + std::to_string(LUTLDPC_MAX_NODE_CLASSES) + "]");
+    static_assert(LUTLDPC_MAX_NODE_CLASSES == kMaxNodeClasses, "the header's limit is the kernel's");
+    std::vector<NodeClassTable> tables((size_t)n);
+    std::vector<int> nodes((size_t)n, 0);
+    if (n > 0) {
+        if (!nc->tables || !nc->node_class) return fail(LUTLDPC_ERR_ARG, "node channels: NULL member");
+        for (int c = 0; c < n; c++) {
+            ChannelCells C;
+            if (int rc = fill_cells(&nc->tables[c], d, C)) return rc;
+            fill_node_class_table(C, tables[(size_t)c]);
+        }
+        for (int v = 0; v < d->nvar; v++) {
+            if (nc->node_class[v] >= n) return fail(LUTLDPC_ERR_ARG, "node channels: node_class[" + std::to_string(v) + "] outside [0, n_classes)");
+            nodes[nc->node_class[v]]++;
+        }
+    }
+    if (int rc = device_entry(d)) return rc;
+    // Everything above refuses without touching the setting.  From here on only the HIP runtime can fail, and then no classes are
+    // set.  The two buffers are allocated once, for the largest record (16 tables, nvar bytes), and written in place: a caller that
+    // sets new tables for every SNR point or batch (the codec layer does) pays two small copies, no allocation.
+    lutldpc_decoder::NodeChannels &cur = d->node_channels;
+    HIP_TRY(hipStreamSynchronize(d->stream));      // (no sampler launch still reads the record)
+    // describe() shows the classes and their node counts only; its checksums are not computed again where those stay
+    const bool shown = n != cur.n || nodes != cur.nodes;
+    cur.n = 0;
+    if (n > 0) {
+        HIP_TRY(cur.tables.alloc((size_t)kMaxNodeClasses * sizeof(NodeClassTable) / sizeof(uint64_t)));
+        HIP_TRY(cur.node_class.alloc((size_t)d->nvar));
+        HIP_TRY(hipMemcpy(cur.tables.p, tables.data(), (size_t)n * sizeof(NodeClassTable), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(cur.node_class.p, nc->node_class, (size_t)d->nvar, hipMemcpyHostToDevice));
+        cur.n = n;
+    } else {
+        cur.tables.release();
+        cur.node_class.release();
+    }
+    cur.nodes = nodes;
+    if (shown) make_describe(d);
+    return LUTLDPC_OK;
+}
+
 int lutldpc_decoder_sim_batch(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0, int B,
                               const uint8_t *codewords, int K_info, int32_t *frame_stats, uint8_t *cha_out, uint8_t *bits_out) {
     return sim_batch_impl(d, cells, seed, stream, frame0, B, codewords, false, K_info, frame_stats, cha_out, bits_out);
@@ -104,11 +165,11 @@ int lutldpc_decoder_sample_labels(lutldpc_decoder *d, const lutldpc_channel_cell
     if (!d || !cha || !msg0) return fail(LUTLDPC_ERR_ARG, "NULL argument");
     int rc = batch_entry(d, B, stream);
     if (rc) return rc;
-    ChannelCells C;
-    if ((rc = fill_cells(cells, d, C))) return rc;
+    FrontEnd fe;
+    if ((rc = front_end_of(cells, d, fe))) return rc;
     const uint8_t *sent_rows = nullptr;
     if ((rc = sent_rows_from_host(d, codewords, B, &sent_rows))) return rc;
-    if ((rc = sample_tiles(d, C, seed, stream, frame0, B, sent_rows))) return rc;
+    if ((rc = sample_tiles(d, fe, seed, stream, frame0, B, sent_rows))) return rc;
     if ((rc = rows_to_host(d, d->d_cha_t.p, cha, B)) || (rc = rows_to_host(d, d->d_msg0_t.p, msg0, B))) return rc;
     HIP_TRY(hipStreamSynchronize(d->stream));
     return LUTLDPC_OK;

@@ -41,7 +41,7 @@
 #include <vector>
 
 namespace lutldpc { LUTLDPC_FAST_LAUNCHERS(extern) }     // instantiated in fast_*.hip / fused_b*.hip
-namespace lutldpc { struct ChannelCells; }               // kernels_frontend.hpp
+namespace lutldpc { struct ChannelCells; struct FrontEnd; }      // kernels_frontend.hpp
 
 using namespace lutldpc;
 
@@ -224,6 +224,15 @@ struct lutldpc_decoder {
             DevBuf<uint64_t> inv;
         } sparse;
     } gen;
+    // Per-node channel classes of the sampler (lutldpc_decoder_set_node_channels, decoder_frontend.hip): n classes (0 = none set),
+    // their LDS images (n NodeClassTable of kernels_frontend.hpp, bucket index included) and the class byte of every node on the
+    // device (allocated once for 16 classes, written in place by every set); nodes[c] = nodes of class c, for describe().
+    struct NodeChannels {
+        int n = 0;
+        std::vector<int> nodes;
+        DevBuf<uint64_t> tables;
+        DevBuf<uint8_t> node_class;
+    } node_channels;
     // d_sent: the sent-bit rows of a batch; d_enc_rows: the bit rows encode_packed works on with the sparse form (its own: no entry
     // of a decode reads or writes them)
     DevBuf<uint8_t> d_sent, d_enc_rows;
@@ -455,8 +464,12 @@ int launch_resident(lutldpc_decoder *d, int G, int B, const FrameMajorIO *fm = n
 // ---- decoder_frontend.hip (home of the kernels of kernels_frontend.hpp)
 hipError_t preload_frontend_kernels();
 int fill_cells(const lutldpc_channel_cells *c, const lutldpc_decoder *d, ChannelCells &C);
-// sampler -> d_cha_t / d_msg0_t; sent_rows: the sent bits as sent-bit rows (device), null = all-zero codeword
-int sample_tiles(lutldpc_decoder *d, const ChannelCells &C, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *sent_rows);
+// what an entry that takes `cells` samples with: the caller's table where one is given (fill_cells), else the handle's node
+// channels, else the LUTLDPC_ERR_ARG of fill_cells for a NULL table
+int front_end_of(const lutldpc_channel_cells *cells, const lutldpc_decoder *d, FrontEnd &fe);
+// sampler -> d_cha_t / d_msg0_t, with either front end: the only place that chooses the kernel; sent_rows: the sent bits as
+// sent-bit rows (device), null = all-zero codeword
+int sample_tiles(lutldpc_decoder *d, const FrontEnd &fe, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *sent_rows);
 // lutldpc_decoder_sim_batch / _random; req != null: the capture of decoder_events.hip on top (lutldpc_decoder_sim_batch_events)
 int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *codewords,
                    bool device_codewords, int K_info, int32_t *frame_stats, uint8_t *cha_out, uint8_t *bits_out, lutldpc_event_request *req = nullptr);

@@ -174,11 +174,11 @@ int lutldpc_decoder_sim_batch_histogram(lutldpc_decoder *d, const lutldpc_channe
     int nd = 0, rc;
     if ((rc = hist_check_args(d, B, level, mode, n_labels, hist, hist_cap, &nd, stream))) return rc;
     if (device_codewords && (rc = require_generator(d, "sim_batch_histogram: no generator set (lutldpc_decoder_set_generator)"))) return rc;
-    ChannelCells C;
-    if ((rc = fill_cells(cells, d, C))) return rc;
+    FrontEnd fe;
+    if ((rc = front_end_of(cells, d, fe))) return rc;
     const uint8_t *sent_rows = nullptr;
     if ((rc = sent_rows_of(d, codewords, device_codewords != 0, seed, stream, frame0, B, &sent_rows))) return rc;
-    auto fill = [&]() -> int { return sample_tiles(d, C, seed, stream, frame0, B, sent_rows); };   // (a pure function of seed, stream, frame)
+    auto fill = [&]() -> int { return sample_tiles(d, fe, seed, stream, frame0, B, sent_rows); };   // (a pure function of seed, stream, frame)
     if ((rc = fill())) return rc;
     if ((rc = histogram_tiles(d, B, level, mode, n_labels, sent_rows, fill, nullptr, nullptr, hist, nd))) return rc;
     if (n_dumps) *n_dumps = nd;

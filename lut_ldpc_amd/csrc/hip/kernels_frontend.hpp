@@ -34,6 +34,12 @@ struct ChannelCells {
     uint8_t msg_m[kMaxCells];
 };
 
+// what an entry samples with: the caller's one table, or the per-node classes the handle holds (sample_labels_classes_kernel)
+struct FrontEnd {
+    ChannelCells C;
+    bool node_classes = false;
+};
+
 struct Philox {
     __host__ __device__ static inline void round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
         const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
@@ -148,6 +154,133 @@ __global__ __launch_bounds__(256) void sample_labels_kernel(const ChannelCells *
                 const uint32_t at = attr_lds[cell], sel = bit ? at >> 16 : at;
                 const uint32_t a = sel & 0x7Fu, m = (sel >> 8) & 0xFFu;
                 // slicer decision: neg for bit 0, its mirror for bit 1 -- wrong exactly when the cell lies on the negative side
+                unc[j] += (int)((at >> 7) & 1u);
+                ca[hh][j / 4] |= a << (8 * (j & 3));
+                ms[hh][j / 4] |= m << (8 * (j & 3));
+            }
+        }
+#pragma unroll
+        for (int hh = 0; hh < 2; hh++) {
+            const int v = 2 * p + hh;
+            if (v >= N) continue;
+            *reinterpret_cast<uint32_t *>(cha_t + ((size_t)g * N + v) * kRowBytes + lane * 4) = pack_halves<PACK>(ca[hh]);
+            *reinterpret_cast<uint32_t *>(msg_t + ((size_t)g * N + v) * kRowBytes + lane * 4) = pack_halves<PACK>(ms[hh]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < F; j++) {
+        const int fl = (g * kWave + lane) * F + j;
+        if (fl < B && unc[j]) atomicAdd(&stats[(size_t)fl * 4 + 3], unc[j]);
+    }
+}
+
+// ---- per-node channel classes (lutldpc_decoder_set_node_channels): node v is sampled with table node_class[v] -----------------
+// One class as the sampler wants it in LDS, made once by the setter: thresholds padded as sample_labels_kernel pads them, the
+// packed labels of every cell, the bucket index first[bucket] = number of thresholds <= the bucket's lower end.
+constexpr int kMaxNodeClasses = 16;     // LUTLDPC_MAX_NODE_CLASSES: 16 * (576 + 288 + 1024) B = 30208 B of static LDS
+struct NodeClassTable {
+    uint64_t thr[kMaxCells];
+    uint32_t attr[kMaxCells];           // cha | neg << 7 | msg << 8 | cha_m << 16 | msg_m << 24
+    uint8_t first[1 << kBucketBits];
+    int32_t n_thr, pad;
+};
+static_assert(sizeof(NodeClassTable) % 8 == 0, "the tables of the classes follow each other as 64-bit words");
+
+// the host twin of the prologue of sample_labels_kernel: C -> its LDS image (first[] by the same upper-bound search)
+inline void fill_node_class_table(const ChannelCells &C, NodeClassTable &T) {
+    const int n_thr = C.n_cells - 1;
+    for (int j = 0; j < kMaxCells; j++) {
+        const int t = j < C.n_cells ? j : 0;
+        T.thr[j] = C.thr[j < n_thr ? j : 0];
+        T.attr[j] = (uint32_t)C.cha[t] | ((uint32_t)C.neg[t] << 7) | ((uint32_t)C.msg[t] << 8) | ((uint32_t)C.cha_m[t] << 16) | ((uint32_t)C.msg_m[t] << 24);
+    }
+    int cell = 0;
+    for (int b = 0; b < (1 << kBucketBits); b++) {
+        const uint64_t lo = (uint64_t)b << (64 - kBucketBits);
+        while (cell < n_thr && C.thr[cell] <= lo) cell++;          // ascending thresholds: the count never falls from one bucket to the next
+        T.first[b] = (uint8_t)cell;
+    }
+    T.n_thr = n_thr; T.pad = 0;
+}
+
+// sample_labels_kernel with the table chosen per node: same grid, same uniforms, same rows and stats.  A wave's lanes are frames
+// of ONE node, so the class byte is read once per node as a wave-uniform value and becomes three LDS base offsets; the search of
+// a sample is cell_from_bucket on the class's slice.  The prologue copies the LDS images of the classes that occur among the
+// workgroup's nodes from device memory (coalesced dwords): no bucket index is built here.  Every class id was checked by the
+// setter (< n_classes <= kMaxNodeClasses); nodes beyond N are never looked up.
+template <int PACK, bool SENT_ROWS = false>
+__global__ __launch_bounds__(256) void sample_labels_classes_kernel(const NodeClassTable *__restrict__ tables, const uint8_t *__restrict__ node_class, uint32_t seed_lo,
+                                                                    uint32_t seed_hi, uint32_t stream, uint64_t frame0, int B, int N, const uint8_t *__restrict__ sent,
+                                                                    uint8_t *__restrict__ cha_t, uint8_t *__restrict__ msg_t, int32_t *__restrict__ stats, int pairs_per_thread)
+{
+    constexpr int F = 4 * PACK;                                     // frames per lane
+    constexpr int kFirstDwords = (1 << kBucketBits) / 4;
+    __shared__ uint64_t thr_lds[kMaxNodeClasses * kMaxCells];
+    __shared__ uint32_t attr_lds[kMaxNodeClasses * kMaxCells];
+    __shared__ uint32_t first_lds[kMaxNodeClasses * kFirstDwords];
+    __shared__ int32_t nthr_lds[kMaxNodeClasses];
+    __shared__ uint32_t used_lds;
+    const int npairs = (N + 1) / 2;
+    if (threadIdx.x == 0) used_lds = 0;
+    __syncthreads();
+    {   // the classes of the workgroup's nodes: 4 waves x pairs_per_thread pairs, two nodes each
+        const int v0 = blockIdx.x * 4 * pairs_per_thread * 2, v1 = min(N, v0 + 4 * pairs_per_thread * 2);
+        uint32_t mine = 0;
+        for (int v = v0 + (int)threadIdx.x; v < v1; v += 256) mine |= 1u << node_class[v];
+        if (mine) atomicOr(&used_lds, mine);
+    }
+    __syncthreads();
+    const uint32_t used = used_lds;
+    for (int c = 0; c < kMaxNodeClasses; c++) {
+        if (!((used >> c) & 1u)) continue;                          // (workgroup-uniform)
+        const NodeClassTable &T = tables[c];
+        if (threadIdx.x < kMaxCells) { thr_lds[c * kMaxCells + threadIdx.x] = T.thr[threadIdx.x]; attr_lds[c * kMaxCells + threadIdx.x] = T.attr[threadIdx.x]; }
+        first_lds[c * kFirstDwords + threadIdx.x] = reinterpret_cast<const uint32_t *>(T.first)[threadIdx.x];      // 256 threads = 1024 bytes
+        if (threadIdx.x == 0) nthr_lds[c] = T.n_thr;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, g = blockIdx.y;
+    const int w = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    int p0 = w * pairs_per_thread, p1 = p0 + pairs_per_thread;
+    if (p1 > npairs) p1 = npairs;
+    int unc[F];
+#pragma unroll
+    for (int j = 0; j < F; j++) unc[j] = 0;
+    for (int p = p0; p < p1; p++) {
+        uint32_t ca[2][PACK], ms[2][PACK];
+#pragma unroll
+        for (int h = 0; h < PACK; h++) { ca[0][h] = ca[1][h] = 0; ms[0][h] = ms[1][h] = 0; }
+        uint32_t sb[2] = {0u, 0u};
+        const uint64_t *thr_c[2];
+        const uint32_t *attr_c[2];
+        const uint8_t *first_c[2];
+        int n_thr[2];
+#pragma unroll
+        for (int hh = 0; hh < 2; hh++) {
+            const int v = 2 * p + hh;
+            const int cls = v < N ? __builtin_amdgcn_readfirstlane((int)node_class[v]) : 0;      // (the pad node of an odd N is never sampled)
+            thr_c[hh] = thr_lds + cls * kMaxCells;
+            attr_c[hh] = attr_lds + cls * kMaxCells;
+            first_c[hh] = reinterpret_cast<const uint8_t *>(first_lds) + cls * (1 << kBucketBits);
+            n_thr[hh] = v < N ? nthr_lds[cls] : 0;
+            if constexpr (SENT_ROWS) { if (v < N) sb[hh] = sent_bits_of_lane<PACK>(sent, (size_t)g * N + v, lane); }
+        }
+#pragma unroll
+        for (int j = 0; j < F; j++) {
+            const int fl = (g * kWave + lane) * F + j;              // frame within the batch
+            if (fl >= B) continue;                                  // pad frames keep label 0
+            const uint64_t f = frame0 + (uint64_t)fl;
+            uint32_t c[4] = {(uint32_t)f, (uint32_t)(f >> 32), (uint32_t)p, stream};
+            Philox::gen(c, seed_lo, seed_hi);
+            const uint64_t u[2] = {((uint64_t)c[1] << 32) | c[0], ((uint64_t)c[3] << 32) | c[2]};
+#pragma unroll
+            for (int hh = 0; hh < 2; hh++) {
+                const int v = 2 * p + hh;
+                if (v >= N) continue;
+                const int cell = cell_from_bucket(thr_c[hh], first_c[hh], n_thr[hh], u[hh]);
+                const int bit = (int)((sb[hh] >> j) & 1u);          // (no sent rows: sb stays zero)
+                const uint32_t at = attr_c[hh][cell], sel = bit ? at >> 16 : at;
+                const uint32_t a = sel & 0x7Fu, m = (sel >> 8) & 0xFFu;
                 unc[j] += (int)((at >> 7) & 1u);
                 ca[hh][j / 4] |= a << (8 * (j & 3));
                 ms[hh][j / 4] |= m << (8 * (j & 3));

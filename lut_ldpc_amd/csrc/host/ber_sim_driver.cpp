@@ -37,6 +37,10 @@ void LDPC_BER_Sim_Results::write_itfile(const std::string &filename) const {
     f.write("ldpc_nvar", std::vector<double>{(double)ldpc_nvar});
     f.write("ldpc_nchk", std::vector<double>{(double)ldpc_nchk});
     f.write("ldpc_code_rate", std::vector<double>{ldpc_code_rate});
+    if (!channel_class_snr_offset_dB.empty()) {
+        f.write("channel_node_classes", channel_node_classes);
+        f.write("channel_class_snr_offset_dB", channel_class_snr_offset_dB);
+    }
     f.write("runtime", runtime);
     f.write("gitversion", std::string("lut_ldpc_amd-0.1"));
     f.close();
@@ -101,6 +105,60 @@ ChannelCellTable make_channel_cells(double N0, const vec &qb_Cha, const vec &qb_
 ChannelCellTable channel_cells_at(const LDPC_Code_LUT &C, double snr_db) {
     const int mode = C.get_initial_message_mode() == LDPC_Code_LUT::QCHA ? 1 : 0;
     return make_channel_cells(noise_n0(snr_db, C.get_rate()), C.get_qb_Cha(), C.get_qb_Msg(), mode, C.get_Nq_Cha_2_Nq_Msg_map());
+}
+
+void check_node_channel_classes(const uint8_t *node_class, int nvar, int n_classes, const double *offset_db, const std::string &what) {
+    if (n_classes < 1 || n_classes > LUTLDPC_MAX_NODE_CLASSES)
+        throw std::invalid_argument(what + ": " + std::to_string(n_classes) + " classes, 1 .. " + std::to_string(LUTLDPC_MAX_NODE_CLASSES) + " are possible");
+    if (!node_class || !offset_db) throw std::invalid_argument(what + ": NULL argument");
+    for (int c = 0; c < n_classes; c++)
+        if (std::isnan(offset_db[c])) throw std::invalid_argument(what + ": the offset of class " + std::to_string(c) + " is not a number");
+    for (int v = 0; v < nvar; v++)
+        if (node_class[v] >= n_classes)
+            throw std::invalid_argument(what + ": node " + std::to_string(v) + " has class " + std::to_string(node_class[v]) + ", beyond the " + std::to_string(n_classes) + " offsets");
+}
+
+ChannelCellTable node_channel_cells_at(const LDPC_Code_LUT &C, double snr_db, double offset_db) {
+    if (std::isnan(offset_db)) throw std::invalid_argument("node channel cells: the offset is not a number");
+    if (std::isfinite(offset_db)) return channel_cells_at(C, snr_db + offset_db);
+    const bool qcha = C.get_initial_message_mode() == LDPC_Code_LUT::QCHA;
+    const vec &qc = C.get_qb_Cha(), &qm = C.get_qb_Msg();
+    const ivec &map = C.get_Nq_Cha_2_Nq_Msg_map();
+    const int Nq_Cha = (int)qc.size() + 1, Nq_Msg = (int)qm.size() + 1;
+    ChannelCellTable T;
+    const auto cell = [&](int cha, int msg_cont, bool neg) {
+        T.cha.push_back((uint8_t)cha);
+        T.msg.push_back((uint8_t)(qcha ? map.at((size_t)cha) : msg_cont));
+        T.neg.push_back(neg ? 1 : 0);
+        T.cha_m.push_back((uint8_t)(Nq_Cha - 1 - cha));
+        T.msg_m.push_back((uint8_t)(qcha ? map.at((size_t)(Nq_Cha - 1 - cha)) : Nq_Msg - 1 - msg_cont));
+    };
+    if (offset_db > 0) {                 // known bit: x = +inf
+        cell(Nq_Cha - 1, Nq_Msg - 1, false);
+        T.thr.push_back(0);              // (no threshold: one entry, so that the view's pointer is not NULL)
+        return T;
+    }
+    // punctured: every boundary but one at 0 has run off to +-inf; x is 0- or 0+ with probability 1/2 each
+    const auto below = [](const vec &q, bool or_equal) { int n = 0; for (double b : q) n += (b < 0 || (or_equal && b == 0)) ? 1 : 0; return n; };
+    cell(below(qc, false), below(qm, false), true);
+    cell(below(qc, true), below(qm, true), false);
+    T.thr.push_back((uint64_t)1 << 63);
+    return T;
+}
+
+int set_point_cells(LDPC_Code_LUT &C, const NodeChannelClasses &nc, double snr_db, PointCells &pc) {
+    pc.classes = nc.set();
+    if (!pc.classes) {
+        pc.one = channel_cells_at(C, snr_db);
+        pc.view = pc.one.view();
+        return LUTLDPC_OK;
+    }
+    std::vector<ChannelCellTable> tables;
+    std::vector<lutldpc_channel_cells> views;
+    for (double off : nc.offset_db) tables.push_back(node_channel_cells_at(C, snr_db, off));
+    for (const ChannelCellTable &t : tables) views.push_back(t.view());
+    const lutldpc_node_channels record{(int32_t)views.size(), views.data(), nc.node_class.data()};
+    return lutldpc_decoder_set_node_channels(C.device_handle(), &record);
 }
 
 // include/lut_ldpc_bp.h: lutldpc_bp_awgn_cells.  Thresholds T_k = (k + 0.5) N0 / (4 2^d1), k = -QMAX .. QMAX-1, between the cells
@@ -192,6 +250,19 @@ LDPC_BER_Sim::LDPC_BER_Sim(const std::string &params, const std::string &base) :
     // the compaction of the surviving frames takes; 6.8 GB of rows) and costs the short codes nothing; the frame loop still
     // starts at 512 frames (one frame group) and quadruples (sim_snr_point), so a point that stops after Nfers errors wastes little work
     batch_frames = ini.get("Sim.batch_frames", 32768);
+    // build-side: per-node channel classes of the sampler ([LUT] only)
+    const auto nc_file = ini.lookup("Channel.node_classes_filename"), nc_off = ini.lookup("Channel.class_snr_offset_dB");
+    if ((bool)nc_file != (bool)nc_off)
+        throw std::runtime_error(std::string("Channel.") + (nc_file ? "class_snr_offset_dB" : "node_classes_filename") + " is missing: Channel.node_classes_filename and Channel.class_snr_offset_dB go together");
+    if (nc_file) {
+        node_classes_filename = *nc_file;
+        try { class_snr_offset_dB = parse_vec(*nc_off); }
+        catch (const std::exception &) { throw std::runtime_error("Channel.class_snr_offset_dB: not a list of numbers (inf and -inf are allowed): " + *nc_off); }
+        if (node_classes_filename.empty()) throw std::runtime_error("Channel.node_classes_filename is empty");
+        if (class_snr_offset_dB.empty() || class_snr_offset_dB.size() > LUTLDPC_MAX_NODE_CLASSES)
+            throw std::runtime_error("Channel.class_snr_offset_dB: " + std::to_string(class_snr_offset_dB.size()) + " offsets, 1 .. " + std::to_string(LUTLDPC_MAX_NODE_CLASSES) + " classes are possible");
+        for (double o : class_snr_offset_dB) if (std::isnan(o)) throw std::runtime_error("Channel.class_snr_offset_dB: an offset is not a number");
+    }
     codes_path = join(base, codes_dir);
     results_path = join(base, results_dir);
     fs::create_directories(codes_path);
@@ -378,6 +449,32 @@ void LDPC_BER_Sim_LUT::load() {
         C->set_exit_conditions(max_iter, parity_check_iter, parity_check_iter);
     }
     results = LDPC_BER_Sim_Results(codeword_length, codeword_length - dataword_length);
+    load_node_classes();
+}
+
+void LDPC_BER_Sim_LUT::load_node_classes() {
+    if (node_classes_filename.empty()) return;
+    const fs::path file = fs::path(join(codes_path, node_classes_filename));
+    std::ifstream f(file);
+    if (!f) throw std::runtime_error("Channel.node_classes_filename: cannot open " + file.string());
+    std::vector<uint8_t> ids;
+    const int n_classes = (int)class_snr_offset_dB.size();
+    for (std::string tok; f >> tok;) {
+        size_t used = 0;
+        long id = -1;
+        try { id = std::stol(tok, &used); } catch (const std::exception &) { used = 0; }
+        if (used != tok.size() || id < 0) throw std::runtime_error("Channel.node_classes_filename: '" + tok + "' in " + file.string() + " is not a class id");
+        if (id >= n_classes)
+            throw std::runtime_error("Channel.node_classes_filename: node " + std::to_string(ids.size()) + " has class " + std::to_string(id) + ", Channel.class_snr_offset_dB has " +
+                                     std::to_string(n_classes) + " offsets");
+        ids.push_back((uint8_t)id);
+    }
+    if ((int)ids.size() != codeword_length)
+        throw std::runtime_error("Channel.node_classes_filename: " + file.string() + " holds " + std::to_string(ids.size()) + " class ids, the code has " + std::to_string(codeword_length) + " nodes");
+    node_channels.node_class = ids;
+    node_channels.offset_db = class_snr_offset_dB;
+    results.channel_node_classes.assign(ids.begin(), ids.end());
+    results.channel_class_snr_offset_dB = class_snr_offset_dB;
 }
 
 std::string LDPC_BER_Sim_LUT::gen_filename() const {
@@ -388,10 +485,21 @@ std::string LDPC_BER_Sim_LUT::gen_filename() const {
     return fn.str();
 }
 
+int LDPC_BER_Sim_LUT::point_cells(double snr, int snr_index, PointCells &pc) {
+    if (node_channels.set() && classes_on && classes_on == C->device_handle() && classes_snr_index == snr_index) {
+        pc.classes = true;
+        return LUTLDPC_OK;
+    }
+    const int rc = set_point_cells(*C, node_channels, snr, pc);
+    classes_on = rc == LUTLDPC_OK && node_channels.set() ? C->device_handle() : nullptr;
+    classes_snr_index = snr_index;
+    return rc;
+}
+
 void LDPC_BER_Sim_LUT::sim_batch(double snr, int snr_index, int64_t frame0, int B, FrameStats *stats) {
     const int N = codeword_length, K = dataword_length;
-    const ChannelCellTable cells = channel_cells_at(*C, snr);
-    const lutldpc_channel_cells view = cells.view();
+    PointCells pc;
+    if (point_cells(snr, snr_index, pc) != LUTLDPC_OK) throw std::runtime_error(std::string("LDPC_BER_Sim_LUT::sim_snr_point(): ") + lutldpc_last_error());
     const uint64_t seed = (uint64_t)(int64_t)(rand_seed + rand_seed_offset);      // RNG_reset(rand_seed + rand_seed_offset), :129
     if (!zero_codeword && !encoder_set) throw std::runtime_error("Non zero codewords require the encoder to be set!");
     // random codewords are made on the device, next to the sampler (the same codewords as random_info_bits + encode: a pure
@@ -407,7 +515,7 @@ void LDPC_BER_Sim_LUT::sim_batch(double snr, int snr_index, int64_t frame0, int 
         // prints the dumps frame after frame (LDPC_Code_LUT::lut_decode_batch_dump), the counters are taken on the host.
         std::vector<uint8_t> cha((size_t)B * N), msg((size_t)B * N), bits((size_t)B * N);
         std::vector<int32_t> its((size_t)B);
-        if (lutldpc_decoder_sample_labels(C->device_handle(), &view, seed, (uint32_t)snr_index, (uint64_t)frame0, B, cwp, cha.data(), msg.data()) != LUTLDPC_OK)
+        if (lutldpc_decoder_sample_labels(C->device_handle(), pc.cells(), seed, (uint32_t)snr_index, (uint64_t)frame0, B, cwp, cha.data(), msg.data()) != LUTLDPC_OK)
             throw std::runtime_error(std::string("LDPC_BER_Sim_LUT::sim_snr_point(): ") + lutldpc_last_error());
         const int nzc = C->get_Nq_Cha() / 2;
         for (int i = 0; i < B; i++) {
@@ -427,9 +535,9 @@ void LDPC_BER_Sim_LUT::sim_batch(double snr, int snr_index, int64_t frame0, int 
     std::vector<uint8_t> cha_dump, bits_dump;
     if (decoder_output_verbosity > 0) { cha_dump.resize((size_t)B * N); bits_dump.resize((size_t)B * N); }
     const int rc = device_codewords
-        ? lutldpc_decoder_sim_batch_random(C->device_handle(), &view, seed, (uint32_t)snr_index, (uint64_t)frame0, B, K, reinterpret_cast<int32_t *>(stats),
+        ? lutldpc_decoder_sim_batch_random(C->device_handle(), pc.cells(), seed, (uint32_t)snr_index, (uint64_t)frame0, B, K, reinterpret_cast<int32_t *>(stats),
                                            cha_dump.empty() ? nullptr : cha_dump.data(), bits_dump.empty() ? nullptr : bits_dump.data())
-        : lutldpc_decoder_sim_batch(C->device_handle(), &view, seed, (uint32_t)snr_index, (uint64_t)frame0, B, cwp, K, reinterpret_cast<int32_t *>(stats),
+        : lutldpc_decoder_sim_batch(C->device_handle(), pc.cells(), seed, (uint32_t)snr_index, (uint64_t)frame0, B, cwp, K, reinterpret_cast<int32_t *>(stats),
                                     cha_dump.empty() ? nullptr : cha_dump.data(), bits_dump.empty() ? nullptr : bits_dump.data());
     if (rc != LUTLDPC_OK) throw std::runtime_error(std::string("LDPC_BER_Sim_LUT::sim_snr_point(): ") + lutldpc_last_error());
     for (int i = 0; i < B && !cha_dump.empty(); i++) C->print_stimuli(&cha_dump[(size_t)i * N], &bits_dump[(size_t)i * N]);
@@ -438,29 +546,29 @@ void LDPC_BER_Sim_LUT::sim_batch(double snr, int snr_index, int64_t frame0, int 
 // the frames of sim_batch -- same seed, same stream, same codewords -- with their edge messages counted instead of their errors
 int LDPC_BER_Sim_LUT::message_histogram(double snr, int snr_index, int64_t frame0, int B, int level, int mode, int n_labels, int64_t *hist, int64_t hist_cap,
                                         int32_t *n_dumps) {
-    const ChannelCellTable cells = channel_cells_at(*C, snr);
-    const lutldpc_channel_cells view = cells.view();
+    PointCells pc;
+    if (int rc = point_cells(snr, snr_index, pc)) return rc;
     const uint64_t seed = (uint64_t)(int64_t)(rand_seed + rand_seed_offset);
     if (!zero_codeword && !encoder_set) throw std::runtime_error("Non zero codewords require the encoder to be set!");
     lutldpc_decoder *d = C->device_handle();
     const bool device_codewords = !zero_codeword && C->has_device_generator();
     std::vector<unsigned char> codewords;
     if (!zero_codeword && !device_codewords) codewords = random_codewords(*C, seed, (uint32_t)snr_index, (uint64_t)frame0, B, codeword_length, dataword_length);
-    return lutldpc_decoder_sim_batch_histogram(d, &view, seed, (uint32_t)snr_index, (uint64_t)frame0, B, codewords.empty() ? nullptr : codewords.data(),
+    return lutldpc_decoder_sim_batch_histogram(d, pc.cells(), seed, (uint32_t)snr_index, (uint64_t)frame0, B, codewords.empty() ? nullptr : codewords.data(),
                                                device_codewords ? 1 : 0, level, mode, n_labels, hist, hist_cap, n_dumps);
 }
 
 // the frames of sim_batch -- same seed, same stream, same codewords, made where sim_batch makes them -- with the failed ones captured
 int LDPC_BER_Sim_LUT::error_events(double snr, int snr_index, int64_t frame0, int B, lutldpc_event_request *req) {
-    const ChannelCellTable cells = channel_cells_at(*C, snr);
-    const lutldpc_channel_cells view = cells.view();
+    PointCells pc;
+    if (int rc = point_cells(snr, snr_index, pc)) return rc;
     const uint64_t seed = (uint64_t)(int64_t)(rand_seed + rand_seed_offset);
     if (!zero_codeword && !encoder_set) throw std::runtime_error("Non zero codewords require the encoder to be set!");
     const bool device_codewords = !zero_codeword && decoder_output_verbosity <= 1 && C->has_device_generator();
     std::vector<unsigned char> codewords;
     if (!zero_codeword && !device_codewords) codewords = random_codewords(*C, seed, (uint32_t)snr_index, (uint64_t)frame0, B, codeword_length, dataword_length);
     std::vector<int32_t> stats((size_t)B * 4);
-    return lutldpc_decoder_sim_batch_events(C->device_handle(), &view, seed, (uint32_t)snr_index, (uint64_t)frame0, B, codewords.empty() ? nullptr : codewords.data(),
+    return lutldpc_decoder_sim_batch_events(C->device_handle(), pc.cells(), seed, (uint32_t)snr_index, (uint64_t)frame0, B, codewords.empty() ? nullptr : codewords.data(),
                                             device_codewords ? 1 : 0, dataword_length, stats.data(), req);
 }
 
@@ -503,6 +611,8 @@ LDPC_BER_Sim_BP::LDPC_BER_Sim_BP(const std::string &params, const std::string &b
     // device: the cell sampler of include/lut_ldpc_bp.h on the uniforms of the [LUT] back-end -- another random stream
     front_end = ini.get("BP.front_end", "host");
     if (front_end != "host" && front_end != "device") throw std::runtime_error("BP.front_end must be host or device");
+    if (!node_classes_filename.empty())
+        throw std::runtime_error("Channel.node_classes_filename / Channel.class_snr_offset_dB: the [BP] front end has no per-node channel classes; they exist for [LUT] simulations only");
 }
 
 LDPC_BER_Sim_BP::~LDPC_BER_Sim_BP() { if (dec) lutldpc_bp_destroy(dec); }

@@ -38,6 +38,8 @@ public:
     std::vector<int64_t> sim_Nframes, sim_Ndatabits, sim_frame_errors, sim_data_bit_errors, sim_uncoded_bit_errors;
     int ldpc_nvar = 0, ldpc_nchk = 0;
     double ldpc_code_rate = 0, runtime = 0;
+    // written only where the parameter file gave the two Channel keys: the class of every node, the SNR offset of every class
+    std::vector<double> channel_node_classes, channel_class_snr_offset_dB;
 };
 
 // The received-value partition handed to the device sampler (see kernels_frontend.hpp).
@@ -71,6 +73,33 @@ BpCellTable make_bp_awgn_cells(int d1, int d4, double N0);
 inline double noise_n0(double snr_db, double code_rate) { return std::pow(10.0, -snr_db / 10.0) / code_rate; }
 // the cell table of codec C at this SNR
 ChannelCellTable channel_cells_at(const LDPC_Code_LUT &C, double snr_db);
+
+// Per-node channel classes as the codec layer holds them (include/lut_ldpc_host.h: lutldpc_codec_set_node_channels; ber_sim:
+// Channel.node_classes_filename / Channel.class_snr_offset_dB): the class of every node and, per class, an SNR offset in dB.  The
+// table of class c at an SNR point is that of the code at snr_db + offset_db[c]; -inf is a punctured node (an erasure), +inf a
+// known bit.  Nothing else is rescaled: N0 stays noise_n0(snr, code rate), a user who punctures accounts for the effective rate.
+struct NodeChannelClasses {
+    std::vector<uint8_t> node_class;     // nvar ids, in the decoder's column order
+    std::vector<double> offset_db;       // empty = no classes
+    bool set() const { return !offset_db.empty(); }
+};
+// throws std::invalid_argument: n_classes outside 1 .. LUTLDPC_MAX_NODE_CLASSES, a NaN offset, an id >= n_classes; `what` opens the message
+void check_node_channel_classes(const uint8_t *node_class, int nvar, int n_classes, const double *offset_db, const std::string &what);
+// channel_cells_at(C, snr_db + offset_db) and its two limits, the limits of make_channel_cells:
+//   -inf  two cells, thr = {2^63}: x = 0- (cha = #{qb_Cha < 0}, neg = 1) and x = 0+ (cha = #{qb_Cha <= 0}, neg = 0)
+//   +inf  one cell: the top labels, neg = 0
+// msg counts qb_Msg the same way (CONT) or is map[cha] (QCHA); mirrors as make_channel_cells makes them
+ChannelCellTable node_channel_cells_at(const LDPC_Code_LUT &C, double snr_db, double offset_db);
+// The cells the four codec entries that sample hand to the decoder for one SNR point: without classes the code's one table;
+// with classes the per-class tables are set on the handle (lutldpc_decoder_set_node_channels) and cells() is NULL.
+struct PointCells {
+    const lutldpc_channel_cells *cells() const { return classes ? nullptr : &view; }
+    ChannelCellTable one;
+    lutldpc_channel_cells view{};
+    bool classes = false;
+};
+// returns the code of the setter (LUTLDPC_OK without classes); `pc` must stay where it is while its cells() are in use
+int set_point_cells(LDPC_Code_LUT &C, const NodeChannelClasses &nc, double snr_db, PointCells &pc);
 
 // Philox4x32-10 block of (counter, seed): the host twin of the device generator (kernels_frontend.hpp)
 void philox4x32_10(uint32_t (&counter)[4], uint64_t seed);
@@ -146,6 +175,10 @@ public:
     std::string custom_name, results_prefix = "RES", results_dir = "results", codes_dir = "codes", codec_filename, parity_filename;
     bool zero_codeword = true, save_permuted = false, parity_check_iter = true;
     std::string generator_form = "auto";     // LDPC.generator_form: auto (dense where the matrix is small enough, else sparse) or sparse
+    // Channel.node_classes_filename (a text file of nvar class ids under codes_dir) and Channel.class_snr_offset_dB (one offset per
+    // class; inf = known bit, -inf = punctured): both or neither.  [LUT] only; the ids are read by load(), which knows nvar
+    std::string node_classes_filename;
+    vec class_snr_offset_dB;
     int max_iter = 30;
     LDPC_BER_Sim_Results results;
     // build-side knobs
@@ -188,8 +221,15 @@ public:
     int known_rank = 0;              // LDPC.known_rank (build-side: skip the GF(2) rank computation)
 
 private:
+    void load_node_classes();        // Channel.node_classes_filename -> node_channels, checked against nvar and the offsets
+    // set_point_cells once per SNR point: the class tables depend on the point alone, so a batch of the point that the handle
+    // already holds the tables of sets nothing (as LDPC_BER_Sim_BP keeps one cell table per point)
+    int point_cells(double snr, int snr_index, PointCells &pc);
+    const lutldpc_decoder *classes_on = nullptr;     // the handle and the point whose class tables it holds
+    int classes_snr_index = -1;
     std::string trees_path;
     std::unique_ptr<LDPC_Code_LUT> C;
+    NodeChannelClasses node_channels;
 };
 
 // BPSK over AWGN in double precision on the host, Philox-addressed per (seed, stream = SNR index, frame, bit pair), Box-Muller:

@@ -17,6 +17,7 @@ struct lutldpc_codec {
     std::unique_ptr<LDPC_Parity> H;
     std::unique_ptr<LDPC_Generator_Systematic> G;
     std::unique_ptr<LDPC_Code_LUT> C;
+    NodeChannelClasses nc;      // lutldpc_codec_set_node_channels
 };
 
 extern "C" void lutldpc_set_last_error(const char *msg);   // decoder.hip
@@ -183,14 +184,14 @@ int lutldpc_codec_sim_batch(lutldpc_codec *c, double snr_db, uint64_t seed, uint
     return guarded([&] {
         if (!c || !stats || B <= 0) throw std::invalid_argument("NULL / bad argument");
         if (int rc = lutldpc_check_stream(stream)) return rc;
-        const ChannelCellTable cells = channel_cells_at(*c->C, snr_db);
-        const lutldpc_channel_cells view = cells.view();
+        PointCells pc;
+        if (int rc = set_point_cells(*c->C, c->nc, snr_db, pc)) return rc;
         // random codewords: made on the device (dense generators beyond the device encoder's size whose H has no sparse form: on the host)
         if (!zero_codeword && c->C->has_device_generator())
-            return lutldpc_decoder_sim_batch_random(c->C->device_handle(), &view, seed, stream, frame0, B, c->C->get_ninfo(), stats, nullptr, nullptr);
+            return lutldpc_decoder_sim_batch_random(c->C->device_handle(), pc.cells(), seed, stream, frame0, B, c->C->get_ninfo(), stats, nullptr, nullptr);
         std::vector<unsigned char> cw;
         if (!zero_codeword) cw = random_codewords(*c->C, seed, stream, frame0, B, c->C->get_nvar(), c->C->get_ninfo());
-        return lutldpc_decoder_sim_batch(c->C->device_handle(), &view, seed, stream, frame0, B, zero_codeword ? nullptr : cw.data(), c->C->get_ninfo(), stats, nullptr, nullptr);
+        return lutldpc_decoder_sim_batch(c->C->device_handle(), pc.cells(), seed, stream, frame0, B, zero_codeword ? nullptr : cw.data(), c->C->get_ninfo(), stats, nullptr, nullptr);
     });
 }
 
@@ -199,14 +200,14 @@ int lutldpc_codec_message_histogram(lutldpc_codec *c, double snr_db, uint64_t se
     return guarded([&] {
         if (!c || !hist || B <= 0) throw std::invalid_argument("NULL / bad argument");
         if (int rc = lutldpc_check_stream(stream)) return rc;
-        const ChannelCellTable cells = channel_cells_at(*c->C, snr_db);
-        const lutldpc_channel_cells view = cells.view();
+        PointCells pc;
+        if (int rc = set_point_cells(*c->C, c->nc, snr_db, pc)) return rc;
         lutldpc_decoder *d = c->C->device_handle();
         // the sent codewords as lutldpc_codec_sim_batch chooses them: device encoder where the generator is there, else the host's
         const bool on_device = !zero_codeword && c->C->has_device_generator();
         std::vector<unsigned char> cw;
         if (!zero_codeword && !on_device) cw = random_codewords(*c->C, seed, stream, frame0, B, c->C->get_nvar(), c->C->get_ninfo());
-        return lutldpc_decoder_sim_batch_histogram(d, &view, seed, stream, frame0, B, cw.empty() ? nullptr : cw.data(), on_device ? 1 : 0, level, mode, n_labels,
+        return lutldpc_decoder_sim_batch_histogram(d, pc.cells(), seed, stream, frame0, B, cw.empty() ? nullptr : cw.data(), on_device ? 1 : 0, level, mode, n_labels,
                                                    hist, hist_cap, n_dumps);
     });
 }
@@ -216,14 +217,14 @@ int lutldpc_codec_error_events(lutldpc_codec *c, double snr_db, uint64_t seed, u
     return guarded([&] {
         if (!c || !req || B <= 0) throw std::invalid_argument("NULL / bad argument");
         if (int rc = lutldpc_check_stream(stream)) return rc;
-        const ChannelCellTable cells = channel_cells_at(*c->C, snr_db);
-        const lutldpc_channel_cells view = cells.view();
+        PointCells pc;
+        if (int rc = set_point_cells(*c->C, c->nc, snr_db, pc)) return rc;
         // the sent codewords as lutldpc_codec_sim_batch chooses them
         const bool on_device = !zero_codeword && c->C->has_device_generator();
         std::vector<unsigned char> cw;
         if (!zero_codeword && !on_device) cw = random_codewords(*c->C, seed, stream, frame0, B, c->C->get_nvar(), c->C->get_ninfo());
         std::vector<int32_t> stats((size_t)B * 4);
-        return lutldpc_decoder_sim_batch_events(c->C->device_handle(), &view, seed, stream, frame0, B, cw.empty() ? nullptr : cw.data(), on_device ? 1 : 0,
+        return lutldpc_decoder_sim_batch_events(c->C->device_handle(), pc.cells(), seed, stream, frame0, B, cw.empty() ? nullptr : cw.data(), on_device ? 1 : 0,
                                                 c->C->get_ninfo(), stats.data(), req);
     });
 }
@@ -243,12 +244,12 @@ int lutldpc_codec_sample_labels(lutldpc_codec *c, double snr_db, uint64_t seed, 
     return guarded([&] {
         if (!c || !cha || !msg0 || B <= 0) throw std::invalid_argument("NULL / bad argument");
         if (int rc = lutldpc_check_stream(stream)) return rc;
-        const ChannelCellTable cells = channel_cells_at(*c->C, snr_db);
-        const lutldpc_channel_cells view = cells.view();
+        PointCells pc;
+        if (int rc = set_point_cells(*c->C, c->nc, snr_db, pc)) return rc;
         std::vector<unsigned char> cw;
         if (!zero_codeword) cw = random_codewords(*c->C, seed, stream, frame0, B, c->C->get_nvar(), c->C->get_ninfo());
         if (codewords) { if (zero_codeword) std::memset(codewords, 0, (size_t)B * c->C->get_nvar()); else std::memcpy(codewords, cw.data(), cw.size()); }
-        return lutldpc_decoder_sample_labels(c->C->device_handle(), &view, seed, stream, frame0, B, zero_codeword ? nullptr : cw.data(), cha, msg0);
+        return lutldpc_decoder_sample_labels(c->C->device_handle(), pc.cells(), seed, stream, frame0, B, zero_codeword ? nullptr : cw.data(), cha, msg0);
     });
 }
 
@@ -260,6 +261,34 @@ int lutldpc_codec_channel_cells(lutldpc_codec *c, double snr_db, uint64_t *thr, 
         n = (int)t.cha.size();
         if (n > 72) throw std::invalid_argument("more than 72 cells");
         std::memcpy(thr, t.thr.data(), sizeof(uint64_t) * t.thr.size());
+        std::memcpy(cha, t.cha.data(), (size_t)n); std::memcpy(msg, t.msg.data(), (size_t)n); std::memcpy(neg, t.neg.data(), (size_t)n);
+        std::memcpy(cha_m, t.cha_m.data(), (size_t)n); std::memcpy(msg_m, t.msg_m.data(), (size_t)n);
+        return LUTLDPC_OK;
+    });
+    return rc == LUTLDPC_OK ? n : rc;
+}
+
+int lutldpc_codec_set_node_channels(lutldpc_codec *c, const uint8_t *node_class, int n_classes, const double *offset_db) {
+    return guarded([&] {
+        if (!c) throw std::invalid_argument("NULL codec");
+        if (n_classes == 0) { c->nc = NodeChannelClasses(); return LUTLDPC_OK; }
+        const int nvar = c->C->get_nvar();
+        check_node_channel_classes(node_class, nvar, n_classes, offset_db, "lutldpc_codec_set_node_channels");
+        c->nc.node_class.assign(node_class, node_class + nvar);
+        c->nc.offset_db.assign(offset_db, offset_db + n_classes);
+        return LUTLDPC_OK;
+    });
+}
+
+int lutldpc_codec_node_channel_cells(lutldpc_codec *c, double snr_db, int cls, uint64_t *thr, uint8_t *cha, uint8_t *msg, uint8_t *neg, uint8_t *cha_m, uint8_t *msg_m) {
+    int n = 0;
+    int rc = guarded([&] {
+        if (!c || !thr || !cha || !msg || !neg || !cha_m || !msg_m) throw std::invalid_argument("NULL argument");
+        if (cls < 0 || cls >= (int)c->nc.offset_db.size()) throw std::invalid_argument("class outside the " + std::to_string(c->nc.offset_db.size()) + " classes set");
+        const ChannelCellTable t = node_channel_cells_at(*c->C, snr_db, c->nc.offset_db[(size_t)cls]);
+        n = (int)t.cha.size();
+        if (n > 72) throw std::invalid_argument("more than 72 cells");
+        std::memcpy(thr, t.thr.data(), sizeof(uint64_t) * (size_t)(n - 1));
         std::memcpy(cha, t.cha.data(), (size_t)n); std::memcpy(msg, t.msg.data(), (size_t)n); std::memcpy(neg, t.neg.data(), (size_t)n);
         std::memcpy(cha_m, t.cha_m.data(), (size_t)n); std::memcpy(msg_m, t.msg_m.data(), (size_t)n);
         return LUTLDPC_OK;

@@ -37,7 +37,10 @@ def _out(a, rows, width, dtype, what):
 
 
 def _cells(cells):
-    return cells if isinstance(cells, _capi.ChannelCells) else _capi.ChannelCells.from_table(cells)
+    """The `cells` argument of a sampling entry: a reference to the caller's table, or None (NULL: the node channels of the handle)."""
+    if cells is None:
+        return None
+    return C.byref(cells if isinstance(cells, _capi.ChannelCells) else _capi.ChannelCells.from_table(cells))
 
 
 class _Side:
@@ -226,7 +229,7 @@ class Decoder:
         return (rq.result(), bits, iters) if decode else rq.result()
 
     # ---- Monte-Carlo front end on the device: cell sampler, random codewords, error counters --------------------------------
-    #      cells: a _capi.ChannelCells or the dict Codec.channel_cells returns; codewords: host [B, nvar] sent bits (bit 0 of a byte
+    #      cells: a _capi.ChannelCells or the dict Codec.channel_cells returns, or None for the node channels of set_node_channels; codewords: host [B, nvar] sent bits (bit 0 of a byte
     #      counts) or None for the all-zero codeword; outputs: new arrays, or the caller's own with at least B rows
     def set_generator(self, K, R, rows):
         """The generator of the device encoder: R rows of ceil(K/64) uint64 words, K + R = nvar (replaces an earlier one)."""
@@ -246,6 +249,18 @@ class Decoder:
         buf = cols if cols.size else np.zeros(1, np.int32)          # (no terms: nothing is read, the pointer must not be null)
         check(lib.lutldpc_decoder_set_sparse_generator(self._h, int(K), int(R), _p(row_ptr, C.c_int32), _p(buf, C.c_int32)))
 
+    def set_node_channels(self, node_class, tables=None):
+        """Per-node channel classes of the sampler (lutldpc_decoder_set_node_channels): node v is sampled with tables[node_class[v]]
+        by every entry called with cells=None.  node_class: nvar ids; tables: up to 16 cell tables (dicts as Codec.channel_cells
+        returns them).  set_node_channels(None) clears."""
+        if node_class is None:
+            check(lib.lutldpc_decoder_set_node_channels(self._h, None))
+            return
+        ids = np.ascontiguousarray(node_class, np.uint8)
+        if ids.shape != (self.nvar,):
+            raise ValueError("node_class must hold one class id per node")
+        check(lib.lutldpc_decoder_set_node_channels(self._h, C.byref(_capi.NodeChannels.from_tables(ids, tables))))
+
     def encode_random(self, seed, stream, frame0, B, fetch=True, out=None):
         """The random codewords of frames frame0 .. frame0+B-1, uint8 [B, nvar]; fetch=False keeps them on the device only."""
         cw = _out(out, B, self.nvar, np.uint8, "out") if fetch else None
@@ -264,7 +279,7 @@ class Decoder:
         """(cha, msg0) as the sampler makes them for those frames."""
         cells, cw = _cells(cells), self._codewords(codewords, B)
         cha, msg = _out(cha, B, self.nvar, np.uint8, "cha"), _out(msg, B, self.nvar, np.uint8, "msg")
-        check(lib.lutldpc_decoder_sample_labels(self._h, C.byref(cells), int(seed), int(stream), int(frame0), int(B), _opt(cw, C.c_uint8),
+        check(lib.lutldpc_decoder_sample_labels(self._h, cells, int(seed), int(stream), int(frame0), int(B), _opt(cw, C.c_uint8),
                                                 _p(cha, C.c_uint8), _p(msg, C.c_uint8)))
         return cha, msg
 
@@ -277,7 +292,7 @@ class Decoder:
         stats = _out(frame_stats, B, 4, np.int32, "frame_stats")
         cha = None if cha_out is None else _out(None if cha_out is True else cha_out, B, self.nvar, np.uint8, "cha_out")
         bits = None if bits_out is None else _out(None if bits_out is True else bits_out, B, self.nvar, np.uint8, "bits_out")
-        head = (self._h, C.byref(cells), int(seed), int(stream), int(frame0), int(B))
+        head = (self._h, cells, int(seed), int(stream), int(frame0), int(B))
         tail = (int(k_info), _p(stats, C.c_int32), _opt(cha, C.c_uint8), _opt(bits, C.c_uint8))
         if random:
             if cw is not None:
@@ -292,7 +307,7 @@ class Decoder:
         cells, cw = _cells(cells), self._codewords(codewords, B)
         hist = self._hist(hist, level, n_labels)
         got = C.c_int32()
-        check(lib.lutldpc_decoder_sim_batch_histogram(self._h, C.byref(cells), int(seed), int(stream), int(frame0), int(B), _opt(cw, C.c_uint8),
+        check(lib.lutldpc_decoder_sim_batch_histogram(self._h, cells, int(seed), int(stream), int(frame0), int(B), _opt(cw, C.c_uint8),
                                                       int(device_codewords), int(level), MODES[mode] if isinstance(mode, str) else int(mode),
                                                       hist.shape[3], _p(hist, C.c_int64), hist.size, C.byref(got)))
         assert got.value == hist.shape[0]
@@ -305,7 +320,7 @@ class Decoder:
         cells, cw = _cells(cells), self._codewords(codewords, B)
         rq = _Request(self.nvar, self.nchk, select, max_frames, max_pos, max_chk, profiles)
         stats = _out(frame_stats, B, 4, np.int32, "frame_stats")
-        check(lib.lutldpc_decoder_sim_batch_events(self._h, C.byref(cells), int(seed), int(stream), int(frame0), int(B), _opt(cw, C.c_uint8),
+        check(lib.lutldpc_decoder_sim_batch_events(self._h, cells, int(seed), int(stream), int(frame0), int(B), _opt(cw, C.c_uint8),
                                                    int(device_codewords), int(self.nvar - self.nchk if k_info is None else k_info),
                                                    _p(stats, C.c_int32), C.byref(rq.c)))
         return rq.result(), stats
