@@ -74,12 +74,7 @@ int lutldpc_bp_set_cells(lutldpc_bp_decoder *d, const lutldpc_bp_cells *cells) {
     std::vector<int32_t> attr((size_t)n);
     std::vector<uint32_t> first((size_t)S + 1);
     for (int j = 0; j < n; j++) attr[(size_t)j] = cells->qllr[j] * 2 + (cells->slicer_neg[j] ? 1 : 0);     // |q| <= QMAX < 2^28
-    uint32_t k = 0;
-    for (int s = 0; s < S; s++) {
-        const uint64_t low = (uint64_t)s << (64 - lutldpc::kBpSliceBits);
-        while (k < (uint32_t)(n - 1) && thr[k] <= low) k++;
-        first[(size_t)s] = k;
-    }
+    lutldpc::slice_index<lutldpc::kBpSliceBits>(thr.data(), n - 1, first.data());
     first[(size_t)S] = (uint32_t)(n - 1);
     BP_TRY(hipSetDevice(d->device));
     BP_TRY(hipStreamSynchronize(d->stream));       // no batch of the previous table is in flight (before the uploads: nothing to release if it fails)

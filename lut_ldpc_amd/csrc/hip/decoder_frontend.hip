@@ -11,25 +11,43 @@ hipError_t preload_frontend_kernels() {
     return hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&sample_labels_kernel<1>));
 }
 
-int fill_cells(const lutldpc_channel_cells *c, const lutldpc_decoder *d, ChannelCells &C) {
+// instantiate a launch for the decoder's packing (PK) and for sent-bit rows or the all-zero codeword (SR)
+#define PACK_SENT_DISPATCH(d, sent_rows, ...)                                        \
+    do {                                                                             \
+        if (sent_rows) { constexpr bool SR = true; PACK_DISPATCH(d, __VA_ARGS__); }  \
+        else { constexpr bool SR = false; PACK_DISPATCH(d, __VA_ARGS__); }           \
+    } while (0)
+
+// a caller's cell table -> the image the sampler reads: the checks of the header's error contract, the thresholds and the packed
+// labels of the cells (what lies past them stays zero: the image is also its key in the parameter arena), the bucket index
+static int fill_table(const lutldpc_channel_cells *c, const lutldpc_decoder *d, NodeClassTable &T) {
     if (!c || !c->thr || !c->cha_label || !c->msg_label || !c->slicer_neg || !c->cha_label_mirror || !c->msg_label_mirror)
         return fail(LUTLDPC_ERR_ARG, "channel cells: NULL member");
     if (c->n_cells < 1 || c->n_cells > kMaxCells) return fail(LUTLDPC_ERR_ARG, "channel cells: n_cells outside [1,72]");
-    std::memset(&C, 0, sizeof(C));
-    C.n_cells = c->n_cells;
+    std::memset(&T, 0, sizeof(T));
+    T.n_thr = c->n_cells - 1;
     for (int j = 0; j < c->n_cells; j++) {
-        if (j < c->n_cells - 1) { C.thr[j] = c->thr[j]; if (j && c->thr[j] < c->thr[j - 1]) return fail(LUTLDPC_ERR_ARG, "channel cells: thresholds must ascend"); }
+        if (j < T.n_thr) { T.thr[j] = c->thr[j]; if (j && c->thr[j] < c->thr[j - 1]) return fail(LUTLDPC_ERR_ARG, "channel cells: thresholds must ascend"); }
         if (c->cha_label[j] >= d->Nq_Cha || c->cha_label_mirror[j] >= d->Nq_Cha || c->msg_label[j] >= d->Nq_Msg[0] || c->msg_label_mirror[j] >= d->Nq_Msg[0])
             return fail(LUTLDPC_ERR_ARG, "channel cells: label outside its alphabet");
-        C.cha[j] = c->cha_label[j]; C.msg[j] = c->msg_label[j]; C.neg[j] = c->slicer_neg[j] ? 1 : 0;
-        C.cha_m[j] = c->cha_label_mirror[j]; C.msg_m[j] = c->msg_label_mirror[j];
+        T.attr[j] = (uint32_t)c->cha_label[j] | (c->slicer_neg[j] ? 1u << 7 : 0u) | ((uint32_t)c->msg_label[j] << 8) | ((uint32_t)c->cha_label_mirror[j] << 16) |
+                    ((uint32_t)c->msg_label_mirror[j] << 24);
     }
+    slice_index<kBucketBits>(T.thr, T.n_thr, T.first);
     return LUTLDPC_OK;
 }
 
-int front_end_of(const lutldpc_channel_cells *cells, const lutldpc_decoder *d, FrontEnd &fe) {
-    fe.node_classes = !cells && d->node_channels.n > 0;
-    return fe.node_classes ? LUTLDPC_OK : fill_cells(cells, d, fe.C);
+int front_end_of(const lutldpc_channel_cells *cells, lutldpc_decoder *d, FrontEnd &fe) {
+    const lutldpc_decoder::NodeChannels &nc = d->node_channels;
+    if (!cells && nc.n > 0) {
+        fe = {reinterpret_cast<const NodeClassTable *>(nc.tables.p), nc.node_class.p, nc.n};
+        return LUTLDPC_OK;
+    }
+    NodeClassTable T;
+    if (int rc = fill_table(cells, d, T)) return rc;
+    DEV_PARAM(dT, d, T);
+    fe = {dT, nullptr, 1};
+    return LUTLDPC_OK;
 }
 
 // sampler -> d_cha_t / d_msg0_t (tile layout); stats zeroed and slicer errors accumulated.  sent_rows: the sent bits of the
@@ -38,31 +56,16 @@ int sample_tiles(lutldpc_decoder *d, const FrontEnd &fe, uint64_t seed, uint32_t
     int rc = ensure_batch(d, B);
     if (rc) return rc;
     const int Bpad = d->bpad(B), G = Bpad / d->tile(), N = d->nvar;
+    // one slot without class bytes, or the handle's classes with a byte for every node
+    if (!fe.tables || (fe.node_class ? fe.n_slots < 1 || fe.n_slots > kMaxNodeClasses || d->node_channels.node_class.n < (size_t)N : fe.n_slots != 1))
+        return fail(LUTLDPC_ERR_STATE, "sampler: no node channels on the device");
     HIP_TRY(d->d_stats.alloc((size_t)Bpad * 4));
     HIP_TRY(hipMemsetAsync(d->d_stats.p, 0, sizeof(int32_t) * (size_t)Bpad * 4, d->stream));
     Timed t(d, LUTLDPC_K_FRONTEND);
     const int ppt = 8, npairs = (N + 1) / 2;
     dim3 grid((unsigned)((npairs + 4 * ppt - 1) / (4 * ppt)), (unsigned)G);
-    if (fe.node_classes) {
-        const lutldpc_decoder::NodeChannels &nc = d->node_channels;
-        if (nc.n < 1 || !nc.tables.p || !nc.node_class.p || nc.node_class.n < (size_t)N) return fail(LUTLDPC_ERR_STATE, "sampler: no node channels on the device");
-        const NodeClassTable *tables = reinterpret_cast<const NodeClassTable *>(nc.tables.p);
-        if (sent_rows)
-            PACK_DISPATCH(d, launch_k(sample_labels_classes_kernel<PK, true>, grid, dim3(256), 0, d->stream, tables, nc.node_class.p, (uint32_t)seed, (uint32_t)(seed >> 32), stream,
-                               frame0, B, N, sent_rows, d->d_cha_t.p, d->d_msg0_t.p, d->d_stats.p, ppt));
-        else
-            PACK_DISPATCH(d, launch_k(sample_labels_classes_kernel<PK>, grid, dim3(256), 0, d->stream, tables, nc.node_class.p, (uint32_t)seed, (uint32_t)(seed >> 32), stream,
-                               frame0, B, N, sent_rows, d->d_cha_t.p, d->d_msg0_t.p, d->d_stats.p, ppt));
-        LAUNCH_CHECK();
-        return LUTLDPC_OK;
-    }
-    DEV_PARAM(dC, d, fe.C);
-    if (sent_rows)
-        PACK_DISPATCH(d, launch_k(sample_labels_kernel<PK, true>, grid, dim3(256), 0, d->stream, dC, (uint32_t)seed, (uint32_t)(seed >> 32), stream, frame0, B, N,
-                           sent_rows, d->d_cha_t.p, d->d_msg0_t.p, d->d_stats.p, ppt));
-    else
-        PACK_DISPATCH(d, launch_k(sample_labels_kernel<PK>, grid, dim3(256), 0, d->stream, dC, (uint32_t)seed, (uint32_t)(seed >> 32), stream, frame0, B, N,
-                           sent_rows, d->d_cha_t.p, d->d_msg0_t.p, d->d_stats.p, ppt));
+    PACK_SENT_DISPATCH(d, sent_rows, launch_k(sample_labels_kernel<PK, SR>, grid, dim3(256), (size_t)fe.n_slots * sizeof(NodeClassTable), d->stream, fe.tables, fe.node_class,
+                                              fe.n_slots, (uint32_t)seed, (uint32_t)(seed >> 32), stream, frame0, B, N, sent_rows, d->d_cha_t.p, d->d_msg0_t.p, d->d_stats.p, ppt));
     LAUNCH_CHECK();
     return LUTLDPC_OK;
 }
@@ -90,10 +93,7 @@ int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint6
         const int Bpad = d->bpad(B), G = Bpad / d->tile(), rpw = 64;
         const int rows = K_info > 0 ? K_info : 1;
         const dim3 grid((unsigned)((rows + 4 * rpw - 1) / (4 * rpw)), (unsigned)G);
-        if (sent_rows)
-            PACK_DISPATCH(d, launch_k(count_errors_kernel<PK, true>, grid, dim3(256), 0, d->stream, d->d_hard.p, sent_rows, B, d->nvar, K_info, d->d_iters.p, d->d_stats.p, rpw));
-        else
-            PACK_DISPATCH(d, launch_k(count_errors_kernel<PK>, grid, dim3(256), 0, d->stream, d->d_hard.p, sent_rows, B, d->nvar, K_info, d->d_iters.p, d->d_stats.p, rpw));
+        PACK_SENT_DISPATCH(d, sent_rows, launch_k(count_errors_kernel<PK, SR>, grid, dim3(256), 0, d->stream, d->d_hard.p, sent_rows, B, d->nvar, K_info, d->d_iters.p, d->d_stats.p, rpw));
         LAUNCH_CHECK();
     }
     if ((rc = copy_to_host(d, frame_stats, d->d_stats.p, sizeof(int32_t) * (size_t)B * 4))) return rc;
@@ -116,11 +116,8 @@ int lutldpc_decoder_set_node_channels(lutldpc_decoder *d, const lutldpc_node_cha
     std::vector<int> nodes((size_t)n, 0);
     if (n > 0) {
         if (!nc->tables || !nc->node_class) return fail(LUTLDPC_ERR_ARG, "node channels: NULL member");
-        for (int c = 0; c < n; c++) {
-            ChannelCells C;
-            if (int rc = fill_cells(&nc->tables[c], d, C)) return rc;
-            fill_node_class_table(C, tables[(size_t)c]);
-        }
+        for (int c = 0; c < n; c++)
+            if (int rc = fill_table(&nc->tables[c], d, tables[(size_t)c])) return rc;
         for (int v = 0; v < d->nvar; v++) {
             if (nc->node_class[v] >= n) return fail(LUTLDPC_ERR_ARG, "node channels: node_class[" + std::to_string(v) + "] outside [0, n_classes)");
             nodes[nc->node_class[v]]++;

@@ -24,6 +24,7 @@
 #include "../../../include/lut_ldpc_hip.h"
 #include "kernels_common.hpp"
 #include "kernels_fast.hpp"
+#include "kernels_frontend.hpp"     // FrontEnd, NodeClassTable
 #include "lut_program.hpp"
 #include "jit.hpp"
 #include "jit_resident.hpp"
@@ -41,7 +42,6 @@
 #include <vector>
 
 namespace lutldpc { LUTLDPC_FAST_LAUNCHERS(extern) }     // instantiated in fast_*.hip / fused_b*.hip
-namespace lutldpc { struct ChannelCells; struct FrontEnd; }      // kernels_frontend.hpp
 
 using namespace lutldpc;
 
@@ -463,12 +463,10 @@ int launch_resident(lutldpc_decoder *d, int G, int B, const FrameMajorIO *fm = n
 
 // ---- decoder_frontend.hip (home of the kernels of kernels_frontend.hpp)
 hipError_t preload_frontend_kernels();
-int fill_cells(const lutldpc_channel_cells *c, const lutldpc_decoder *d, ChannelCells &C);
-// what an entry that takes `cells` samples with: the caller's table where one is given (fill_cells), else the handle's node
-// channels, else the LUTLDPC_ERR_ARG of fill_cells for a NULL table
-int front_end_of(const lutldpc_channel_cells *cells, const lutldpc_decoder *d, FrontEnd &fe);
-// sampler -> d_cha_t / d_msg0_t, with either front end: the only place that chooses the kernel; sent_rows: the sent bits as
-// sent-bit rows (device), null = all-zero codeword
+// what an entry that takes `cells` samples with: the caller's table where one is given (checked, made into the sampler's image and
+// placed in the parameter arena), else the handle's node channels, else the LUTLDPC_ERR_ARG of the table checks for a NULL table
+int front_end_of(const lutldpc_channel_cells *cells, lutldpc_decoder *d, FrontEnd &fe);
+// sampler -> d_cha_t / d_msg0_t with the front end `fe`; sent_rows: the sent bits as sent-bit rows (device), null = all-zero codeword
 int sample_tiles(lutldpc_decoder *d, const FrontEnd &fe, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *sent_rows);
 // lutldpc_decoder_sim_batch / _random; req != null: the capture of decoder_events.hip on top (lutldpc_decoder_sim_batch_events)
 int sim_batch_impl(lutldpc_decoder *d, const lutldpc_channel_cells *cells, uint64_t seed, uint32_t stream, uint64_t frame0, int B, const uint8_t *codewords,

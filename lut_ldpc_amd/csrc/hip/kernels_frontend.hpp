@@ -23,21 +23,38 @@ namespace lutldpc {
 
 constexpr int kMaxCells = 72;      // 2*(Nq-1)+1 thresholds for Nq <= 32 ... generous
 
-struct ChannelCells {
-    int32_t n_cells;
-    int32_t pad;
-    uint64_t thr[kMaxCells];       // thr[j] = floor(2^64 * P(cell <= j | bit 0)), j < n_cells-1
-    uint8_t cha[kMaxCells];        // labels of each cell when bit 0 was sent
-    uint8_t msg[kMaxCells];
-    uint8_t neg[kMaxCells];        // 1: x < 0 (slicer decides bit 1)
-    uint8_t cha_m[kMaxCells];      // labels of the mirrored cell (bit 1 was sent: x -> -x)
-    uint8_t msg_m[kMaxCells];
-};
+constexpr int kBucketBits = 10;    // the top bits of a uniform select one of 1024 equal slices of the unit interval (cell_from_bucket)
+constexpr int kMaxNodeClasses = 16; // LUTLDPC_MAX_NODE_CLASSES: 16 tables of 1896 B = 30336 B of LDS
 
-// what an entry samples with: the caller's one table, or the per-node classes the handle holds (sample_labels_classes_kernel)
+// One cell table (lutldpc_channel_cells) as the sampler reads it, in device memory and, copied verbatim, in LDS.  Made on the host
+// by the one builder (decoder_frontend.hip: fill_table); entries past the table's own are zero.
+struct NodeClassTable {
+    uint64_t thr[kMaxCells];            // thr[j] = floor(2^64 * P(cell <= j | bit 0)), j < n_thr
+    // per cell: cha | neg << 7 | msg << 8 | cha_m << 16 | msg_m << 24 -- the labels when bit 0 was sent (< 128), neg = 1: x < 0 (the
+    // slicer decides bit 1), the labels of the mirrored cell (bit 1 was sent: x -> -x)
+    uint32_t attr[kMaxCells];
+    uint8_t first[1 << kBucketBits];    // first[bucket] = number of thresholds <= the bucket's lower end
+    int32_t n_thr, pad;                 // n_cells - 1
+};
+static_assert(sizeof(NodeClassTable) % 8 == 0, "the tables of the classes follow each other as 64-bit words");
+
+// first[s] = how many of the n ascending thresholds are <= s << (64 - BITS), the lower end of slice s of the 2^BITS equal slices
+// of the unit interval: one merge, the count never falls from one slice to the next
+template <int BITS, class T>
+inline void slice_index(const uint64_t *thr, int n, T *first) {
+    int k = 0;
+    for (int s = 0; s < (1 << BITS); s++) {
+        while (k < n && thr[k] <= (uint64_t)s << (64 - BITS)) k++;
+        first[s] = (T)k;
+    }
+}
+
+// what an entry samples with, as sample_labels_kernel takes it: the caller's one table (one slot, no class bytes) or the per-node
+// classes the handle holds (lutldpc_decoder_set_node_channels); all device memory
 struct FrontEnd {
-    ChannelCells C;
-    bool node_classes = false;
+    const NodeClassTable *tables = nullptr;
+    const uint8_t *node_class = nullptr;
+    int n_slots = 0;
 };
 
 struct Philox {
@@ -55,29 +72,14 @@ struct Philox {
     }
 };
 
-// cell index = number of thresholds <= u.  The thresholds ascend (checked on the host), so this is an upper-bound
-// binary search: 7 steps over the LDS copy of the table instead of up to 71 64-bit compares per sample.  (Used once per
-// bucket in the prologue of the sampler; the samples themselves start from their bucket's first cell, below.)
-__device__ __forceinline__ int cell_of(const uint64_t *thr_lds, int n_thr, uint64_t u) {
-    int lo = 0, n = n_thr;                    // invariant: thr[0..lo) <= u, answer in [lo, lo + n]
-#pragma unroll
-    for (int step = 0; step < 7; step++) {    // 2^7 > kMaxCells
-        const int half = n >> 1;
-        const bool right = n > 0 && u >= thr_lds[lo + half];
-        lo = right ? lo + half + 1 : lo;
-        n = right ? n - half - 1 : half;
-    }
-    return lo;
-}
-// The same cell index, found from the sample's BUCKET: the top kBucketBits bits of u select one of 1024 equal slices of the
-// unit interval, first_lds[bucket] = number of thresholds <= the slice's lower end, and the few thresholds inside the slice are
-// walked one by one (most slices hold none or one; the dense ones sit in the far tails, hit once in ~500 samples).  The
-// walk is a wave loop: it ends when no lane advances.  Same result as cell_of for every u.
-constexpr int kBucketBits = 10;
-__device__ __forceinline__ int cell_from_bucket(const uint64_t *thr_lds, const uint8_t *first_lds, int n_thr, uint64_t u) {
-    int cell = first_lds[(uint32_t)(u >> (64 - kBucketBits))];
+// cell index = number of thresholds <= u (they ascend: checked on the host), found from the sample's BUCKET: the top kBucketBits
+// bits of u select one of 1024 equal slices of the unit interval, T.first[bucket] = number of thresholds <= the slice's lower
+// end, and the few thresholds inside the slice are walked one by one (most slices hold none or one; the dense ones sit in the
+// far tails, hit once in ~500 samples).  The walk is a wave loop: it ends when no lane advances.  T: a table in LDS.
+__device__ __forceinline__ int cell_from_bucket(const NodeClassTable &T, int n_thr, uint64_t u) {
+    int cell = T.first[(uint32_t)(u >> (64 - kBucketBits))];
     for (;;) {
-        const bool adv = cell < n_thr && u >= thr_lds[cell < n_thr ? cell : 0];
+        const bool adv = cell < n_thr && u >= T.thr[cell < n_thr ? cell : 0];
         if (!__any(adv)) break;
         cell += adv ? 1 : 0;
     }
@@ -99,144 +101,37 @@ __device__ __forceinline__ uint32_t sent_bits_of_lane(const uint8_t *__restrict_
 // adds the slicer errors of each frame to stats[f][3].  One thread = 4*PACK frames x a run of
 // code-bit pairs.  SENT_ROWS: the sent bits are the sent-bit rows `sent` (never null); otherwise the
 // all-zero codeword was sent and `sent` is not read.
+// Node v is sampled with table node_class[v] of the n_slots `tables` (device memory: the argument segment stays small); a null
+// node_class is class 0 on every node, the caller's one table.  The tables live in dynamic LDS, n_slots * sizeof(NodeClassTable)
+// bytes, slot = class id; the prologue copies the images of the classes that occur among the workgroup's nodes (coalesced dwords).
+// A wave's lanes are frames of ONE node, so the class byte is read once per node as a wave-uniform value and selects the slot.
+// Every class id was checked by the setter (< n_classes = n_slots <= kMaxNodeClasses); nodes beyond N are never looked up.
 template <int PACK, bool SENT_ROWS = false>
-__global__ __launch_bounds__(256) void sample_labels_kernel(const ChannelCells *__restrict__ Cp, uint32_t seed_lo, uint32_t seed_hi, uint32_t stream, uint64_t frame0,
-                                                            int B, int N, const uint8_t *__restrict__ sent, uint8_t *__restrict__ cha_t,
-                                                            uint8_t *__restrict__ msg_t, int32_t *__restrict__ stats, int pairs_per_thread)
+__global__ __launch_bounds__(256) void sample_labels_kernel(const NodeClassTable *__restrict__ tables, const uint8_t *__restrict__ node_class, int n_slots, uint32_t seed_lo,
+                                                            uint32_t seed_hi, uint32_t stream, uint64_t frame0, int B, int N, const uint8_t *__restrict__ sent,
+                                                            uint8_t *__restrict__ cha_t, uint8_t *__restrict__ msg_t, int32_t *__restrict__ stats, int pairs_per_thread)
 {
     constexpr int F = 4 * PACK;                                     // frames per lane
-    __shared__ uint64_t thr_lds[kMaxCells];
-    __shared__ uint32_t attr_lds[kMaxCells];                        // per cell: cha | neg << 7 | msg << 8 | cha_m << 16 | msg_m << 24 (labels < 128)
-    __shared__ uint8_t first_lds[1 << kBucketBits];
-    const ChannelCells &C = *Cp;                                    // (device memory: the argument segment stays small)
-    const int n_thr = C.n_cells - 1;
-    if (threadIdx.x < kMaxCells) {
-        const int t = threadIdx.x < C.n_cells ? threadIdx.x : 0;
-        thr_lds[threadIdx.x] = C.thr[threadIdx.x < n_thr ? threadIdx.x : 0];
-        attr_lds[threadIdx.x] = (uint32_t)C.cha[t] | ((uint32_t)C.neg[t] << 7) | ((uint32_t)C.msg[t] << 8) | ((uint32_t)C.cha_m[t] << 16) | ((uint32_t)C.msg_m[t] << 24);
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < (1 << kBucketBits); t += 256)
-        first_lds[t] = (uint8_t)cell_of(thr_lds, n_thr, (uint64_t)t << (64 - kBucketBits));
-    __syncthreads();
-    const int lane = threadIdx.x & 63, g = blockIdx.y;
-    const int w = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int npairs = (N + 1) / 2;
-    int p0 = w * pairs_per_thread, p1 = p0 + pairs_per_thread;
-    if (p1 > npairs) p1 = npairs;
-    int unc[F];
-#pragma unroll
-    for (int j = 0; j < F; j++) unc[j] = 0;
-    for (int p = p0; p < p1; p++) {
-        uint32_t ca[2][PACK], ms[2][PACK];
-#pragma unroll
-        for (int h = 0; h < PACK; h++) { ca[0][h] = ca[1][h] = 0; ms[0][h] = ms[1][h] = 0; }
-        uint32_t sb[2] = {0u, 0u};
-        if constexpr (SENT_ROWS) {
-#pragma unroll
-            for (int hh = 0; hh < 2; hh++)
-                if (2 * p + hh < N) sb[hh] = sent_bits_of_lane<PACK>(sent, (size_t)g * N + 2 * p + hh, lane);
-        }
-#pragma unroll
-        for (int j = 0; j < F; j++) {
-            const int fl = (g * kWave + lane) * F + j;              // frame within the batch
-            if (fl >= B) continue;                                  // pad frames keep label 0
-            const uint64_t f = frame0 + (uint64_t)fl;
-            uint32_t c[4] = {(uint32_t)f, (uint32_t)(f >> 32), (uint32_t)p, stream};
-            Philox::gen(c, seed_lo, seed_hi);
-            const uint64_t u[2] = {((uint64_t)c[1] << 32) | c[0], ((uint64_t)c[3] << 32) | c[2]};
-#pragma unroll
-            for (int hh = 0; hh < 2; hh++) {
-                const int v = 2 * p + hh;
-                if (v >= N) continue;
-                const int cell = cell_from_bucket(thr_lds, first_lds, n_thr, u[hh]);
-                const int bit = (int)((sb[hh] >> j) & 1u);          // (no sent rows: sb stays zero)
-                const uint32_t at = attr_lds[cell], sel = bit ? at >> 16 : at;
-                const uint32_t a = sel & 0x7Fu, m = (sel >> 8) & 0xFFu;
-                // slicer decision: neg for bit 0, its mirror for bit 1 -- wrong exactly when the cell lies on the negative side
-                unc[j] += (int)((at >> 7) & 1u);
-                ca[hh][j / 4] |= a << (8 * (j & 3));
-                ms[hh][j / 4] |= m << (8 * (j & 3));
-            }
-        }
-#pragma unroll
-        for (int hh = 0; hh < 2; hh++) {
-            const int v = 2 * p + hh;
-            if (v >= N) continue;
-            *reinterpret_cast<uint32_t *>(cha_t + ((size_t)g * N + v) * kRowBytes + lane * 4) = pack_halves<PACK>(ca[hh]);
-            *reinterpret_cast<uint32_t *>(msg_t + ((size_t)g * N + v) * kRowBytes + lane * 4) = pack_halves<PACK>(ms[hh]);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < F; j++) {
-        const int fl = (g * kWave + lane) * F + j;
-        if (fl < B && unc[j]) atomicAdd(&stats[(size_t)fl * 4 + 3], unc[j]);
-    }
-}
-
-// ---- per-node channel classes (lutldpc_decoder_set_node_channels): node v is sampled with table node_class[v] -----------------
-// One class as the sampler wants it in LDS, made once by the setter: thresholds padded as sample_labels_kernel pads them, the
-// packed labels of every cell, the bucket index first[bucket] = number of thresholds <= the bucket's lower end.
-constexpr int kMaxNodeClasses = 16;     // LUTLDPC_MAX_NODE_CLASSES: 16 * (576 + 288 + 1024) B = 30208 B of static LDS
-struct NodeClassTable {
-    uint64_t thr[kMaxCells];
-    uint32_t attr[kMaxCells];           // cha | neg << 7 | msg << 8 | cha_m << 16 | msg_m << 24
-    uint8_t first[1 << kBucketBits];
-    int32_t n_thr, pad;
-};
-static_assert(sizeof(NodeClassTable) % 8 == 0, "the tables of the classes follow each other as 64-bit words");
-
-// the host twin of the prologue of sample_labels_kernel: C -> its LDS image (first[] by the same upper-bound search)
-inline void fill_node_class_table(const ChannelCells &C, NodeClassTable &T) {
-    const int n_thr = C.n_cells - 1;
-    for (int j = 0; j < kMaxCells; j++) {
-        const int t = j < C.n_cells ? j : 0;
-        T.thr[j] = C.thr[j < n_thr ? j : 0];
-        T.attr[j] = (uint32_t)C.cha[t] | ((uint32_t)C.neg[t] << 7) | ((uint32_t)C.msg[t] << 8) | ((uint32_t)C.cha_m[t] << 16) | ((uint32_t)C.msg_m[t] << 24);
-    }
-    int cell = 0;
-    for (int b = 0; b < (1 << kBucketBits); b++) {
-        const uint64_t lo = (uint64_t)b << (64 - kBucketBits);
-        while (cell < n_thr && C.thr[cell] <= lo) cell++;          // ascending thresholds: the count never falls from one bucket to the next
-        T.first[b] = (uint8_t)cell;
-    }
-    T.n_thr = n_thr; T.pad = 0;
-}
-
-// sample_labels_kernel with the table chosen per node: same grid, same uniforms, same rows and stats.  A wave's lanes are frames
-// of ONE node, so the class byte is read once per node as a wave-uniform value and becomes three LDS base offsets; the search of
-// a sample is cell_from_bucket on the class's slice.  The prologue copies the LDS images of the classes that occur among the
-// workgroup's nodes from device memory (coalesced dwords): no bucket index is built here.  Every class id was checked by the
-// setter (< n_classes <= kMaxNodeClasses); nodes beyond N are never looked up.
-template <int PACK, bool SENT_ROWS = false>
-__global__ __launch_bounds__(256) void sample_labels_classes_kernel(const NodeClassTable *__restrict__ tables, const uint8_t *__restrict__ node_class, uint32_t seed_lo,
-                                                                    uint32_t seed_hi, uint32_t stream, uint64_t frame0, int B, int N, const uint8_t *__restrict__ sent,
-                                                                    uint8_t *__restrict__ cha_t, uint8_t *__restrict__ msg_t, int32_t *__restrict__ stats, int pairs_per_thread)
-{
-    constexpr int F = 4 * PACK;                                     // frames per lane
-    constexpr int kFirstDwords = (1 << kBucketBits) / 4;
-    __shared__ uint64_t thr_lds[kMaxNodeClasses * kMaxCells];
-    __shared__ uint32_t attr_lds[kMaxNodeClasses * kMaxCells];
-    __shared__ uint32_t first_lds[kMaxNodeClasses * kFirstDwords];
-    __shared__ int32_t nthr_lds[kMaxNodeClasses];
+    constexpr int kTableDwords = sizeof(NodeClassTable) / 4;
+    extern __shared__ __attribute__((aligned(16))) NodeClassTable table_lds[];
     __shared__ uint32_t used_lds;
     const int npairs = (N + 1) / 2;
-    if (threadIdx.x == 0) used_lds = 0;
-    __syncthreads();
-    {   // the classes of the workgroup's nodes: 4 waves x pairs_per_thread pairs, two nodes each
+    uint32_t used = 1;
+    if (node_class) {   // the classes of the workgroup's nodes: 4 waves x pairs_per_thread pairs, two nodes each
+        if (threadIdx.x == 0) used_lds = 0;
+        __syncthreads();
         const int v0 = blockIdx.x * 4 * pairs_per_thread * 2, v1 = min(N, v0 + 4 * pairs_per_thread * 2);
         uint32_t mine = 0;
         for (int v = v0 + (int)threadIdx.x; v < v1; v += 256) mine |= 1u << node_class[v];
         if (mine) atomicOr(&used_lds, mine);
+        __syncthreads();
+        used = used_lds;
     }
-    __syncthreads();
-    const uint32_t used = used_lds;
-    for (int c = 0; c < kMaxNodeClasses; c++) {
+    for (int c = 0; c < n_slots; c++) {
         if (!((used >> c) & 1u)) continue;                          // (workgroup-uniform)
-        const NodeClassTable &T = tables[c];
-        if (threadIdx.x < kMaxCells) { thr_lds[c * kMaxCells + threadIdx.x] = T.thr[threadIdx.x]; attr_lds[c * kMaxCells + threadIdx.x] = T.attr[threadIdx.x]; }
-        first_lds[c * kFirstDwords + threadIdx.x] = reinterpret_cast<const uint32_t *>(T.first)[threadIdx.x];      // 256 threads = 1024 bytes
-        if (threadIdx.x == 0) nthr_lds[c] = T.n_thr;
+        const uint32_t *src = reinterpret_cast<const uint32_t *>(tables + c);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(table_lds + c);
+        for (int i = threadIdx.x; i < kTableDwords; i += 256) dst[i] = src[i];
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, g = blockIdx.y;
@@ -251,18 +146,14 @@ __global__ __launch_bounds__(256) void sample_labels_classes_kernel(const NodeCl
 #pragma unroll
         for (int h = 0; h < PACK; h++) { ca[0][h] = ca[1][h] = 0; ms[0][h] = ms[1][h] = 0; }
         uint32_t sb[2] = {0u, 0u};
-        const uint64_t *thr_c[2];
-        const uint32_t *attr_c[2];
-        const uint8_t *first_c[2];
+        const NodeClassTable *T[2];
         int n_thr[2];
 #pragma unroll
         for (int hh = 0; hh < 2; hh++) {
             const int v = 2 * p + hh;
-            const int cls = v < N ? __builtin_amdgcn_readfirstlane((int)node_class[v]) : 0;      // (the pad node of an odd N is never sampled)
-            thr_c[hh] = thr_lds + cls * kMaxCells;
-            attr_c[hh] = attr_lds + cls * kMaxCells;
-            first_c[hh] = reinterpret_cast<const uint8_t *>(first_lds) + cls * (1 << kBucketBits);
-            n_thr[hh] = v < N ? nthr_lds[cls] : 0;
+            const int cls = node_class && v < N ? __builtin_amdgcn_readfirstlane((int)node_class[v]) : 0;      // (the pad node of an odd N is never sampled)
+            T[hh] = table_lds + cls;
+            n_thr[hh] = v < N ? T[hh]->n_thr : 0;
             if constexpr (SENT_ROWS) { if (v < N) sb[hh] = sent_bits_of_lane<PACK>(sent, (size_t)g * N + v, lane); }
         }
 #pragma unroll
@@ -277,10 +168,11 @@ __global__ __launch_bounds__(256) void sample_labels_classes_kernel(const NodeCl
             for (int hh = 0; hh < 2; hh++) {
                 const int v = 2 * p + hh;
                 if (v >= N) continue;
-                const int cell = cell_from_bucket(thr_c[hh], first_c[hh], n_thr[hh], u[hh]);
+                const int cell = cell_from_bucket(*T[hh], n_thr[hh], u[hh]);
                 const int bit = (int)((sb[hh] >> j) & 1u);          // (no sent rows: sb stays zero)
-                const uint32_t at = attr_c[hh][cell], sel = bit ? at >> 16 : at;
+                const uint32_t at = T[hh]->attr[cell], sel = bit ? at >> 16 : at;
                 const uint32_t a = sel & 0x7Fu, m = (sel >> 8) & 0xFFu;
+                // slicer decision: neg for bit 0, its mirror for bit 1 -- wrong exactly when the cell lies on the negative side
                 unc[j] += (int)((at >> 7) & 1u);
                 ca[hh][j / 4] |= a << (8 * (j & 3));
                 ms[hh][j / 4] |= m << (8 * (j & 3));

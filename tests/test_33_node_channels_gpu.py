@@ -1,7 +1,8 @@
-"""Per-node channel classes of the sampler on the device (lutldpc_decoder_set_node_channels, sample_labels_classes_kernel) against the
-reference of tests/node_channel_cases.py -- the one-table reference of tests/frontend_cases.py, column by column -- through the
-C-ABI: sample_labels, sim_batch, sim_batch_random, sim_batch_histogram and sim_batch_events with NULL cells, the precedence of a
-non-NULL table, clearing, refused setters; the codec layer with a punctured, a known and a 3 dB weaker class; ber_sim with the two
+"""Per-node channel classes of the sampler on the device (lutldpc_decoder_set_node_channels, sample_labels_kernel with a class byte
+per node) against the reference of tests/node_channel_cases.py -- the one-table reference of tests/frontend_cases.py, column by
+column -- through the C-ABI: sample_labels, sim_batch, sim_batch_random, sim_batch_histogram and sim_batch_events with NULL cells,
+the precedence of a non-NULL table (five tables of frontend_cases over a 16-class record), clearing, refused setters; the codec
+layer with a punctured, a known and a 3 dB weaker class; ber_sim with the two
 Channel keys through the C++ driver and the Python driver.  All integer, all equal bit for bit.  (tests/test_node_channels_cpu.py
 holds the cases to the conditions they are built for.)"""
 import ctypes as C
@@ -88,6 +89,40 @@ def test_sampler_with_node_channels_equals_the_reference_label_for_label(case, h
         assert (a[0] == b[0]).all() and (a[1] == b[1]).all()
     dec.set_node_channels(None)
     assert "node_channels" not in dec.describe()
+
+
+ONE_TABLE_NAMES = ["trivial1", "trivial2", "pins", "boundaries", "dense_q4"]
+
+
+@pytest.mark.parametrize("handle,bk", [("n33", "T+1"), ("n127_pack1", "T+1"), ("n127_pack1", "1")])
+def test_a_callers_table_over_sixteen_classes_equals_the_one_table_reference(handle, bk, handles):
+    """With the 16 classes of `mod16` on the handle, sample_labels and sim_batch with each table of frontend_cases are the one-table
+    reference frontend_cases.sample, labels and uncoded count, and NULL cells afterwards are still the class reference: the launch
+    with no class bytes and one slot of LDS next to the one with 16.  Odd N with its pad node, both row formats, a ragged batch and a
+    single frame (on n127: the 35-cell class table needs more than the 33 samples one frame of n33 has)."""
+    code, _, T = nc.HANDLES[handle]
+    dec, cd = handles(handle), fc.codec(code)
+    N, B = cd.code.nvar, fc.batch_size(bk, T)
+    seed, stream, f0 = fc.SEED_BIG, 7, fc.F_CARRY
+    u = fc.uniforms(seed, stream, f0, B, N)
+    cw = np.random.default_rng(B * 1000 + N).integers(0, 256, (B, N), dtype=np.uint8)
+    cls = nc.node_classes("mod16", N)
+    class_tables = [nc.table(name, u, cd.nq_cha, T, f0) for name in nc.LAYOUT_TABLES["mod16"]]
+    dec.set_node_channels(cls, class_tables)
+
+    def check(table, want_sent, want_zero, what):
+        cha, msg = _sample(dec, table, seed, stream, f0, B, cw)
+        _same(cha, want_sent[0], what + ": channel labels", u)
+        _same(msg, want_sent[1], what + ": message labels", u)
+        stats, cha_out, _ = _sim(dec, table, seed, stream, f0, B, None, N // 2)
+        _same(cha_out, want_zero[0], what + ": sim_batch channel labels", u)
+        assert (stats[:, 3] == want_zero[2]).all(), (what, np.flatnonzero(stats[:, 3] != want_zero[2])[:8])
+
+    for name in ONE_TABLE_NAMES:
+        one = nc.table(name, u, cd.nq_cha, T, f0)
+        check(one, fc.sample(one, seed, stream, f0, B, N, cw, u=u), fc.sample(one, seed, stream, f0, B, N, None, u=u), name)
+    check(None, nc.sample(class_tables, cls, seed, stream, f0, B, N, cw, u=u), nc.sample(class_tables, cls, seed, stream, f0, B, N, None, u=u), "classes")
+    dec.set_node_channels(None)
 
 
 def test_clearing_brings_back_the_argument_error_and_a_refused_setter_changes_nothing(handles):

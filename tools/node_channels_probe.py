@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""What the per-node channel classes cost in the sampler: sample_labels_classes_kernel against the unchanged sample_labels_kernel on
-ONE handle of the DVB-S2 code, 16384 frames per call, in one process, the variants alternating:
-  single       the caller's one table (cells != NULL): sample_labels_kernel, the baseline of this run
-  classes 1    node channels with one class: the same table on every node through sample_labels_classes_kernel
+"""What the per-node channel classes cost in the sampler: sample_labels_kernel with the handle's classes against the same kernel with
+the caller's one table, on ONE handle of the DVB-S2 code, 16384 frames per call, in one process, the variants alternating:
+  single       the caller's one table (cells != NULL): one slot in LDS, no class bytes read -- the baseline of this run
+  classes 1    node channels with one class: the same table on every node, found through the class byte of each node
   classes 4    four classes in contiguous blocks of nodes (offsets 0, -inf, +inf, -3 dB): a workgroup loads one or two tables
   classes 16   16 classes v % 16 (offsets -7.5 .. 0 dB in steps of 0.5): every workgroup loads all 16 tables, every wave changes
                its table from node to node -- the worst case
